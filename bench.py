@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DAU forward+backward hot path (BASELINE.json metric: GSamples/s = N*H*W / (t_fwd+t_bwd)).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 For N > 1 this starts N ranks itself (one per GPU, `python -m torch.distributed.run ... bench.py`), relays rank 0's one
 JSON line and exits with the ranks' return code; started under torch.distributed.run (RANK set) it is one of those ranks.
@@ -11,15 +11,26 @@ already resident in HBM.  With more than one rank the batch is sharded (weak sca
 raw parameter-gradient sums [4,S,G,F] are all-reduced over RCCL/xGMI under the dx pass and finalized after the
 exchange.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the --steps steps and prints the line; everything else it can measure or check runs
+only with --full (the parity gate, the steady-state run, the layer timing and the CPU baseline below).
+
 Extra objects in the line:
   roofline      dominant kernel's ALGORITHMIC FLOPs per pass / its average time per pass, measured live with HIP
-                events on the launch stream (dau_conv_profile_begin/_end; a pass over large offsets takes several
-                window launches, whose times add).  The operator is compute bound (1640 FLOP/B at the north-star shape,
-                SURVEY.md 8d), so the roof is the fp32 matrix/vector peak of 157.3 TFLOP/s.
-  cpu_baseline  the CPU oracle (oracle/dau_oracle.c, OpenMP) timed on this box's host cores on a small slice of the
+                events on the launch stream during the timed steps (dau_conv_profile_begin/_end; a pass over large
+                offsets takes several window launches, whose times add).  The operator is compute bound (1640 FLOP/B at
+                the north-star shape), so the roof is the fp32 matrix/vector peak of 157.3 TFLOP/s.
+                With --full it also carries steady_state_ms (--steady-seconds).
+  parity_gate   (--full, or an explicit --check) y and dx of the first images, and the parameter gradients of the first
+                output channels, against the CPU oracle before the warm-up.
+  cpu_baseline  (--full) the CPU oracle (oracle/dau_oracle.c, OpenMP) timed on this box's host cores on a small slice of the
                 same workload.  A reported baseline, not a target.
-  layer         the same step through the drop-in layer (dau_conv.DAUConv2d + autograd, default check_offsets), so that
-                the binding's host work is visible next to the ABI-level number.
+  layer         (--full) the same step through the drop-in layer (dau_conv.DAUConv2d + autograd, default check_offsets), so
+                that the binding's host work is visible next to the ABI-level number.
+
+--dump-outputs DIR writes what the last timed step computed (y, dx, dw, dmu1, dmu2, dsigma) as DIR/<name>.npy in float32:
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.  An output larger than
+DUMP_SAMPLE elements is written as a fixed, seeded sample of DUMP_SAMPLE of its elements (flat indices in ascending order,
+the same for every build), so that the files stay below 64 MB in all.
 """
 import argparse
 import hashlib
@@ -61,6 +72,7 @@ WORKLOADS = {
                label="north-star shape under max_kernel_size 65 with mu~U(-3,3) (per-call bucket selection)"),
     "small": dict(N=8, S=32, F=32, H=56, W=56, G=4, k=9, m=3.0, label="smoke-size N=8 C=32->32 HW=56 G=4"),
 }
+DUMP_SAMPLE = 1 << 21      # elements per --dump-outputs file at most (8 MiB of float32: six files stay below 64 MB)
 FP32_PEAK_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md: fp32 vector == fp32 MFMA peak
 BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (same guide; the 2:1-sparsity headline figure is not used)
 
@@ -68,8 +80,15 @@ BF16_PEAK_TFLOPS = 2500.0  # dense bf16 MFMA peak (same guide; the 2:1-sparsity 
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the parity gate against the CPU oracle (--check, unless "
+                         "--no-check), the thermal steady-state run (--steady-seconds), the layer-level timing (unless --no-layer) "
+                         "and the CPU baseline (unless --no-cpu-baseline); a plain run does none of these")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of %d elements of an output larger than that)" % DUMP_SAMPLE)
     ap.add_argument("--workload", default="ns", choices=sorted(WORKLOADS))
     ap.add_argument("--shape", default=None, help="ad-hoc workload N,S,F,H,W,G,k[,m] (overrides --workload)")
     ap.add_argument("--io", default="f32", choices=["f32", "bf16"],
@@ -91,30 +110,33 @@ def parse_args():
                     help="capture one step into a HIP graph and time its replays (single rank; no per-kernel events, so the "
                          "line carries no roofline object: a launch-overhead probe for the small workloads)")
     ap.add_argument("--algo", type=int, default=0, help="0 auto, 1 direct, 2 tiled")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-layer", action="store_true", help="skip the layer-level (DAUConv2d + autograd) timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-layer", action="store_true", help="with --full: skip the layer-level (DAUConv2d + autograd) timing")
     ap.add_argument("--offsets", default="uniform", metavar="uniform|grid[:JITTER]",
                     help="offset distribution: uniform = mu ~ U(-m, m) per unit (the reference tests' and BASELINE's synthetic "
                          "data; the worst case for the binned large-offset kernels), grid = the units of every channel pair on "
                          "the regular grid the reference layer initialises them on (DAUGridMean) + U(-JITTER, JITTER), default 1")
     ap.add_argument("--check", type=int, default=None, metavar="IMAGES",
-                    help="parity gate before timing: y and dx of the first IMAGES images against the CPU oracle (default 1; "
-                         "--no-check: none)")
+                    help="parity gate before timing: y and dx of the first IMAGES images against the CPU oracle (default 1 "
+                         "with --full, else 0; --no-check: none)")
     ap.add_argument("--check-params", type=int, default=None, metavar="CHANNELS",
                     help="with --check: also dw, dmu1, dmu2, dsigma of the first CHANNELS output channels (sums over the WHOLE "
                          "batch: the oracle runs all N images on that slice of the output channels; default 4)")
     ap.add_argument("--no-check", action="store_true", help="no parity gate in front of the timing (the line then says parity_gate: null)")
-    ap.add_argument("--steady-seconds", type=float, default=8.0,
+    ap.add_argument("--steady-seconds", type=float, default=None,
                     help="after the timed steps, keep stepping for about this long (at most 200 steps) and report the mean step "
                          "time of that run as roofline.steady_state_ms: the kernels are power limited and the headline's few "
-                         "steps are over before the chip has warmed up (0: skip)")
+                         "steps are over before the chip has warmed up (default 8 with --full, else 0: skip)")
     args = ap.parse_args()
-    # the gate is ON by default (about 1.5 s of oracle time at the north-star size, before the warm-up): the driver's fixed
-    # command line must carry a parity verdict too
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.steady_seconds is None:
+        args.steady_seconds = 8.0 if args.full else 0.0
+    # with --full the gate is ON by default (about 1.5 s of oracle time at the north-star size, before the warm-up)
     if args.no_check:
         args.check, args.check_params = 0, 0
     else:
-        args.check = 1 if args.check is None else args.check
+        args.check = (1 if args.full else 0) if args.check is None else args.check
         args.check_params = (4 if args.check > 0 else 0) if args.check_params is None else args.check_params
     return args
 
@@ -193,6 +215,25 @@ def measured_traffic(workload_key, io, dominant, split_r=0):
     if not fam or "hbm_bytes_per_pass" not in fam:
         return None, "dominant kernel not in the committed PMC pass"
     return round(fam["hbm_bytes_per_pass"] / 1e9, 3), "profiles/r4_pmc_traffic.json (2*FETCH_SIZE + WRITE_SIZE, separate passes)"
+
+
+def dump_outputs(out_dir, outs):
+    """DIR/<name>.npy (float32) of the outputs of one step; an output of more than DUMP_SAMPLE elements as the elements at
+    DUMP_SAMPLE flat indices drawn with a fixed seed (sorted; the same indices for every build and every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    samples = {}
+    for name, t in zip(("y", "dx", "dw", "dmu1", "dmu2", "dsigma"), outs):
+        if t is None:                          # a gradient the step did not ask for (--no-dsigma)
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            if t.numel() not in samples:
+                idx = np.sort(np.random.default_rng(20240601).choice(t.numel(), DUMP_SAMPLE, replace=False))
+                samples[t.numel()] = torch.from_numpy(idx).to(t.device)
+            t = t.reshape(-1)[samples[t.numel()]]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -297,6 +338,7 @@ def main():
     exchange = OverlappedBackward((1, S, G, F), dev) if use_dist else None
 
     last_grads = [None]
+    last_out = [None]                          # (y, dx, dw, dmu1, dmu2, dsigma) of the most recent step, for --dump-outputs
     need_mask = _capi.NEED_ALL & ~_capi.NEED_DSIGMA if args.no_dsigma else _capi.NEED_ALL
 
     def step():
@@ -307,10 +349,11 @@ def main():
             dx = exchange.run(lambda out: plan.backward_param_sums(x, dy, mu1, mu2, sigma, out=out),
                               lambda: plan.backward(x, dy, w, mu1, mu2, sigma, need_mask=_capi.NEED_DX)[0],
                               lambda sums: plan.finalize_param_grads(sums, w))
-            exchange.wait()
+            last_out[0] = (y, dx) + tuple(exchange.wait())
         else:
             last_grads[0] = plan.backward(x, dy, w, mu1, mu2, sigma, need_mask=need_mask)
             dx = last_grads[0][0]
+            last_out[0] = (y,) + tuple(last_grads[0])
         return y, dx
 
     def fence():
@@ -404,6 +447,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0].item())
         exposed_ms = float(t[1].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out[0])
     # thermal steady state: NOT part of the headline (value / ms_per_step come from exactly --steps steps above); the same
     # step repeated for several seconds, timed as a whole
     steady = None
@@ -490,7 +535,7 @@ def main():
     # the same step through the drop-in layer: DAUConv2d + autograd with its default offset check ("async": the previous
     # call's status is read from pinned host memory, no sync) -- what a model built on the Python surface pays
     layer = None
-    if rank == 0 and world == 1 and not args.no_layer and ignore == 0 and not args.dense:
+    if args.full and rank == 0 and world == 1 and not args.no_layer and ignore == 0 and not args.dense:
         import dau_conv
         torch.cuda.empty_cache()
         lay = dau_conv.DAUConv2d(filters=F, dau_units=(1, G), max_kernel_size=k, use_bias=False, in_channels=S,
@@ -520,7 +565,7 @@ def main():
         del lay, xl
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import dau_oracle as orc
         # bounded sample (about 8 s of CPU work at the ~6e10 FLOP/s the oracle reaches on the box's cores, so that the run
         # stays GPU-dominated): whole images of the same batch; where one image is already too much (512 x 512 maps), the

@@ -119,8 +119,10 @@ def test_plan_cache_keys_on_the_prefilter_support_and_is_bounded():
     import importlib
     dc = importlib.import_module("dau_conv.dau_conv")        # (the package attribute of that name is the op function)
     dc._PLANS.clear()
-    x = torch.zeros(2, 3, 8, 9)
-    w = torch.zeros(1, 3, 2, 4)
+    # the plan is made for the input's device: where a GPU is visible that must be a GPU tensor (no kernel runs either way)
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    x = torch.zeros(2, 3, 8, 9, device=dev)
+    w = torch.zeros(1, 3, 2, 4, device=dev)
     st = lambda sigma: dc._settings(torch.full((1,), sigma), num_output=4, kernel_size=9)
     first = dc._get_plan(x, w, st(0.5))
     for i in range(1, 40):
@@ -129,7 +131,7 @@ def test_plan_cache_keys_on_the_prefilter_support_and_is_bounded():
     other = dc._get_plan(x, w, st(0.61))                               # 2*ceil(3.05)+1 = 9: another plan
     assert other is not first and other.info["blur_support"] == 9 and len(dc._PLANS) == 2
     for h in range(8, 8 + dc._PLAN_CACHE_MAX + 10):                    # many shapes: least recently used plans are dropped
-        dc._get_plan(torch.zeros(2, 3, h, 9), w, st(0.5))
+        dc._get_plan(torch.zeros(2, 3, h, 9, device=dev), w, st(0.5))
     assert len(dc._PLANS) == dc._PLAN_CACHE_MAX
     dc._PLANS.clear()
 
