@@ -101,6 +101,10 @@ struct BucketSet {
     bool split_ok[3] = {false, false, false};
     DenseConfig split_fwd[3], split_dx[3];
     bool any_split() const { return split_ok[0] || split_ok[1] || split_ok[2]; }
+    // bucket 4 only: calls whose offsets lie within +-4 run the parameter gradients as the two-limb f16 GEMM with the bilinear
+    // corners as rows (k_split_dot.hip: fp32 accuracy); the call's device guard (-1, 4] decides, the exact gather-dot takes the rest
+    bool sdot_ok = false;
+    SplitDotConfig sdot;
     // Batch slabs.  Every pass stages its whole input before it gathers; where that staged copy would exceed the workspace
     // budget (DAU_WORKSPACE_BUDGET_GB at plan creation, default 12: only the 512 x 512 configurations get there) the pass
     // runs slab by slab over the batch -- the configs above are made for `slab_*` images, the passes loop -- so that the
@@ -202,6 +206,7 @@ struct Candidate {
     Guard guard;
     bool r3 = false;          // the set's radius-3 dense bf16 member (sets[0] only)
     int split_r = 0;          // 2, 3, 4: the set's two-limb f16 dense member of that radius (sets[0], gather-sum passes only)
+    bool sdot = false;        // the set's two-limb f16 gather-dot member (sets[0], parameter-gradient pass only)
 };
 
 // dau_conv_last_status has just reported the whole mirror: forget it, sticky record included.
@@ -233,7 +238,8 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int pass_k
     const BucketSet& s0 = p->sets[0];
     const bool d3 = pass_kind == 0 ? s0.dense3_ok : s0.wgrad3_ok;
     const bool split = pass_kind == 0 && s0.any_split();
-    if (p->nsets < 2 && !d3 && !split) return 1;
+    const bool sdot = pass_kind == 1 && s0.sdot_ok;
+    if (p->nsets < 2 && !d3 && !split && !sdot) return 1;
     const BucketSet* dense = (pass_kind == 0 ? s0.dense_ok : s0.wgrad_ok) ? &s0 : nullptr;
     const BucketSet* hinted = nullptr;
     if (p->host_status && p->nsets >= 2) {
@@ -256,6 +262,7 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int pass_k
     if (split)
         for (int r = 2; r <= 4; ++r)
             if (s0.split_ok[r - 2]) { out[n] = Candidate{&s0, Guard{dev_status, lo, (float)r}}; out[n++].split_r = r; lo = (float)r; }
+    if (sdot) { out[n] = Candidate{&s0, Guard{dev_status, lo, 4.0f}}; out[n++].sdot = true; lo = 4.0f; }
     if (d3) { out[n] = Candidate{&s0, Guard{dev_status, lo, 3.0f}}; out[n++].r3 = true; lo = 3.0f; }
     if (dense && hinted != dense && dense != top) { out[n++] = Candidate{dense, Guard{dev_status, lo, (float)dense->bucket}}; lo = (float)dense->bucket; }
     if (hinted && lo < (float)hinted->bucket) { out[n++] = Candidate{hinted, Guard{dev_status, lo, (float)hinted->bucket}}; lo = (float)hinted->bucket; }
@@ -282,6 +289,7 @@ int ensure_attrs(const dau_conv_plan* p) {
         if (p->sets[i].wgrad_ok) r4::dense_wgrad_init(p->sets[i].wgrad);
         if (p->sets[i].dense3_ok) { r3::dense_gather_init(p->sets[i].dense3_fwd); r3::dense_gather_init(p->sets[i].dense3_dx); }
         if (p->sets[i].wgrad3_ok) r3::dense_wgrad_init(p->sets[i].wgrad3);
+        if (p->sets[i].sdot_ok) split_dot_init(p->sets[i].sdot);
         for (int r = 0; r < 3; ++r)
             if (p->sets[i].split_ok[r]) { kSplit[r].init(p->sets[i].split_fwd[r]); kSplit[r].init(p->sets[i].split_dx[r]); }
         const hipError_t e = hipGetLastError();
@@ -354,6 +362,7 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
         for (int i = 0; i < p->nsets; ++i) {
             if (p->sets[i].wgrad_ok) need = std::max(need, r4::dense_wgrad_workspace_bytes(p->sets[i].wgrad));
             if (p->sets[i].wgrad3_ok) need = std::max(need, r3::dense_wgrad_workspace_bytes(p->sets[i].wgrad3));
+            if (p->sets[i].sdot_ok) need = std::max(need, split_dot_workspace_bytes(p->sets[i].sdot));
         }
         w.tiled_dot = c.take<char>(need);
     } else {
@@ -498,6 +507,15 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             bs.wgrad3_ok = bs.wgrad_ok && bs.dense3_ok && r3::dense_wgrad_configure(s, blur_k, bf16, &bs.wgrad3) &&
                            (double)r3::dense_wgrad_workspace_bytes(bs.wgrad3) <= budget_bytes;
         }
+        {
+            // two-limb f16 gather-dot: fp32 layers, bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default
+            // where the blocks of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with
+            // DAU_FLAG_DENSE_SPLIT_F16 whatever the unit count
+            const bool interp2d = (desc->flags & DAU_FLAG_USE_INTERPOLATION) && !(desc->flags & DAU_FLAG_SINGLE_DIM_KERNEL);
+            const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
+            bs.sdot_ok = split_allowed && !bf16 && b == 4 && interp2d && bs.dot_ok && bs.slab_dot == s.N && (split_forced || fill) &&
+                         split_dot_configure(s, blur_k, bf16, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
+        }
     }
     if ((desc->flags & DAU_FLAG_DENSE_BF16) && !bf16) {
         delete p;
@@ -526,7 +544,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     // dynamic bucket selection: tiled kernels, more than one bucket (or the two radii of the dense forms), not switched off (DAU_FLAG_STATIC_BUCKET; tuning build:
     // DAU_DYNAMIC_BUCKET=0 in the environment at plan creation).  The pinned status mirror needs a device; without one
     // (header-only checks on a CPU box) the plan simply has no hint.
-    p->dynamic = (p->nsets > 1 || p->sets[0].dense3_ok || p->sets[0].any_split()) && !(desc->flags & DAU_FLAG_STATIC_BUCKET) && DAU_TUNE_INT("DAU_DYNAMIC_BUCKET", 1) != 0 &&
+    p->dynamic = (p->nsets > 1 || p->sets[0].dense3_ok || p->sets[0].any_split() || p->sets[0].sdot_ok) && !(desc->flags & DAU_FLAG_STATIC_BUCKET) && DAU_TUNE_INT("DAU_DYNAMIC_BUCKET", 1) != 0 &&
                  (p->algo_fwd == DAU_ALGO_TILED || p->algo_bwd == DAU_ALGO_TILED);
     void* hs = nullptr;
     // portable + mapped: a plan may be used on any device, and every device's prepare_units_kernel writes the mirror
@@ -692,6 +710,12 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
         for (int ci = 0; ci < ncand; ++ci) {
             const BucketSet& bs = *cand[ci].set;
             const TiledDotConfig& cfg = bs.tiled_dot;
+            if (cand[ci].sdot) {                                               // offsets within +-4: two-limb f16 GEMM, fp32 accuracy
+                split_dot_prepare(st, bs.sdot, x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, cand[ci].guard);
+                ProfScope prof(p, 2, st);
+                split_dot_run(st, bs.sdot, ws.table_bare, r4, ws.tiled_dot, cand[ci].guard);
+                continue;
+            }
             if (cand[ci].r3) {                                                 // offsets within +-3: 49 displacements
                 ProfScope prof(p, 2, st);
                 r3::dense_wgrad_run(st, bs.wgrad3, x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4, ws.tiled_dot, cand[ci].guard, kinds);

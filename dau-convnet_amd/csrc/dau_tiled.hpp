@@ -113,6 +113,27 @@ void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int
 void blur4_pack_init(int blur_k);
 bool blur4_pack_fits(int blur_k, int Hp, int Wp);
 
+// r4[k][u] = sum over the slabs of partial[slab][k][u] in double (the gather-dot's deterministic reduction, k_gather_dot.hip)
+void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, long n, int G, int F, int g_split, int slabs0,
+                       int slabs1, int zero_from, bool accumulate, float* r4, const Guard& guard);
+
+// Parameter gradients at fp32 accuracy on the f16 matrix cores (k_split_dot.hip): per input channel a GEMM with the four kinds x
+// four bilinear corners as rows, the units as columns and (position, image) as K, both operands split into two binary16 limbs.
+// Offsets within +-4, fp32 activations, interpolation on; the whole batch in one pass.
+struct SplitDotConfig {
+    Shape sh;
+    int blur_k;
+    int RW;               // region columns = K steps per item (14, 15 or 16: the least padding of the W + 1 staged columns)
+};
+bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg);
+size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);
+void split_dot_init(const SplitDotConfig& cfg);
+// prepare: fp32 derivative filtering (blur4_pack), per-channel maxima, limb staging of Xk and of the error; run: the GEMM + the
+// reduction into r4 (all four kinds; x, dy fp32 NCHW; table = bare unit table [S][G][F])
+void split_dot_prepare(hipStream_t st, const SplitDotConfig& cfg, const float* x, const float* dy, const float* filters,
+                       int drop_col, int drop_row, void* workspace, const Guard& guard);
+void split_dot_run(hipStream_t st, const SplitDotConfig& cfg, const UnitRef* table, float* r4, void* workspace, const Guard& guard);
+
 // Densified parameter gradients on the bf16 matrix cores (k_dense_wgrad.hip; DAU_FLAG_DENSE_BF16, bucket 4, bfloat16
 // activations, three or more units): C_k[d][s][f] = sum_{n,q} Xk[n,s,q+d] * E'[n,f,q] for the 9 x 9 displacements d as a GEMM
 // with K = (image, position), then r_k[u] = sum_taps b_t(u) * C_k[o_u + t].

@@ -1363,6 +1363,12 @@ void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int
     b.lds_item_floats = (unsigned)(blur_lds / 4);
     hipLaunchKernelGGL(kern, dim3((b.items + b.ppb - 1) / b.ppb), dim3(512), b.ppb * blur_lds, st, b);
 }
+void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, long n, int G, int F, int g_split, int slabs0,
+                       int slabs1, int zero_from, bool accumulate, float* r4, const Guard& guard) {
+    const int rgrid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(dot_reduce_kernel, dim3(rgrid), dim3(256), 0, st, partial, partial_f32, n, G, F, g_split, slabs0, slabs1,
+                       zero_from, accumulate ? 1 : 0, r4, guard);
+}
 void blur4_pack_init(int blur_k) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur4_pack_for(blur_k)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

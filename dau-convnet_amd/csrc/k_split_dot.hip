@@ -1,0 +1,489 @@
+// Parameter gradients (gather-dot) on the f16 matrix cores at fp32 accuracy: two-limb GEMM, bilinear corners as rows.
+//
+//   r_k[u] = sum_{n,p} E'[n,f,p] * sum_d b_d(u) Xk[n,s,k, p + o_u + d]          (u = (s, g, f), d in {0,1}^2)
+//          = sum_d b_d(u) * D[(k,d), u],   D[(k,d), u] = sum_{n,q} Xk[n,s,k, q + d] * E'[n,f, q - o_u]
+//
+// (q = p + o_u).  For one input channel s, D is a GEMM: M = 16 rows (k, d) that do not depend on the unit, N = the units of s,
+// K = (position q, image).  It runs as v_mfma_f32_16x16x32_f16 with both operands split into two binary16 limbs (hi = f16(v),
+// lo = f16(v - hi), three products hi*hi + lo*hi + hi*lo, fp32 sums), as the two-limb gather-sum does (k_dense_split.hip).
+//  * Fragments.  Lane l holds A row l % 16 = 4k + d and B column l % 16 for the K group l / 16 = one position x 8 images, and
+//    receives D rows 4(l / 16) .. +3: the four corners d of kind k = l / 16 of its unit.  The bilinear combination is lane-local.
+//  * No interpolation in the loop; the FLOPs do not depend on the offsets -- only the halo of the error window does.  One radius
+//    (4, the layer's clip of 3.99 included) serves every call within +-4.
+//  * Staging (8 images innermost, so that a 16-byte fragment is aligned at any displacement):
+//      XS[oct][s][k][Ty][Tx][limb][8 img]   Ty, Tx = image position + 1 (a zero row / column in front for the corner d = 0 of q = -1)
+//      ES[oct][fb][Vy][Vx][limb][16 f][8 img]   Vy, Vx = image position + R + 1, zero halo, the unit_testing edge rule applied
+//    Exact power-of-two scales per (s, k) and per f bring each maximum to [2^13, 2^14); the maxima are taken over finite values only
+//    (an Inf / NaN does not remove the scaling of the other channels).  The epilogue undoes them exactly.
+//  * Main kernel.  Workgroup = (chunk of (image octet, region) items, 16 output channels, 16 input channels, 4 units); region =
+//    4 rows x RW columns of q; the ES window of the 16 channels (RH + 2R rows x RW + 2R columns x 512 B) sits in LDS.  A wave owns
+//    2 input channels x 4 units = 8 tiles of 16 units (s, g, the block's 16 f) for the whole kernel.  Lane group j = row j of
+//    the region, K step = one column: every address is a per-lane base plus an immediate.
+//  * Bank conflicts.  The LDS window is position-major with the 16 output channels of a position in consecutive 16-byte groups, so
+//    the bank group of a ds_read_b128 is (lane % 16) whatever the unit's displacement: every read phase of 16 lanes touches 16
+//    distinct groups.  The unit-to-lane placement (lane % 16 = f % 16) is conflict-free by construction; no placement table.
+//  * Accuracy.  Per item a tile's accumulator chains 3 x RW MFMAs (hierarchical accumulation, as in the gather-sum); the bilinear
+//    combination joins a running fp32 sum per unit, flushed every few items into the float partial sums [chunk][4][S][G][F] with a
+//    no-return atomic add (the slot belongs to one lane: the program's order), summed over the chunks in double (dot_reduce).
+#include <algorithm>
+#include <cfloat>
+
+#include "dau_tiled.hpp"
+
+namespace dau {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f4s __attribute__((ext_vector_type(4)));
+
+namespace {
+
+constexpr int kSdWaves = 8;             // waves per workgroup (two per SIMD)
+constexpr int kSdAS = 2;                // input channels per wave (four spill the accumulators)
+constexpr int kSdGT = 4;                // units per (input channel, output channel) in one workgroup
+constexpr int kSdSB = kSdWaves * kSdAS; // input channels per workgroup
+constexpr int kSdFB = 16;               // output channels per workgroup = B columns of a tile
+constexpr int kSdR = 4;                 // offset radius of the error window
+constexpr int kSdRH = 4;                // region rows = K groups of one MFMA
+constexpr int kSdFlushItems = 16;       // items per flush of the running sums (at most 16 float additions per slot and chunk)
+
+inline size_t rup(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+struct SdGeom {
+    int Hq, Wq, rq, cq, XTr, XTc, EYs, EXs, octs, nfb, nsb, ngb, items, chunks, per, NP;
+};
+
+SdGeom sd_geom(const SplitDotConfig& c) {
+    const Shape& s = c.sh;
+    SdGeom g{};
+    g.Hq = (s.H + 1 + kSdRH - 1) / kSdRH * kSdRH;
+    g.Wq = (s.W + 1 + c.RW - 1) / c.RW * c.RW;
+    g.rq = g.Hq / kSdRH; g.cq = g.Wq / c.RW;
+    g.XTr = g.Hq + 1; g.XTc = g.Wq + 1;
+    g.EYs = g.Hq + 2 * kSdR; g.EXs = g.Wq + 2 * kSdR;
+    g.octs = (s.N + 7) / 8;
+    g.NP = (s.N + 1) / 2;
+    g.nfb = (s.F + kSdFB - 1) / kSdFB;
+    g.nsb = (s.S + kSdSB - 1) / kSdSB;
+    g.ngb = (s.G + kSdGT - 1) / kSdGT;
+    g.items = g.octs * g.rq * g.cq;
+    // about four rounds of one workgroup per CU (the LDS window leaves room for one), no chunk without items
+    const int per_chunk = g.nfb * g.nsb * g.ngb;
+    int chunks = (1024 + per_chunk - 1) / per_chunk;
+    chunks = std::max(1, std::min(chunks, g.items));
+    g.per = (g.items + chunks - 1) / chunks;
+    g.chunks = (g.items + g.per - 1) / g.per;
+    return g;
+}
+
+struct SdLayout { size_t maxes_off, xk_off, xs_off, es_off, partial_off, total; };
+
+SdLayout sd_layout(const SplitDotConfig& c, const SdGeom& g) {
+    const Shape& s = c.sh;
+    SdLayout l{};
+    size_t off = 0;
+    l.maxes_off = off; off += rup((size_t)(s.S * kNumK + s.F) * 4);
+    l.xk_off = off; off += rup((size_t)g.NP * s.S * s.H * s.W * 32);                              // blur4_pack output, fp32
+    l.xs_off = off; off += rup((size_t)g.octs * s.S * kNumK * g.XTr * g.XTc * 32);
+    l.es_off = off; off += rup((size_t)g.octs * g.nfb * g.EYs * g.EXs * 512);
+    l.partial_off = off; off += rup((size_t)g.chunks * kNumK * s.S * s.G * s.F * 4);
+    l.total = off;
+    return l;
+}
+
+// power-of-two scale exponent that brings a maximum (float bits, finite, >= 0) to [2^13, 2^14); 0 for a zero maximum
+__device__ __forceinline__ int sd_shift(unsigned maxbits) {
+    if (maxbits == 0u) return 0;
+    const int e = (int)(maxbits >> 23) - 127;          // denormal maxima count as 2^-127: the shift is clamped below
+    const int sh = 13 - e;
+    return sh > 120 ? 120 : sh;
+}
+
+__device__ __forceinline__ bool finite_abs(float v, float* a) {
+    *a = fabsf(v);
+    return *a <= FLT_MAX;
+}
+
+// max |Xk| per (input channel, kind) over the fp32 staging of blur4_pack ([NP][S][H][W][4 kinds][2 images]): grid (S, split)
+__global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restrict__ xk, int NP, int S, int HW, int split,
+                                                          unsigned* __restrict__ xmax, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const int s = blockIdx.x % S, part = blockIdx.x / S;
+    float m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const long per_np = (long)HW * 2;                    // float4 per (np, s) plane: HW positions x 8 floats / 4
+    const long total = (long)NP * per_np;
+    for (long i = part * 256L + threadIdx.x; i < total; i += 256L * split) {
+        const long np = i / per_np, r = i - np * per_np;
+        const float4 v = reinterpret_cast<const float4*>(xk + ((size_t)np * S + s) * HW * 8)[r];
+        const int k0 = (int)(r & 1) * 2;                 // float4 0 of a position: kinds 0, 1; float4 1: kinds 2, 3
+        float a;
+        if (finite_abs(v.x, &a)) m[k0] = fmaxf(m[k0], a);
+        if (finite_abs(v.y, &a)) m[k0] = fmaxf(m[k0], a);
+        if (finite_abs(v.z, &a)) m[k0 + 1] = fmaxf(m[k0 + 1], a);
+        if (finite_abs(v.w, &a)) m[k0 + 1] = fmaxf(m[k0 + 1], a);
+    }
+    // (per thread both parities of r visit the same kinds only if the stride is even: 256 * split is)
+    __shared__ float red[4][256];
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = m[k];
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = fmaxf(red[k][threadIdx.x], red[k][threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) atomicMax(&xmax[s * kNumK + threadIdx.x], __float_as_uint(red[threadIdx.x][0]));
+}
+
+// max |dy| per output channel: grid (F, split)
+__global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split,
+                                                          unsigned* __restrict__ emax, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const int f = blockIdx.x % F, part = blockIdx.x / F;
+    float m = 0.0f;
+    const long total = (long)N * HW;
+    for (long i = part * 256L + threadIdx.x; i < total; i += 256L * split) {
+        const long n = i / HW, p = i - n * HW;
+        float a;
+        if (finite_abs(dy[((size_t)n * F + f) * HW + p], &a)) m = fmaxf(m, a);
+    }
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(&emax[f], __float_as_uint(m));
+}
+
+__device__ __forceinline__ void split_limbs(float v, _Float16* hi, _Float16* lo) {
+    const _Float16 h = (_Float16)v;
+    const float hf = (float)h;
+    *hi = h;
+    *lo = (hf - hf == 0.0f) ? (_Float16)(v - hf) : (_Float16)0.0f;   // a non-finite value keeps its hi limb only
+}
+
+// XS[oct][s][k][Ty][Tx][limb][8] from the fp32 staging: one thread per (oct, s, Ty, Tx), all four kinds
+__global__ void __launch_bounds__(256) sd_stage_x_kernel(const float* __restrict__ xk, const unsigned* __restrict__ xmax, int N,
+                                                         int NP, int S, int H, int W, int octs, int XTr, int XTc,
+                                                         h8* __restrict__ xs, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const long total = (long)octs * S * XTr * XTc;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        long t = idx;
+        const int tx = (int)(t % XTc); t /= XTc;
+        const int ty = (int)(t % XTr); t /= XTr;
+        const int s = (int)(t % S);
+        const int oct = (int)(t / S);
+        const int y = ty - 1, x = tx - 1;
+        const bool in = y >= 0 && y < H && x >= 0 && x < W;
+        float v[4][8];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int np = oct * 4 + p;
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+            if (in && np < NP) {
+                const float4* src = reinterpret_cast<const float4*>(xk + ((((size_t)np * S + s) * H + y) * W + x) * 8);
+                a = src[0]; b = src[1];
+            }
+            // [k][image of the pair]: (k0 i0, k0 i1, k1 i0, k1 i1) (k2 ...)
+            v[0][2 * p] = a.x; v[0][2 * p + 1] = a.y; v[1][2 * p] = a.z; v[1][2 * p + 1] = a.w;
+            v[2][2 * p] = b.x; v[2][2 * p + 1] = b.y; v[3][2 * p] = b.z; v[3][2 * p + 1] = b.w;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float sc = ldexpf(1.0f, sd_shift(xmax[s * kNumK + k]));
+            h8 hi, lo;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                _Float16 h, l;
+                split_limbs(v[k][i] * sc, &h, &l);
+                hi[i] = h; lo[i] = l;
+            }
+            h8* dst = xs + ((((size_t)oct * S + s) * kNumK + k) * XTr * XTc + (size_t)ty * XTc + tx) * 2;
+            dst[0] = hi; dst[1] = lo;
+        }
+    }
+}
+
+// ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W]: one thread per (oct, fb, Vy, Vx), the 16 channels of the block
+__global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
+                                                         int F, int H, int W, int octs, int nfb, int EYs, int EXs, int drop_col,
+                                                         int drop_row, h8* __restrict__ es, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const long total = (long)octs * nfb * EYs * EXs;
+    const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        long t = idx;
+        const int vx = (int)(t % EXs); t /= EXs;
+        const int vy = (int)(t % EYs); t /= EYs;
+        const int fb = (int)(t % nfb);
+        const int oct = (int)(t / nfb);
+        const int y = vy - (kSdR + 1), x = vx - (kSdR + 1);
+        const bool in = y >= 0 && y < hlim && x >= 0 && x < wlim;
+        h8* dst = es + (size_t)idx * 32;
+        for (int fl = 0; fl < kSdFB; ++fl) {
+            const int f = fb * kSdFB + fl;
+            const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
+            h8 hi, lo;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int n = oct * 8 + i;
+                const float v = (in && f < F && n < N) ? dy[(((size_t)n * F + f) * H + y) * W + x] : 0.0f;
+                _Float16 h, l;
+                split_limbs(v * sc, &h, &l);
+                hi[i] = h; lo[i] = l;
+            }
+            dst[fl] = hi; dst[kSdFB + fl] = lo;
+        }
+    }
+}
+
+struct SdArgs {
+    const h8* xs;
+    const char* es;
+    const unsigned* xmax;
+    const unsigned* emax;
+    const UnitRef* table;       // bare unit table [S][G][F]
+    float* partial;             // [chunk][4][S][G][F]
+    int S, F, G;
+    int nfb, nsb, ngb, per, items, rq, cq, XTr, XTc, EYs, EXs;
+    Guard guard;
+};
+
+// RW: columns per region (K steps per item); the error window is (RH + 2R) x (RW + 2R) positions x 512 B
+template <int RW>
+__global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) split_gather_dot_kernel(const SdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (!guard_pass(a.guard)) return;
+    constexpr int WL = RW + 2 * kSdR, WR = kSdRH + 2 * kSdR;
+    int t = blockIdx.x;
+    const int gb = t % a.ngb; t /= a.ngb;
+    const int sb = t % a.nsb; t /= a.nsb;
+    const int fb = t % a.nfb; t /= a.nfb;
+    const int chunk = t;
+    const int it0 = chunk * a.per, it1 = min(it0 + a.per, a.items);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int fl = lane & 15, j = lane >> 4;
+    const int f = fb * kSdFB + fl;
+    const bool f_ok = f < a.F;
+    // A operand of this lane: row m = 4 k + d, K group j
+    const int m = lane & 15, ak = m >> 2, ady = (m >> 1) & 1, adx = m & 1;
+    const size_t xplane = (size_t)a.XTr * a.XTc;         // positions per (oct, s, k) plane
+    unsigned aoff[kSdAS];                                // lane offset (in 16-byte units) of its A row, per input channel
+    int sidx[kSdAS];
+    bool s_ok[kSdAS];
+    int base[kSdAS][kSdGT];                              // LDS byte address of the unit's B column at K step 0
+    float run[kSdAS][kSdGT];
+#pragma unroll
+    for (int i = 0; i < kSdAS; ++i) {
+        const int s = sb * kSdSB + wave * kSdAS + i;
+        s_ok[i] = s < a.S;
+        sidx[i] = s_ok[i] ? s : a.S - 1;
+        aoff[i] = (unsigned)((((size_t)sidx[i] * kNumK + ak) * xplane + (size_t)(j + ady) * a.XTc + adx) * 2);
+#pragma unroll
+        for (int gg = 0; gg < kSdGT; ++gg) {
+            const int g = gb * kSdGT + gg;
+            UnitRef u{0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+            if (s_ok[i] && g < a.G && f_ok) u = a.table[((size_t)sidx[i] * a.G + g) * a.F + f];
+            base[i][gg] = ((j - u.oy + kSdR) * WL + (kSdR - u.ox)) * 512 + fl * 16;
+            run[i][gg] = 0.0f;
+        }
+    }
+    auto flush = [&]() {
+#pragma unroll
+        for (int i = 0; i < kSdAS; ++i) {
+            // undo the scales: 2^-(shift of (s, k) + shift of f), in two exact steps
+            const int shx = sd_shift(a.xmax[sidx[i] * kNumK + j]);
+            const int she = f_ok ? sd_shift(a.emax[f]) : 0;
+#pragma unroll
+            for (int gg = 0; gg < kSdGT; ++gg) {
+                const int g = gb * kSdGT + gg;
+                if (s_ok[i] && g < a.G && f_ok) {
+                    const float v = ldexpf(ldexpf(run[i][gg], -shx), -she);
+                    float* dst = a.partial + ((((size_t)chunk * kNumK + j) * a.S + sidx[i]) * a.G + g) * a.F + f;
+                    __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                run[i][gg] = 0.0f;
+            }
+        }
+    };
+    const int per_oct = a.rq * a.cq;
+    auto item_off = [&](int item) {                       // A offset (16-byte units) of an item's region corner
+        const int oct = item / per_oct, reg = item - oct * per_oct;
+        return ((size_t)oct * a.S * kNumK * xplane + (size_t)((reg / a.cq) * kSdRH) * a.XTc + (reg % a.cq) * RW) * 2;
+    };
+    // A fragments of the current K step; the last step of an item fetches the first of the next item (software pipeline)
+    h8 ahi[kSdAS], alo[kSdAS];
+    if (it0 < it1) {
+#pragma unroll
+        for (int i = 0; i < kSdAS; ++i) { const h8* ap = a.xs + item_off(it0) + aoff[i]; ahi[i] = ap[0]; alo[i] = ap[1]; }
+    }
+    int since_flush = 0;
+    for (int it = it0; it < it1; ++it) {
+        const int oct = it / per_oct, reg = it - oct * per_oct;
+        const int r0 = (reg / a.cq) * kSdRH, c0 = (reg % a.cq) * RW;
+        // error window of the item -> LDS (rows r0 .. r0 + WR - 1, columns c0 .. c0 + WL - 1 of ES[oct][fb])
+        __syncthreads();                                 // every wave is done with the previous window
+        {
+            const uint4* src = reinterpret_cast<const uint4*>(a.es + (((size_t)oct * a.nfb + fb) * a.EYs + r0) * a.EXs * 512);
+            uint4* dst = reinterpret_cast<uint4*>(lds);
+            constexpr int kPieces = WR * WL * 32;        // 16-byte pieces
+            constexpr int kIter = (kPieces + kSdWaves * 64 - 1) / (kSdWaves * 64);
+            constexpr int kBatch = 6;                    // loads in flight per thread
+            for (int q0 = 0; q0 < kIter; q0 += kBatch) {
+                uint4 v[kBatch];
+#pragma unroll
+                for (int q = 0; q < kBatch; ++q) {
+                    const int p = (q0 + q) * kSdWaves * 64 + threadIdx.x;
+                    const int pc = p < kPieces ? p : kPieces - 1;
+                    const int row = pc / (WL * 32), rem = pc - row * (WL * 32);
+                    v[q] = src[(size_t)row * a.EXs * 32 + (size_t)c0 * 32 + rem];
+                }
+#pragma unroll
+                for (int q = 0; q < kBatch; ++q) {
+                    const int p = (q0 + q) * kSdWaves * 64 + threadIdx.x;
+                    if (p < kPieces) dst[p] = v[q];
+                }
+            }
+        }
+        __syncthreads();
+        const size_t ioff = item_off(it);
+        const size_t ioff_next = item_off(it + 1 < it1 ? it + 1 : it);
+        f4s part[kSdAS][kSdGT];
+#pragma unroll
+        for (int i = 0; i < kSdAS; ++i)
+#pragma unroll
+            for (int gg = 0; gg < kSdGT; ++gg) part[i][gg] = f4s{0.0f, 0.0f, 0.0f, 0.0f};
+        // One K step per iteration (unrolled over the item, hipcc hoists loads of later steps until it spills).  Inside a step
+        // the two input channels are two groups of 12 MFMAs; the B fragments of group i + 1 are read from LDS while group i
+        // runs, and the A fragments of channel i for the next step are requested once group i has issued (sched barriers pin it).
+#define SD_READ_B(i, bh, bl)                                                                                    \
+    _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
+        const char* bp = lds + base[i][gg] + k * 512;                                                           \
+        bh[gg] = *reinterpret_cast<const h8*>(bp);                                                              \
+        bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                                        \
+    }
+#define SD_GROUP(i, bh, bl)                                                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                                          \
+    _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[i], bh[gg], part[i][gg], 0, 0, 0);             \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[i], bh[gg], part[i][gg], 0, 0, 0);             \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[i], bl[gg], part[i][gg], 0, 0, 0);             \
+    }                                                                                                           \
+    { const h8* ap = a.xs + an + aoff[i]; ahi[i] = ap[0]; alo[i] = ap[1]; }                                      \
+    __builtin_amdgcn_sched_barrier(0);
+        static_assert(kSdAS == 2, "two groups per K step");
+#pragma unroll 1
+        for (int k = 0; k < RW; ++k) {
+            h8 b0h[kSdGT], b0l[kSdGT], b1h[kSdGT], b1l[kSdGT];
+            const size_t an = k + 1 < RW ? ioff + (size_t)(k + 1) * 2 : ioff_next;
+            SD_READ_B(0, b0h, b0l)
+            SD_READ_B(1, b1h, b1l)
+            SD_GROUP(0, b0h, b0l)
+            SD_GROUP(1, b1h, b1l)
+        }
+#undef SD_READ_B
+#undef SD_GROUP
+        // bilinear combination of the four corners (lane-local), into the running sums
+        // (the factors come from the unit table, L2-resident: registers of their own would spill the accumulators)
+#pragma unroll
+        for (int i = 0; i < kSdAS; ++i)
+#pragma unroll
+            for (int gg = 0; gg < kSdGT; ++gg) {
+                const int g = gb * kSdGT + gg;
+                const bool ok = s_ok[i] && g < a.G && f_ok;
+                const UnitRef* u = a.table + (ok ? ((size_t)sidx[i] * a.G + g) * a.F + f : 0);
+                const float2 b01 = *reinterpret_cast<const float2*>(&u->w00), b23 = *reinterpret_cast<const float2*>(&u->w10);
+                const f4s p = part[i][gg];
+                float v = b01.x * p[0];
+                v = fmaf(b01.y, p[1], v);
+                v = fmaf(b23.x, p[2], v);
+                v = fmaf(b23.y, p[3], v);
+                run[i][gg] += ok ? v : 0.0f;
+            }
+        if (++since_flush == kSdFlushItems) { flush(); since_flush = 0; }
+    }
+    // the last item's look-ahead (a dead load) completes before any register is reused
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (since_flush) flush();
+}
+
+template <int RW>
+void launch_sd(hipStream_t st, const SdArgs* a, int grid) {
+    auto kern = split_gather_dot_kernel<RW>;
+    const size_t lds = (size_t)(kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 512;
+    if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kSdWaves * 64), lds, st, *a);
+}
+void dispatch_sd(int RW, hipStream_t st, const SdArgs* a, int grid) {
+    if (RW == 14) launch_sd<14>(st, a, grid);
+    else if (RW == 15) launch_sd<15>(st, a, grid);
+    else launch_sd<16>(st, a, grid);
+}
+
+}  // namespace
+
+bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg) {
+    if (bf16) return false;
+    // the widest region whose error window fits the LDS, padding the q columns (W + 1) least
+    int best = 0, best_w = 1 << 30;
+    for (int rw = 16; rw >= 14; --rw) {
+        const int wq = (sh.W + 1 + rw - 1) / rw * rw;
+        if (wq < best_w) { best_w = wq; best = rw; }
+    }
+    if ((size_t)(kSdRH + 2 * kSdR) * (best + 2 * kSdR) * 512 > 160 * 1024) return false;
+    if (!blur4_pack_fits(blur_k, sh.H, sh.W)) return false;
+    SplitDotConfig c{};
+    c.sh = sh; c.blur_k = blur_k; c.RW = best;
+    const SdGeom g = sd_geom(c);
+    // 32-bit LDS / lane offsets; h8 offsets of the staged planes stay in size_t
+    if ((long)g.EXs * 512 * 32 > (1L << 31)) return false;
+    *cfg = c;
+    return true;
+}
+
+size_t split_dot_workspace_bytes(const SplitDotConfig& c) { return sd_layout(c, sd_geom(c)).total; }
+
+void split_dot_init(const SplitDotConfig& c) {
+    dispatch_sd(c.RW, nullptr, nullptr, 0);
+    blur4_pack_init(c.blur_k);
+}
+
+void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, const float* dy, const float* filters,
+                       int drop_col, int drop_row, void* workspace, const Guard& guard) {
+    const SdGeom g = sd_geom(c);
+    const SdLayout l = sd_layout(c, g);
+    const Shape& s = c.sh;
+    char* ws = static_cast<char*>(workspace);
+    unsigned* xmax = reinterpret_cast<unsigned*>(ws + l.maxes_off);
+    unsigned* emax = xmax + s.S * kNumK;
+    float* xk = reinterpret_cast<float*>(ws + l.xk_off);
+    (void)hipMemsetAsync(xmax, 0, (size_t)(s.S * kNumK + s.F) * 4, st);
+    (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, false, xk, guard);
+    const int HW = s.H * s.W;
+    const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
+    hipLaunchKernelGGL(sd_absmax_x_kernel, dim3(s.S * xsplit), dim3(256), 0, st, xk, g.NP, s.S, HW, xsplit, xmax, guard);
+    const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
+    hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, emax, guard);
+    hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
+                       reinterpret_cast<h8*>(ws + l.xs_off), guard);
+    hipLaunchKernelGGL(sd_stage_e_kernel, dim3(4096), dim3(256), 0, st, dy, emax, s.N, s.F, s.H, s.W, g.octs, g.nfb, g.EYs, g.EXs,
+                       drop_col, drop_row, reinterpret_cast<h8*>(ws + l.es_off), guard);
+}
+
+void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table, float* r4, void* workspace, const Guard& guard) {
+    const SdGeom g = sd_geom(c);
+    const SdLayout l = sd_layout(c, g);
+    const Shape& s = c.sh;
+    char* ws = static_cast<char*>(workspace);
+    SdArgs a{};
+    a.xs = reinterpret_cast<const h8*>(ws + l.xs_off);
+    a.es = ws + l.es_off;
+    a.xmax = reinterpret_cast<const unsigned*>(ws + l.maxes_off);
+    a.emax = a.xmax + s.S * kNumK;
+    a.table = table;
+    a.partial = reinterpret_cast<float*>(ws + l.partial_off);
+    a.S = s.S; a.F = s.F; a.G = s.G;
+    a.nfb = g.nfb; a.nsb = g.nsb; a.ngb = g.ngb; a.per = g.per; a.items = g.items; a.rq = g.rq; a.cq = g.cq;
+    a.XTr = g.XTr; a.XTc = g.XTc; a.EYs = g.EYs; a.EXs = g.EXs;
+    a.guard = guard;
+    dispatch_sd(c.RW, st, &a, g.chunks * g.nfb * g.nsb * g.ngb);
+    launch_dot_reduce(st, a.partial, 1, (long)kNumK * s.S * s.G * s.F, s.G, s.F, s.G, g.chunks, g.chunks, s.G, false, r4, guard);
+}
+
+}  // namespace dau

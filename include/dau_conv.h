@@ -126,11 +126,14 @@ enum {
                                                hi*lo, fp32 sums, k_dense_split.hip): fp32 accuracy -- the same parity bar as the exact
                                                gather, measured margins in profiles/ -- at 3 * taps / 16 of the fp32 rate per (pixel,
                                                channel pair) instead of 4 G.  float32 or bfloat16 activations; the call's offsets decide
-                                               on the device which member runs; every other call, and the parameter gradients, keep the
-                                               exact kernels.  DEFAULT (neither flag): the members that pay for the plan's unit count
-                                               (on whole tiles: radius 2 from two units per channel pair, radius 3 from three, radius 4 from four).
-                                               This flag: all three members whatever the unit count.                        */
-    DAU_FLAG_NO_DENSE_SPLIT = 1 << 10,      /* never: always the exact fp32 gather (excludes DAU_FLAG_DENSE_SPLIT_F16)      */
+                                               on the device which member runs; every other call keeps the exact kernels.
+                                               The parameter gradients of fp32, interpolating, 2-D calls within +-4 likewise run as a
+                                               two-limb f16 GEMM with the four kinds x four bilinear corners as rows (k_split_dot.hip,
+                                               fp32 accuracy).  DEFAULT (neither flag): the members that pay for the plan's unit count
+                                               (on whole tiles: radius 2 from two units per channel pair, radius 3 from three, radius 4 from four;
+                                               the parameter-gradient member where blocks of four units are at least 3/4 full: G = 3, 4, 7, 8, ...).
+                                               This flag: all members whatever the unit count.                             */
+    DAU_FLAG_NO_DENSE_SPLIT = 1 << 10,      /* never: always the exact fp32 gather and gather-dot (excludes DAU_FLAG_DENSE_SPLIT_F16) */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
