@@ -123,7 +123,7 @@ void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, lon
 struct SplitDotConfig {
     Shape sh;
     int blur_k;
-    int RW;               // region columns = K steps per item (14, 15 or 16: the least padding of the W + 1 staged columns)
+    int RW;               // region columns = K steps per item (10 or 12: the ring of error-window rows fills the LDS at 12)
 };
 bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);

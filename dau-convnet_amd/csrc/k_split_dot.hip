@@ -16,7 +16,8 @@
 //    Exact power-of-two scales per (s, k) and per f bring each maximum to [2^13, 2^14); the maxima are taken over finite values only
 //    (an Inf / NaN does not remove the scaling of the other channels).  The epilogue undoes them exactly.
 //  * Main kernel.  Workgroup = (chunk of (image octet, region) items, 16 output channels, 16 input channels, 4 units); region =
-//    4 rows x RW columns of q; the ES window of the 16 channels (RH + 2R rows x RW + 2R columns x 512 B) sits in LDS.  A wave owns
+//    4 rows x RW columns of q; the ES window of the 16 channels (RH + 2R rows x RW + 2R columns x 512 B) sits in LDS as a ring of
+//    rows, the items walking down column strips so that each copies only its RH new rows, one item ahead.  A wave owns
 //    2 input channels x 4 units = 8 tiles of 16 units (s, g, the block's 16 f) for the whole kernel.  Lane group j = row j of
 //    the region, K step = one column: every address is a per-lane base plus an immediate.
 //  * Bank conflicts.  The LDS window is position-major with the 16 output channels of a position in consecutive 16-byte groups, so
@@ -45,6 +46,8 @@ constexpr int kSdFB = 16;               // output channels per workgroup = B col
 constexpr int kSdR = 4;                 // offset radius of the error window
 constexpr int kSdRH = 4;                // region rows = K groups of one MFMA
 constexpr int kSdFlushItems = 16;       // items per flush of the running sums (at most 16 float additions per slot and chunk)
+// s_waitcnt immediates (gfx9 encoding: vmcnt in bits 3:0, expcnt 6:4 and lgkmcnt 11:8 left at their maxima)
+constexpr unsigned kVmcnt0 = 0x0F70, kVmcnt8 = 0x0F78;
 
 inline size_t rup(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -244,12 +247,35 @@ struct SdArgs {
     Guard guard;
 };
 
-// RW: columns per region (K steps per item); the error window is (RH + 2R) x (RW + 2R) positions x 512 B
+// One 1 KiB piece of the error window: 16 bytes per lane from `src` into the LDS bytes [dst, dst + 1024) (lane-linear), with no
+// VGPR in between.  Inline asm, so that hipcc leaves it out of its wait bookkeeping: as a builtin it would put a vmcnt wait in
+// front of every following LDS read and A-fragment use and drain the copy at once.  Its completion is counted by hand (below);
+// hipcc's own counted waits only ever wait MORE for it (its place in the in-order queue of vector loads is not counted there).
+__device__ __forceinline__ void sd_glds16(const char* src, unsigned dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+}
+
+// RW: columns per region (K steps per item).  The error window of an item is WR = RH + 2R rows x RW + 2R columns x 512 B; the
+// LDS holds a RING of WR + RH rows.  The items of a chunk walk DOWN a column strip of regions (one image octet), so the window of
+// the next item is the current one moved down by RH rows: its RH new rows are copied into the ring's RH free slots while the
+// current item computes, and one barrier per item publishes them.  The whole window is copied only at the first item of a chunk
+// and where a strip begins.
+// Timing experiments of a tuning build (tools/build_variant.sh; results are garbage): DAU_SD_DIAG_NOFILL copies no window
+// (waits and barriers stay), DAU_SD_DIAG_NOA reloads no A fragment, DAU_SD_DIAG_AFIXED reads the A fragments of the chunk's
+// first item for every item (the same loads, hitting in the caches).
 template <int RW>
 __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) split_gather_dot_kernel(const SdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     if (!guard_pass(a.guard)) return;
     constexpr int WL = RW + 2 * kSdR, WR = kSdRH + 2 * kSdR;
+    constexpr int kRing = WR + kSdRH;                    // ring slots (rows)
+    constexpr unsigned RB = WL * 512;                    // bytes per window row
+    constexpr int kRowPieces = (RB + 1023) / 1024;       // 1 KiB pieces per row (a whole number: WL is even)
+    static_assert((kRing & (kRing - 1)) == 0, "ring slot = (origin + row) & (kRing - 1)");
+    static_assert(RW % 2 == 0, "A fragment sets by the parity of the K step");
+    static_assert((size_t)kRing * RB <= 160 * 1024, "the ring fills the LDS");
     int t = blockIdx.x;
     const int gb = t % a.ngb; t /= a.ngb;
     const int sb = t % a.nsb; t /= a.nsb;
@@ -257,16 +283,19 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
     const int chunk = t;
     const int it0 = chunk * a.per, it1 = min(it0 + a.per, a.items);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const int fl = lane & 15, j = lane >> 4;
     const int f = fb * kSdFB + fl;
     const bool f_ok = f < a.F;
+    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
     // A operand of this lane: row m = 4 k + d, K group j
     const int m = lane & 15, ak = m >> 2, ady = (m >> 1) & 1, adx = m & 1;
     const size_t xplane = (size_t)a.XTr * a.XTc;         // positions per (oct, s, k) plane
     unsigned aoff[kSdAS];                                // lane offset (in 16-byte units) of its A row, per input channel
     int sidx[kSdAS];
     bool s_ok[kSdAS];
-    int base[kSdAS][kSdGT];                              // LDS byte address of the unit's B column at K step 0
+    unsigned uw[kSdAS][kSdGT];                           // the unit's B column at K step 0: window row | byte offset in the row << 4
+    f4s wb[kSdAS][kSdGT];                                // the unit's bilinear factors (w00, w01, w10, w11)
     float run[kSdAS][kSdGT];
 #pragma unroll
     for (int i = 0; i < kSdAS; ++i) {
@@ -279,21 +308,26 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
             const int g = gb * kSdGT + gg;
             UnitRef u{0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
             if (s_ok[i] && g < a.G && f_ok) u = a.table[((size_t)sidx[i] * a.G + g) * a.F + f];
-            base[i][gg] = ((j - u.oy + kSdR) * WL + (kSdR - u.ox)) * 512 + fl * 16;
+            uw[i][gg] = (unsigned)(j - u.oy + kSdR) | (unsigned)((kSdR - u.ox) * 512 + fl * 16) << 4;
+            wb[i][gg] = f4s{u.w00, u.w01, u.w10, u.w11};
             run[i][gg] = 0.0f;
         }
     }
+    // the scale exponents, read once: with loads in the flush, hipcc's wait bookkeeping at the item loop's header would
+    // become conservative and drain the window copy in flight
+    int shx[kSdAS];
+    const int she = f_ok ? sd_shift(a.emax[f]) : 0;
+#pragma unroll
+    for (int i = 0; i < kSdAS; ++i) shx[i] = sd_shift(a.xmax[sidx[i] * kNumK + j]);
     auto flush = [&]() {
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i) {
             // undo the scales: 2^-(shift of (s, k) + shift of f), in two exact steps
-            const int shx = sd_shift(a.xmax[sidx[i] * kNumK + j]);
-            const int she = f_ok ? sd_shift(a.emax[f]) : 0;
 #pragma unroll
             for (int gg = 0; gg < kSdGT; ++gg) {
                 const int g = gb * kSdGT + gg;
                 if (s_ok[i] && g < a.G && f_ok) {
-                    const float v = ldexpf(ldexpf(run[i][gg], -shx), -she);
+                    const float v = ldexpf(ldexpf(run[i][gg], -shx[i]), -she);
                     float* dst = a.partial + ((((size_t)chunk * kNumK + j) * a.S + sidx[i]) * a.G + g) * a.F + f;
                     __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
@@ -301,48 +335,69 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
             }
         }
     };
+    // item -> (octet, region row ry, region column rx); the regions of an octet are numbered down the column strips
     const int per_oct = a.rq * a.cq;
     auto item_off = [&](int item) {                       // A offset (16-byte units) of an item's region corner
-        const int oct = item / per_oct, reg = item - oct * per_oct;
-        return ((size_t)oct * a.S * kNumK * xplane + (size_t)((reg / a.cq) * kSdRH) * a.XTc + (reg % a.cq) * RW) * 2;
+        const int oct = item / per_oct, reg = item - oct * per_oct, rx = reg / a.rq, ry = reg - rx * a.rq;
+        return ((size_t)oct * a.S * kNumK * xplane + (size_t)(ry * kSdRH) * a.XTc + (size_t)rx * RW) * 2;
     };
-    // A fragments of the current K step; the last step of an item fetches the first of the next item (software pipeline)
-    h8 ahi[kSdAS], alo[kSdAS];
+    // window rows [w0, w0 + nrows) of the item at (oct, ry, rx) into the ring slots (origin + w0 ..) & (kRing - 1), spread over the
+    // eight waves row by row (a piece must be contiguous in LDS)
+    auto fill = [&](int oct, int ry, int rx, int w0, int nrows, int origin) {
+#ifndef DAU_SD_DIAG_NOFILL
+        const char* src = a.es + ((((size_t)oct * a.nfb + fb) * a.EYs + (size_t)(ry * kSdRH + w0)) * a.EXs + (size_t)rx * RW) * 512;
+        for (int u = wave_u; u < nrows * kRowPieces; u += kSdWaves) {
+            const int rr = u / kRowPieces, pc = u - rr * kRowPieces;
+            const unsigned within = pc * 1024 + lane * 16;
+            const unsigned slot = (unsigned)(origin + w0 + rr) & (kRing - 1);
+            if (within < RB) sd_glds16(src + (size_t)rr * a.EXs * 512 + within, lds0 + slot * RB + pc * 1024);
+        }
+#endif
+    };
+    // A fragments, two K steps ahead: set p holds the steps of parity p (RW is even); the last two steps of an item fetch the
+    // first two of the next item (software pipeline)
+    h8 ahi[2][kSdAS], alo[2][kSdAS];
     if (it0 < it1) {
 #pragma unroll
-        for (int i = 0; i < kSdAS; ++i) { const h8* ap = a.xs + item_off(it0) + aoff[i]; ahi[i] = ap[0]; alo[i] = ap[1]; }
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int i = 0; i < kSdAS; ++i) {
+                const h8* ap = a.xs + item_off(it0) + (size_t)p * 2 + aoff[i];
+                ahi[p][i] = ap[0]; alo[p][i] = ap[1];
+            }
     }
     int since_flush = 0;
+    int origin = 0;                                      // ring slot of the current window's row 0
     for (int it = it0; it < it1; ++it) {
-        const int oct = it / per_oct, reg = it - oct * per_oct;
-        const int r0 = (reg / a.cq) * kSdRH, c0 = (reg % a.cq) * RW;
-        // error window of the item -> LDS (rows r0 .. r0 + WR - 1, columns c0 .. c0 + WL - 1 of ES[oct][fb])
-        __syncthreads();                                 // every wave is done with the previous window
-        {
-            const uint4* src = reinterpret_cast<const uint4*>(a.es + (((size_t)oct * a.nfb + fb) * a.EYs + r0) * a.EXs * 512);
-            uint4* dst = reinterpret_cast<uint4*>(lds);
-            constexpr int kPieces = WR * WL * 32;        // 16-byte pieces
-            constexpr int kIter = (kPieces + kSdWaves * 64 - 1) / (kSdWaves * 64);
-            constexpr int kBatch = 6;                    // loads in flight per thread
-            for (int q0 = 0; q0 < kIter; q0 += kBatch) {
-                uint4 v[kBatch];
-#pragma unroll
-                for (int q = 0; q < kBatch; ++q) {
-                    const int p = (q0 + q) * kSdWaves * 64 + threadIdx.x;
-                    const int pc = p < kPieces ? p : kPieces - 1;
-                    const int row = pc / (WL * 32), rem = pc - row * (WL * 32);
-                    v[q] = src[(size_t)row * a.EXs * 32 + (size_t)c0 * 32 + rem];
-                }
-#pragma unroll
-                for (int q = 0; q < kBatch; ++q) {
-                    const int p = (q0 + q) * kSdWaves * 64 + threadIdx.x;
-                    if (p < kPieces) dst[p] = v[q];
-                }
-            }
-        }
+        const int oct = it / per_oct, reg = it - oct * per_oct, rx = reg / a.rq, ry = reg - rx * a.rq;
+        // This wave's rows of the window were requested one item ago, before all of that item's A fragments; the newest eight
+        // vector memory operations (the A fragments of this item's first two K steps) may stay in flight.  The barrier then
+        // publishes every wave's rows, and every wave is done with the previous window.  (The builtin, not an asm statement:
+        // hipcc takes it into its own bookkeeping and needs no wait of its own for registers reused in the item.)
+        __builtin_amdgcn_s_waitcnt(kVmcnt8);
         __syncthreads();
+        if (it > it0 && ry > 0) {
+            origin = (origin + kSdRH) & (kRing - 1);     // the previous item is the region above: its rows RH .. WR - 1 stay
+        } else {
+            origin = 0;                                  // first item of the chunk or of a strip: the whole window
+            fill(oct, ry, rx, 0, WR, 0);
+            __builtin_amdgcn_s_waitcnt(kVmcnt0);
+            __syncthreads();
+        }
+        // the RH new rows of the next item (the region below) into the slots of the previous window's first rows
+        if (it + 1 < it1 && ry + 1 < a.rq) fill(oct, ry, rx, WR, kSdRH, origin);
+        int base[kSdAS][kSdGT];                          // LDS byte address of the unit's B column at K step 0
+#pragma unroll
+        for (int i = 0; i < kSdAS; ++i)
+#pragma unroll
+            for (int gg = 0; gg < kSdGT; ++gg)
+                base[i][gg] = (int)((((unsigned)origin + (uw[i][gg] & 15u)) & (kRing - 1)) * RB + (uw[i][gg] >> 4));
+#ifdef DAU_SD_DIAG_AFIXED
+        const size_t ioff = item_off(it0), ioff_next = ioff;
+#else
         const size_t ioff = item_off(it);
         const size_t ioff_next = item_off(it + 1 < it1 ? it + 1 : it);
+#endif
         f4s part[kSdAS][kSdGT];
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i)
@@ -351,48 +406,60 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
         // One K step per iteration (unrolled over the item, hipcc hoists loads of later steps until it spills).  Inside a step
         // the two input channels are two groups of 12 MFMAs; the B fragments of group i + 1 are read from LDS while group i
         // runs, and the A fragments of channel i for the next step are requested once group i has issued (sched barriers pin it).
+#ifdef DAU_SD_DIAG_NOA
+#define SD_LOAD_A(P, i)
+#else
+#define SD_LOAD_A(P, i) { const h8* ap = a.xs + an + aoff[i]; ahi[P][i] = ap[0]; alo[P][i] = ap[1]; }
+#endif
 #define SD_READ_B(i, bh, bl)                                                                                    \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
         const char* bp = lds + base[i][gg] + k * 512;                                                           \
         bh[gg] = *reinterpret_cast<const h8*>(bp);                                                              \
         bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                                        \
     }
-#define SD_GROUP(i, bh, bl)                                                                                     \
+#define SD_GROUP(P, i, bh, bl)                                                                                  \
     __builtin_amdgcn_sched_barrier(0);                                                                          \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[i], bh[gg], part[i][gg], 0, 0, 0);             \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[i], bh[gg], part[i][gg], 0, 0, 0);             \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[i], bl[gg], part[i][gg], 0, 0, 0);             \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[P][i], bh[gg], part[i][gg], 0, 0, 0);          \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[P][i], bh[gg], part[i][gg], 0, 0, 0);          \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[P][i], bl[gg], part[i][gg], 0, 0, 0);          \
     }                                                                                                           \
-    { const h8* ap = a.xs + an + aoff[i]; ahi[i] = ap[0]; alo[i] = ap[1]; }                                      \
+    SD_LOAD_A(P, i)                                                                                             \
     __builtin_amdgcn_sched_barrier(0);
+        // K step kk with the A set of its parity P; the set then fetches step kk + 2 (of the next item past the last step)
+#define SD_STEP(P, kk)                                                                                          \
+    {                                                                                                           \
+        const int k = (kk);                                                                                     \
+        h8 b0h[kSdGT], b0l[kSdGT], b1h[kSdGT], b1l[kSdGT];                                                      \
+        const size_t an = k + 2 < RW ? ioff + (size_t)(k + 2) * 2 : ioff_next + (size_t)(k + 2 - RW) * 2;       \
+        (void)an;                                                                                               \
+        SD_READ_B(0, b0h, b0l)                                                                                  \
+        SD_READ_B(1, b1h, b1l)                                                                                  \
+        SD_GROUP(P, 0, b0h, b0l)                                                                                \
+        SD_GROUP(P, 1, b1h, b1l)                                                                                \
+    }
         static_assert(kSdAS == 2, "two groups per K step");
 #pragma unroll 1
-        for (int k = 0; k < RW; ++k) {
-            h8 b0h[kSdGT], b0l[kSdGT], b1h[kSdGT], b1l[kSdGT];
-            const size_t an = k + 1 < RW ? ioff + (size_t)(k + 1) * 2 : ioff_next;
-            SD_READ_B(0, b0h, b0l)
-            SD_READ_B(1, b1h, b1l)
-            SD_GROUP(0, b0h, b0l)
-            SD_GROUP(1, b1h, b1l)
+        for (int k2 = 0; k2 < RW; k2 += 2) {
+            SD_STEP(0, k2)
+            SD_STEP(1, k2 + 1)
         }
 #undef SD_READ_B
 #undef SD_GROUP
+#undef SD_LOAD_A
+#undef SD_STEP
         // bilinear combination of the four corners (lane-local), into the running sums
-        // (the factors come from the unit table, L2-resident: registers of their own would spill the accumulators)
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i)
 #pragma unroll
             for (int gg = 0; gg < kSdGT; ++gg) {
                 const int g = gb * kSdGT + gg;
                 const bool ok = s_ok[i] && g < a.G && f_ok;
-                const UnitRef* u = a.table + (ok ? ((size_t)sidx[i] * a.G + g) * a.F + f : 0);
-                const float2 b01 = *reinterpret_cast<const float2*>(&u->w00), b23 = *reinterpret_cast<const float2*>(&u->w10);
-                const f4s p = part[i][gg];
-                float v = b01.x * p[0];
-                v = fmaf(b01.y, p[1], v);
-                v = fmaf(b23.x, p[2], v);
-                v = fmaf(b23.y, p[3], v);
+                const f4s p = part[i][gg], w = wb[i][gg];
+                float v = w[0] * p[0];
+                v = fmaf(w[1], p[1], v);
+                v = fmaf(w[2], p[2], v);
+                v = fmaf(w[3], p[3], v);
                 run[i][gg] += ok ? v : 0.0f;
             }
         if (++since_flush == kSdFlushItems) { flush(); since_flush = 0; }
@@ -405,27 +472,29 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
 template <int RW>
 void launch_sd(hipStream_t st, const SdArgs* a, int grid) {
     auto kern = split_gather_dot_kernel<RW>;
-    const size_t lds = (size_t)(kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 512;
+    const size_t lds = (size_t)(2 * kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 512;
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kSdWaves * 64), lds, st, *a);
 }
 void dispatch_sd(int RW, hipStream_t st, const SdArgs* a, int grid) {
-    if (RW == 14) launch_sd<14>(st, a, grid);
-    else if (RW == 15) launch_sd<15>(st, a, grid);
-    else launch_sd<16>(st, a, grid);
+    if (RW == 10) launch_sd<10>(st, a, grid);
+    else launch_sd<12>(st, a, grid);
 }
 
 }  // namespace
 
 bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg) {
     if (bf16) return false;
-    // the widest region whose error window fits the LDS, padding the q columns (W + 1) least
-    int best = 0, best_w = 1 << 30;
-    for (int rw = 16; rw >= 14; --rw) {
-        const int wq = (sh.W + 1 + rw - 1) / rw * rw;
-        if (wq < best_w) { best_w = wq; best = rw; }
+    // the region width whose ring of error-window rows fits the LDS (RW <= 12) with the least work: the q columns (W + 1) padded
+    // to a multiple of RW, plus about two K steps' worth of per-item cost (barrier, bilinear epilogue) per region
+    int best = 0;
+    long best_cost = 1L << 40;
+    for (int rw = 12; rw >= 10; rw -= 2) {
+        const long wq = (sh.W + 1 + rw - 1) / rw * rw;
+        const long cost = wq * (rw + 2) * (60 / rw);                // wq * (rw + 2) / rw, scaled to an integer
+        if (cost < best_cost) { best_cost = cost; best = rw; }
     }
-    if ((size_t)(kSdRH + 2 * kSdR) * (best + 2 * kSdR) * 512 > 160 * 1024) return false;
+    if ((size_t)(2 * kSdRH + 2 * kSdR) * (best + 2 * kSdR) * 512 > 160 * 1024) return false;
     if (!blur4_pack_fits(blur_k, sh.H, sh.W)) return false;
     SplitDotConfig c{};
     c.sh = sh; c.blur_k = blur_k; c.RW = best;
