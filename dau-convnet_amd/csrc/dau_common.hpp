@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include "dau_conv.h"
 
 // Tuning knobs.  The shipped library's behaviour is fully determined by dau_conv_desc (plus DAU_WORKSPACE_BUDGET_GB): the
@@ -21,25 +22,39 @@
 
 namespace dau {
 
-// bfloat16 I/O (DAU_FLAG_IO_BF16): activations are stored as the upper 16 bits of an fp32
-__device__ __forceinline__ float load_act(const float* base, long idx, bool bf16) {
-    if (!bf16) return base[idx];
-    return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(base)[idx] << 16);
+// Storage format of the activations (x, y, dy, dx) behind the float* of the ABI: fp32, bfloat16 (DAU_FLAG_IO_BF16: the upper
+// 16 bits of an fp32) or IEEE binary16 (DAU_FLAG_IO_F16).  The arithmetic is fp32 for all three; only loads and stores differ.
+enum ActFormat : int { kActF32 = 0, kActBF16 = 1, kActF16 = 2 };
+__device__ __forceinline__ float f16_bits_to_float(unsigned bits) {      // v_cvt_f32_f16 (subnormals, Inf and NaN widen exactly)
+    return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
+}
+__device__ __forceinline__ float load_act(const float* base, long idx, int act) {
+    if (act == kActF32) return base[idx];
+    const unsigned b = reinterpret_cast<const unsigned short*>(base)[idx];
+    return act == kActF16 ? f16_bits_to_float(b) : __uint_as_float(b << 16);
 }
 // the stored bits of an activation, untouched (no arithmetic on a value still in flight), and their conversion
-template <bool BF> struct RawAct { typedef float type; };
-template <> struct RawAct<true> { typedef unsigned type; };   // (zero-extended by the load; a 16-bit pair would be packed = arithmetic)
-template <bool BF>
-__device__ __forceinline__ typename RawAct<BF>::type load_raw(const float* base, long idx) {
-    if constexpr (!BF) return base[idx];
-    else return reinterpret_cast<const unsigned short*>(base)[idx];
+struct F16Bits { unsigned bits; };                            // an f16 activation, zero-extended by the load
+template <int A> struct RawAct { typedef float type; };
+template <> struct RawAct<kActBF16> { typedef unsigned type; };   // (zero-extended by the load; a 16-bit pair would be packed = arithmetic)
+template <> struct RawAct<kActF16> { typedef F16Bits type; };
+template <int A>
+__device__ __forceinline__ typename RawAct<A>::type load_raw(const float* base, long idx) {
+    if constexpr (A == kActF32) return base[idx];
+    else if constexpr (A == kActBF16) return reinterpret_cast<const unsigned short*>(base)[idx];
+    else return F16Bits{reinterpret_cast<const unsigned short*>(base)[idx]};
 }
 __device__ __forceinline__ float act_of(float v) { return v; }
 __device__ __forceinline__ float act_of(unsigned v) { return __uint_as_float(v << 16); }
-template <bool BF>
-__device__ __forceinline__ float load_act_t(const float* base, long idx) {
-    if constexpr (!BF) return base[idx];
-    else return __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(base)[idx] << 16);
+__device__ __forceinline__ float act_of(F16Bits v) { return f16_bits_to_float(v.bits); }
+template <int A>
+__device__ __forceinline__ float load_act_t(const float* base, long idx) { return act_of(load_raw<A>(base, idx)); }
+// f(std::integral_constant<int, A>) for the run-time format `act` (staging kernels: one instantiation of the body per format)
+template <class F>
+__device__ __forceinline__ void with_act(int act, F&& f) {
+    if (act == kActBF16) f(std::integral_constant<int, kActBF16>{});
+    else if (act == kActF16) f(std::integral_constant<int, kActF16>{});
+    else f(std::integral_constant<int, kActF32>{});
 }
 // v where keep, +0 elsewhere, as a bit mask: with a select hipcc moves the load that produced v under a branch on `keep`
 __device__ __forceinline__ float mask_act(float v, bool keep) { return __uint_as_float(__float_as_uint(v) & (keep ? 0xffffffffu : 0u)); }
@@ -91,6 +106,23 @@ __device__ __forceinline__ void store_act(float* base, long idx, float v, bool b
     // exponent: 0xFFFFFFFF -> +0, 0x7F800001 -> +inf), so it is stored as the quiet NaN pattern instead
     u = (v != v) ? 0x7fc00000u : u + 0x7fffu + ((u >> 16) & 1u);
     *p = (unsigned short)(u >> 16);
+}
+// binary16: v_cvt_f16_f32 -- round to nearest even, f16 subnormals kept, beyond the largest finite value +-inf, a NaN stays a
+// NaN (the IEEE conversion, as torch.Tensor.half()); a window pass re-reads the stored value, adds and rounds once more
+__device__ __forceinline__ void store_act_f16(float* base, long idx, float v, bool accumulate) {
+    unsigned short* p = reinterpret_cast<unsigned short*>(base) + idx;
+    if (accumulate) v += f16_bits_to_float(*p);
+    *p = __builtin_bit_cast(unsigned short, (_Float16)v);
+}
+template <int A>
+__device__ __forceinline__ void store_act_t(float* base, long idx, float v, bool accumulate) {
+    if constexpr (A == kActF16) store_act_f16(base, idx, v, accumulate);
+    else store_act(base, idx, v, A == kActBF16, accumulate);
+}
+// run-time format (epilogues of kernels whose instantiations serve all three)
+__device__ __forceinline__ void store_act(float* base, long idx, float v, int act, bool accumulate) {
+    if (act == kActF16) store_act_f16(base, idx, v, accumulate);
+    else store_act(base, idx, v, act == kActBF16, accumulate);
 }
 
 

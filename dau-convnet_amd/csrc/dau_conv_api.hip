@@ -56,7 +56,7 @@ struct Carver {
     }
 };
 
-// image n0 of an activation tensor whose elements are esize bytes (float32, or bfloat16 behind the float* of the ABI)
+// image n0 of an activation tensor whose elements are esize bytes (float32, or bfloat16 / binary16 behind the float* of the ABI)
 inline const float* slab_ptr(const float* base, size_t elements, size_t esize) {
     return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + elements * esize);
 }
@@ -116,7 +116,7 @@ constexpr int kNumBuckets = 7;
 
 // the two-limb f16 dense gather-sum, one set of entry points per offset radius (index r - 2)
 struct SplitFns {
-    bool (*configure)(int, int, int, int, int, int, int, int, bool, DenseConfig*);
+    bool (*configure)(int, int, int, int, int, int, int, int, int, DenseConfig*);
     size_t (*workspace_bytes)(const DenseConfig&);
     void (*init)(const DenseConfig&);
     void (*prepare)(hipStream_t, const DenseConfig&, const float*, const float*, bool, const UnitRef*, void*, const Guard&);
@@ -444,6 +444,10 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
 
     const Shape& s = p->sh;
     const bool bf16 = (desc->flags & DAU_FLAG_IO_BF16) != 0;
+    const bool f16 = (desc->flags & DAU_FLAG_IO_F16) != 0;
+    // storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does
+    // (the staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ
+    const int act = f16 ? kActF16 : bf16 ? kActBF16 : kActF32;
     const char* budget_env = getenv("DAU_WORKSPACE_BUDGET_GB");
     const double budget_bytes = (budget_env ? atof(budget_env) : 12.0) * 1e9;
     for (int b : kBuckets) {
@@ -456,8 +460,8 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         const bool split_allowed = !(desc->flags & (DAU_FLAG_NO_DENSE_SPLIT | DAU_FLAG_DENSE_BF16)) && desc->algo != DAU_ALGO_DIRECT &&
                                    DAU_TUNE_INT("DAU_DENSE_SPLIT", 1) != 0;
         auto configure_gather = [&](int n) {
-            bs.fwd_ok = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, bf16, &bs.tiled_fwd) &&
-                        tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, bf16, &bs.tiled_dx);
+            bs.fwd_ok = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, act, &bs.tiled_fwd) &&
+                        tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, act, &bs.tiled_dx);
             bs.dense_ok = want_dense && bs.fwd_ok &&
                           r4::dense_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, bf16, &bs.dense_fwd) &&
                           r4::dense_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, bf16, &bs.dense_dx);
@@ -471,8 +475,8 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                 const int g_live = s.G - desc->number_units_ignore;
                 ok = split_allowed && bs.fwd_ok && b == 4 &&
                      (split_forced || (split_pays(r, s.S, s.F, g_live, s.H, s.W) && split_pays(r, s.F, s.S, g_live, s.H, s.W))) &&
-                     kSplit[r - 2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, bf16, &bs.split_fwd[r - 2]) &&
-                     kSplit[r - 2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, bf16, &bs.split_dx[r - 2]);
+                     kSplit[r - 2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &bs.split_fwd[r - 2]) &&
+                     kSplit[r - 2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &bs.split_dx[r - 2]);
                 if (ok) need = std::max(need, std::max(kSplit[r - 2].workspace_bytes(bs.split_fwd[r - 2]), kSplit[r - 2].workspace_bytes(bs.split_dx[r - 2])));
             }
             if (bs.dense_ok) need = std::max(need, std::max(r4::dense_gather_workspace_bytes(bs.dense_fwd), r4::dense_gather_workspace_bytes(bs.dense_dx)));
@@ -481,7 +485,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         };
         auto configure_dot = [&](int n) {
             Shape sn = s; sn.N = n;
-            bs.dot_ok = tiled_dot_configure(sn, b, blur_k, bf16, desc->number_units_ignore, &bs.tiled_dot);
+            bs.dot_ok = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
             return bs.dot_ok ? tiled_dot_workspace_bytes(bs.tiled_dot) : (size_t)0;
         };
         auto pick_slab = [&](auto&& configure) {
@@ -508,14 +512,18 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                            (double)r3::dense_wgrad_workspace_bytes(bs.wgrad3) <= budget_bytes;
         }
         {
-            // two-limb f16 gather-dot: fp32 layers, bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default
+            // two-limb f16 gather-dot: fp32 and f16 layers, bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default
             // where the blocks of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with
             // DAU_FLAG_DENSE_SPLIT_F16 whatever the unit count
             const bool interp2d = (desc->flags & DAU_FLAG_USE_INTERPOLATION) && !(desc->flags & DAU_FLAG_SINGLE_DIM_KERNEL);
             const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
             bs.sdot_ok = split_allowed && !bf16 && b == 4 && interp2d && bs.dot_ok && bs.slab_dot == s.N && (split_forced || fill) &&
-                         split_dot_configure(s, blur_k, bf16, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
+                         split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
         }
+    }
+    if (f16 && (desc->flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS))) {
+        delete p;
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_F16 excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
     }
     if ((desc->flags & DAU_FLAG_DENSE_BF16) && !bf16) {
         delete p;
@@ -531,9 +539,10 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
     }
     const bool fwd_ok = p->top().fwd_ok, dot_ok = p->top().dot_ok;
-    if (bf16 && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok))) {
+    if ((bf16 || f16) && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok))) {
         delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_BF16 needs the tiled kernels, which do not support this shape / algo");
+        return fail(DAU_INVALID_ARGUMENT, "%s needs the tiled kernels, which do not support this shape / algo",
+                    f16 ? "DAU_FLAG_IO_F16" : "DAU_FLAG_IO_BF16");
     }
     if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) {
         delete p;
@@ -650,7 +659,7 @@ int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const
         Candidate cand[kMaxCandidates];
         const int ncand = pick_candidates(p, ws.status, 0, cand);
         if (p->profiling) ++p->prof_passes[0];
-        const size_t esize = (p->d.flags & DAU_FLAG_IO_BF16) ? 2 : 4;
+        const size_t esize = (p->d.flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
         for (int ci = 0; ci < ncand; ++ci) {
             const BucketSet& bs = *cand[ci].set;
             for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {             // one slab unless the staged copy exceeds the budget
@@ -706,7 +715,7 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
     if (p->algo_bwd == DAU_ALGO_TILED) {
         Candidate cand[kMaxCandidates];
         const int ncand = pick_candidates(p, ws.status, 1, cand);
-        const size_t esize = (flags & DAU_FLAG_IO_BF16) ? 2 : 4;
+        const size_t esize = (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
         for (int ci = 0; ci < ncand; ++ci) {
             const BucketSet& bs = *cand[ci].set;
             const TiledDotConfig& cfg = bs.tiled_dot;
@@ -784,7 +793,7 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
         if (p->algo_fwd == DAU_ALGO_TILED) {
             Candidate cand[kMaxCandidates];
             const int ncand = pick_candidates(p, ws.status, 0, cand);
-            const size_t esize = (flags & DAU_FLAG_IO_BF16) ? 2 : 4;
+            const size_t esize = (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
             for (int ci = 0; ci < ncand; ++ci) {
                 const BucketSet& bs = *cand[ci].set;
                 for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {

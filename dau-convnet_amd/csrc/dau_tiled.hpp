@@ -23,10 +23,10 @@ struct TiledConfig {
     int fblock;       // out-channels per workgroup
     int variant;      // kernel instantiation id
     int debug;        // DAU_GATHER_DEBUG at plan creation (timing experiments)
-    int bf16;         // activations in and out are bfloat16
+    int act;          // storage format of the activations in and out (ActFormat, dau_common.hpp)
 };
 
-bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, TiledConfig* cfg);
+bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, TiledConfig* cfg);
 size_t tiled_gather_workspace_bytes(const TiledConfig& cfg);
 // prepare: blur `in` ([N,Cin,H,W]) with the Gaussian (`filters` = output of launch_synth_filters; `mirrored`
 // selects the flipped kernel of the input-gradient pass) into the staged pair-interleaved planes and pack the
@@ -45,7 +45,7 @@ void tiled_gather_init(const TiledConfig& cfg);
 struct DenseConfig {
     int N, Cin, Cout, G, H, W;
     int R, blur_k;
-    int bf16;         // activations in and out are bfloat16 (required)
+    int act;          // storage format of the activations in and out (ActFormat; the dense bf16 form requires kActBF16)
     int nsub;         // 8-pixel subtiles per column block = kernel instantiation
     int ftiles;       // 32-channel accumulator tiles per wave (2: four waves per workgroup, 1: eight)
 };
@@ -65,11 +65,11 @@ DAU_DECLARE_DENSE_GATHER(r4)
 DAU_DECLARE_DENSE_GATHER(r3)
 
 // Densified gather-sum at fp32 accuracy (k_dense_split.hip): the same dense form with both operands split into two binary16
-// limbs, three f16 MFMAs per tap -- fp32 or bf16 activations, inside the fp32 parity bar; the same source compiled once per
+// limbs, three f16 MFMAs per tap -- fp32, bf16 or f16 activations, inside the fp32 parity bar; the same source compiled once per
 // offset radius (Makefile): namespaces s2, s3, s4 = offsets within +-2, +-3, +-4 (5 x 5, 7 x 7, 9 x 9 taps).
 #define DAU_DECLARE_SPLIT_GATHER(NS)                                                                                           \
     namespace NS {                                                                                                            \
-    bool split_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, DenseConfig* cfg); \
+    bool split_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, DenseConfig* cfg);  \
     size_t split_gather_workspace_bytes(const DenseConfig& cfg);                                                              \
     void split_gather_init(const DenseConfig& cfg);                                                                           \
     void split_gather_prepare(hipStream_t st, const DenseConfig& cfg, const float* in, const float* filters, bool mirrored,   \
@@ -92,12 +92,12 @@ struct TiledDotConfig {
     bool ring;            // window passes keep the error tile as a ring of rows (k_gather_dot.hip, RING)
     int region_cols, region_rows;   // positions per (item, input channel) sweep: 8 x 8, 8 x 7, 14 x 4 (or 8 x 4 in bucket 18)
     int rounds;           // DAU_DOT_ROUNDS at plan creation: workgroups per CU the chunking aims at (0: default)
-    bool bf16;            // x and dy are bfloat16
+    int act;              // storage format of x and dy (ActFormat)
     int ignore;           // number_units_ignore: binned window passes give those units no slot
     int debug;
 };
 
-bool tiled_dot_configure(const Shape& sh, int R, int blur_k, bool bf16, int ignore, TiledDotConfig* cfg);
+bool tiled_dot_configure(const Shape& sh, int R, int blur_k, int act, int ignore, TiledDotConfig* cfg);
 size_t tiled_dot_workspace_bytes(const TiledDotConfig& cfg);
 // r4[k][s][g][f] = sum_{n,p} dy'[n,f,p] * bilinear(x * D_k, p + o);  `filters` = output of launch_synth_filters.
 void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& cfg, const float* x, const float* dy,
@@ -109,7 +109,7 @@ void tiled_dot_init(const TiledDotConfig& cfg);
 
 // The four derivative-filtered copies of x, staged position-major (k_gather_dot.hip): x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4][2]
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, bool bf16, float* xk, const Guard& guard);
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard);
 void blur4_pack_init(int blur_k);
 bool blur4_pack_fits(int blur_k, int Hp, int Wp);
 
@@ -119,17 +119,18 @@ void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, lon
 
 // Parameter gradients at fp32 accuracy on the f16 matrix cores (k_split_dot.hip): per input channel a GEMM with the four kinds x
 // four bilinear corners as rows, the units as columns and (position, image) as K, both operands split into two binary16 limbs.
-// Offsets within +-4, fp32 activations, interpolation on; the whole batch in one pass.
+// Offsets within +-4, fp32 or f16 activations, interpolation on; the whole batch in one pass.
 struct SplitDotConfig {
     Shape sh;
     int blur_k;
     int RW;               // region columns = K steps per item (10 or 12: the ring of error-window rows fills the LDS at 12)
+    int act;              // storage format of x and dy: kActF32 or kActF16
 };
-bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg);
+bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);
 void split_dot_init(const SplitDotConfig& cfg);
 // prepare: fp32 derivative filtering (blur4_pack), per-channel maxima, limb staging of Xk and of the error; run: the GEMM + the
-// reduction into r4 (all four kinds; x, dy fp32 NCHW; table = bare unit table [S][G][F])
+// reduction into r4 (all four kinds; x, dy fp32 or f16 NCHW; table = bare unit table [S][G][F])
 void split_dot_prepare(hipStream_t st, const SplitDotConfig& cfg, const float* x, const float* dy, const float* filters,
                        int drop_col, int drop_row, void* workspace, const Guard& guard);
 void split_dot_run(hipStream_t st, const SplitDotConfig& cfg, const UnitRef* table, float* r4, void* workspace, const Guard& guard);

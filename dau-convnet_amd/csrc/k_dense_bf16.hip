@@ -623,7 +623,7 @@ void stage_rows_plan(const DenseConfig& c, int* RB, int* nbands, size_t* lds) {
 bool dense_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, DenseConfig* cfg) {
     if (R != kDR || !bf16) return false;          // the 9 x 9 dense kernel covers offsets within +-4; bf16 layers only
     DenseConfig c{};
-    c.N = N; c.Cin = Cin; c.Cout = Cout; c.G = G; c.H = H; c.W = W; c.R = R; c.blur_k = blur_k; c.bf16 = 1;
+    c.N = N; c.Cin = Cin; c.Cout = Cout; c.G = G; c.H = H; c.W = W; c.R = R; c.blur_k = blur_k; c.act = kActBF16;
     const DenseGeom g = dense_geometry(c);
     c.nsub = g.nsub;
     // accumulator tiles per wave: 1 = eight waves per workgroup, two per SIMD (default: 3.71 ms against 4.24 ms with four
@@ -665,7 +665,7 @@ void dense_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
         else
             hipLaunchKernelGGL(densify_units_kernel, dim3(grid), dim3(256), 0, st, table, c.Cin, c.G, c.Cout, g.CoutP, g.nchunk, wd, guard);
     }
-    if (stage_rows_for(c.blur_k) && c.bf16 && DAU_TUNE_INT("DAU_DENSE_STAGE_FAST", 1)) {
+    if (stage_rows_for(c.blur_k) && c.act == kActBF16 && DAU_TUNE_INT("DAU_DENSE_STAGE_FAST", 1)) {
         DenseStageRowsArgs s{};
         s.in = reinterpret_cast<const unsigned short*>(in); s.taps = filters + kTaps1dOffset; s.xd = xd;
         s.N = c.N; s.C = c.Cin; s.H = c.H; s.W = c.W; s.mirrored = mirrored ? 1 : 0;
@@ -680,7 +680,7 @@ void dense_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     } else {
         DenseStageArgs s{};
         s.in = in; s.taps = filters + kTaps1dOffset; s.xd = xd;
-        s.N = c.N; s.C = c.Cin; s.H = c.H; s.W = c.W; s.k = c.blur_k; s.mirrored = mirrored ? 1 : 0; s.bf16 = c.bf16;
+        s.N = c.N; s.C = c.Cin; s.H = c.H; s.W = c.W; s.k = c.blur_k; s.mirrored = mirrored ? 1 : 0; s.bf16 = c.act == kActBF16;
         s.Hs = g.Hs; s.Ws = g.Ws; s.nchunk = g.nchunk; s.guard = guard;
         size_t lds;
         stage_tile(c, g, &s.TR, &s.TC, &lds);
@@ -697,7 +697,7 @@ void dense_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* wo
     DenseArgs a{};
     a.xd = xd; a.wd = wd; a.out = out;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
-    a.ncb = g.ncb; a.nrb = g.nrb; a.out_bf16 = c.bf16; a.guard = guard;
+    a.ncb = g.ncb; a.nrb = g.nrb; a.out_bf16 = c.act == kActBF16; a.guard = guard;
     const int grid = c.N * g.nrb * g.ncb * (g.CoutP / kDFB);
     dispatch_dense(c.nsub, c.ftiles, st, &a, grid);
 }

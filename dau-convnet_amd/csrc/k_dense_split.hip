@@ -156,12 +156,22 @@ constexpr int lds_pitch_narrow(int ntiles) {
 // ------------------------------------------------------------------------------------------------
 // scales: max|input| and max|w| (two launches: per-workgroup maxima, then one workgroup reduces them and derives the scales)
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restrict__ in, long count, int bf16, const UnitRef* __restrict__ table,
+__global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restrict__ in, long count, int act, const UnitRef* __restrict__ table,
                                                            long units, unsigned* __restrict__ partial, const Guard guard) {
     if (!guard_pass(guard)) return;
     unsigned mx = 0, mw = 0;
     const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (bf16) {
+    if (act == kActF16) {
+        // the widened values' bits, so that the maximum (and the scales) are those of the same input given as fp32
+        auto wide = [](unsigned h) { return __float_as_uint(f16_bits_to_float(h)) & 0x7fffffffu; };
+        const uint2* p = reinterpret_cast<const uint2*>(in);          // four f16 per load
+        const long n4 = reinterpret_cast<uintptr_t>(in) % 8 == 0 ? count / 4 : 0;
+        for (long i = t0; i < n4; i += stride) {
+            const uint2 v = p[i];
+            mx = max(mx, max(max(wide(v.x & 0xffffu), wide(v.x >> 16)), max(wide(v.y & 0xffffu), wide(v.y >> 16))));
+        }
+        for (long i = n4 * 4 + t0; i < count; i += stride) mx = max(mx, wide(reinterpret_cast<const unsigned short*>(in)[i]));
+    } else if (act == kActBF16) {
         const uint2* p = reinterpret_cast<const uint2*>(in);          // four bf16 per load
         const long n4 = reinterpret_cast<uintptr_t>(in) % 8 == 0 ? count / 4 : 0;
         for (long i = t0; i < n4; i += stride) {
@@ -362,7 +372,7 @@ __device__ __forceinline__ void split_stage_walk(const float* rawl, const float*
 #define DAU_SPLIT_STAGE_THREADS 512        // eight waves share a band (same box: 375 us per pass at the north-star shape with 256 threads, 362 with 512)
 #endif
 constexpr int kStageThreads = DAU_SPLIT_STAGE_THREADS;
-template <int K, bool BF>
+template <int K, int A>
 __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitStageArgs a) {
     extern __shared__ __attribute__((aligned(16))) float rawl[];   // [row][8 channels][kSP]
     if (!guard_pass(a.guard)) return;
@@ -394,7 +404,11 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
                 if (a.vec) {
                     const bool ok = row_in && xs >= 0 && xs + 4 <= a.W;
                     const long idx = base + (ok ? (long)y * a.W + xs : 0);
-                    if constexpr (BF) {
+                    if constexpr (A == kActF16) {
+                        const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.in) + idx);
+                        v[u] = make_float4(mask_act(f16_bits_to_float(w.x & 0xffffu), ok), mask_act(f16_bits_to_float(w.x >> 16), ok),
+                                           mask_act(f16_bits_to_float(w.y & 0xffffu), ok), mask_act(f16_bits_to_float(w.y >> 16), ok));
+                    } else if constexpr (A == kActBF16) {
                         const uint2 w = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(a.in) + idx);
                         const unsigned m = ok ? 0xffffffffu : 0u;
                         v[u] = make_float4(__uint_as_float((w.x << 16) & m), __uint_as_float(w.x & 0xffff0000u & m),
@@ -408,7 +422,7 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const bool ok = row_in && xs + k >= 0 && xs + k < a.W;
-                        e[k] = mask_act(load_act_t<BF>(a.in, base + (ok ? (long)y * a.W + xs + k : 0)), ok);
+                        e[k] = mask_act(load_act_t<A>(a.in, base + (ok ? (long)y * a.W + xs + k : 0)), ok);
                     }
                     v[u] = make_float4(e[0], e[1], e[2], e[3]);
                 }
@@ -463,8 +477,8 @@ struct SplitArgs {
     const _Float16* xs;
     const _Float16* wsd;
     const SplitScales* sc;
-    float* out;               // [N][Cout][H][W], f32 or bf16
-    int N, Cout, CoutP, H, W, Hs, Ws, nchunk, ncb, nrb, out_bf16;
+    float* out;               // [N][Cout][H][W], f32, bf16 or f16
+    int N, Cout, CoutP, H, W, Hs, Ws, nchunk, ncb, nrb, out_act;   // out_act: ActFormat of out
     int col0;                 // first column of this launch's blocks (a row is covered by blocks of NSUB and of NSUB - 1 tiles)
     int row0;                 // first row of this launch's row blocks (a map whose height leaves 1 .. 4 rows after its 8-row blocks
                               // ends with one block of FOUR rows: RG = 1)
@@ -478,7 +492,8 @@ struct SplitArgs {
 // 8 rows x NSUB*4 columns, its eight waves 4 (32 channels) x 2 (column halves of (NSUB + 1) / 2 and NSUB / 2 tiles -- the two waves of a
 // SIMD, so the SIMD's work is NSUB tiles).  For maps whose width is 1 .. 4 columns more than a multiple of eight (28 = 7 x 4: no padded
 // columns where 4 x 8 tiles pad to 32).
-template <int NSUB, int RG = 2, bool TT = false>
+// H16: out is binary16 (an instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
+template <int NSUB, int RG = 2, bool TT = false, bool H16 = false>
 __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     static_assert(!TT || RG == 2, "tall tiles: blocks of eight rows");
     constexpr int TW = TT ? 4 : 8;                           // columns of a tile
@@ -546,7 +561,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     const int prr = TT ? nn >> 2 : nn >> 3, pcc = TT ? nn & 3 : nn & 7;   // this lane's position inside a tile
     // (kernel arguments the epilogue uses, read once: inside the lambda hipcc reloads them from the argument segment at every store)
     float* const out_ptr = a.out;
-    const bool out_bf16 = a.out_bf16 != 0;
+    const bool out_bf16 = a.out_act != 0;                   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
     auto body = [&](auto ntc) __attribute__((always_inline)) {
     constexpr int NT = decltype(ntc)::value;                 // tiles of this wave
@@ -657,7 +672,11 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int f = fb * kDFB + fw * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (f < out_c) store_act(out_ptr, ((long)n * out_c + f) * plane + (long)y * out_w + x, sum[j][i] * inv, out_bf16, false);
+                if (f < out_c) {
+                    const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
+                    if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv, false);
+                    else store_act(out_ptr, o, sum[j][i] * inv, out_bf16, false);
+                }
             }
         }
     }
@@ -680,38 +699,40 @@ template <int NSUB, int RG, bool TT>
 constexpr size_t split_lds_bytes() { return 2 * (size_t)((4 * (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB)) + 63) / 64) * 1024; }
 
 template <int NSUB, int RG, bool TT = false>
-void launch_split(hipStream_t st, const SplitArgs* a, int grid) {
-    auto kern = split_gather_kernel<NSUB, RG, TT>;
+void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16) {
+    auto kern = h16 ? split_gather_kernel<NSUB, RG, TT, true> : split_gather_kernel<NSUB, RG, TT, false>;
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     constexpr size_t lds = split_lds_bytes<NSUB, RG, TT>();      // (a comma inside the launch macro's arguments would split them)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, *a);
 }
 
-void dispatch_split(int nsub, int rg, hipStream_t st, const SplitArgs* a, int grid, bool tall = false) {
+void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall = false) {
     if (tall) {                                              // nsub = tiles of four columns: 5 or 7 (split_geometry)
-        if (nsub == 5) launch_split<5, 2, true>(st, a, grid);
-        else launch_split<7, 2, true>(st, a, grid);
+        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16);
+        else launch_split<7, 2, true>(st, a, grid, h16);
         return;
     }
     if (rg == 1) {
         switch (nsub) {
-            case 1: launch_split<1, 1>(st, a, grid); break;
-            case 2: launch_split<2, 1>(st, a, grid); break;
-            case 3: launch_split<3, 1>(st, a, grid); break;
-            default: launch_split<4, 1>(st, a, grid); break;
+            case 1: launch_split<1, 1>(st, a, grid, h16); break;
+            case 2: launch_split<2, 1>(st, a, grid, h16); break;
+            case 3: launch_split<3, 1>(st, a, grid, h16); break;
+            default: launch_split<4, 1>(st, a, grid, h16); break;
         }
         return;
     }
     switch (nsub) {
-        case 1: launch_split<1, 2>(st, a, grid); break;
-        case 2: launch_split<2, 2>(st, a, grid); break;
-        case 3: launch_split<3, 2>(st, a, grid); break;
-        default: launch_split<4, 2>(st, a, grid); break;
+        case 1: launch_split<1, 2>(st, a, grid, h16); break;
+        case 2: launch_split<2, 2>(st, a, grid, h16); break;
+        case 3: launch_split<3, 2>(st, a, grid, h16); break;
+        default: launch_split<4, 2>(st, a, grid, h16); break;
     }
 }
 
-const void* stage_for(int blur_k, bool bf16) {
-#define DAU_SPLIT_STAGE(K) case K: return bf16 ? reinterpret_cast<const void*>(split_stage_kernel<K, true>) : reinterpret_cast<const void*>(split_stage_kernel<K, false>)
+const void* stage_for(int blur_k, int act) {
+#define DAU_SPLIT_STAGE(K) case K: return act == kActF16 ? reinterpret_cast<const void*>(split_stage_kernel<K, kActF16>) : \
+                                          act == kActBF16 ? reinterpret_cast<const void*>(split_stage_kernel<K, kActBF16>) : \
+                                                            reinterpret_cast<const void*>(split_stage_kernel<K, kActF32>)
     switch (blur_k) {
         DAU_SPLIT_STAGE(3);
         DAU_SPLIT_STAGE(5);
@@ -736,10 +757,10 @@ void stage_plan(const DenseConfig& c, int* RB, int* nbands, size_t* lds) {
 
 }  // namespace
 
-bool split_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, DenseConfig* cfg) {
-    if (R != kDR || !stage_for(blur_k, bf16)) return false;
+bool split_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, DenseConfig* cfg) {
+    if (R != kDR || !stage_for(blur_k, act)) return false;
     DenseConfig c{};
-    c.N = N; c.Cin = Cin; c.Cout = Cout; c.G = G; c.H = H; c.W = W; c.R = R; c.blur_k = blur_k; c.bf16 = bf16 ? 1 : 0;
+    c.N = N; c.Cin = Cin; c.Cout = Cout; c.G = G; c.H = H; c.W = W; c.R = R; c.blur_k = blur_k; c.act = act;
     const SplitGeom g = split_geometry(c);
     c.nsub = g.nsub_a;
     c.ftiles = 1;
@@ -756,13 +777,14 @@ size_t split_gather_workspace_bytes(const DenseConfig& c) {
 
 void split_gather_init(const DenseConfig& c) {
     const SplitGeom g = split_geometry(c);
+    const bool h16 = c.act == kActF16;
     for (int rg = 1; rg <= 2; ++rg) {
         if (!(rg == 2 ? g.nrb8 : g.nrb4)) continue;
-        if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, nullptr, nullptr, 0, true); continue; }
-        dispatch_split(g.nsub_a, rg, nullptr, nullptr, 0);
-        if (g.nb_b) dispatch_split(g.nsub_b, rg, nullptr, nullptr, 0);
+        if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true); continue; }
+        dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0);
+        if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0);
     }
-    (void)hipFuncSetAttribute(stage_for(c.blur_k, c.bf16 != 0), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(stage_for(c.blur_k, c.act), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in, const float* filters, bool mirrored,
@@ -775,7 +797,7 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     _Float16* wsd = reinterpret_cast<_Float16*>(ws + g.hdr_bytes + g.xs_bytes);
     const long count = (long)c.N * c.Cin * c.H * c.W, units = (long)c.Cin * c.G * c.Cout;
     const int nparts = (int)std::min<long>(kPartials, (count / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(split_absmax_kernel, dim3(nparts), dim3(256), 0, st, in, count, c.bf16, table, units, partial, guard);
+    hipLaunchKernelGGL(split_absmax_kernel, dim3(nparts), dim3(256), 0, st, in, count, c.act, table, units, partial, guard);
     hipLaunchKernelGGL(split_scales_kernel, dim3(1), dim3(256), 0, st, partial, nparts, c.G, sc, guard);
     hipLaunchKernelGGL(split_densify_kernel, dim3(g.nchunk * (g.CoutP / (kScT / 16))), dim3(kScT), 0, st, table, c.Cin, c.G, c.Cout, g.CoutP,
                        g.nchunk, sc, wsd, guard);
@@ -788,11 +810,12 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     s.nsegs = (c.W + 63) / 64;
     s.vec = c.W % 4 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0;
     void* args[] = {&s};
-    (void)hipLaunchKernel(stage_for(c.blur_k, c.bf16 != 0), dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(kStageThreads), args, lds, st);
+    (void)hipLaunchKernel(stage_for(c.blur_k, c.act), dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(kStageThreads), args, lds, st);
 }
 
 void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* workspace, const Guard& guard) {
     const SplitGeom g = split_geometry(c);
+    const bool h16 = c.act == kActF16;
     char* ws = static_cast<char*>(workspace);
     SplitArgs a{};
     a.sc = reinterpret_cast<const SplitScales*>(ws);
@@ -800,21 +823,21 @@ void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* wo
     a.wsd = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes + g.xs_bytes);
     a.out = out;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
-    a.out_bf16 = c.bf16; a.guard = guard;
+    a.out_act = c.act; a.guard = guard;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
         a.nrb = rg == 2 ? g.nrb8 : g.nrb4;
         if (!a.nrb) continue;
         a.row0 = rg == 2 ? 0 : g.nrb8 * kDRows;
         if (rg == 2 && g.tall) {                             // one column block of tall tiles
             a.ncb = 1; a.col0 = 0;
-            dispatch_split(g.tall, 2, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true);
+            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true);
             continue;
         }
         a.ncb = g.nb_a; a.col0 = 0;
-        dispatch_split(g.nsub_a, rg, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB));
+        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB));
         if (g.nb_b) {
             a.ncb = g.nb_b; a.col0 = g.nb_a * g.nsub_a * 8;
-            dispatch_split(g.nsub_b, rg, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB));
+            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB));
         }
     }
 }

@@ -223,7 +223,7 @@ DotGeometry make_dot_geometry(const Shape& sh, int R, bool as1 = false, bool one
 constexpr int kPackErrorChunk = 512;   // padded columns per workgroup (LDS: 64 rows of up to 513 floats)
 
 __global__ void __launch_bounds__(256) pack_error_kernel(const float* __restrict__ dy, int N, int F, int H, int W, int R,
-                                                         int EX, int EY, int nfb, int drop_col, int drop_row, int bf16,
+                                                         int EX, int EY, int nfb, int drop_col, int drop_row, int act,
                                                          float* __restrict__ ep, const Guard guard) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [64 = 32 f x 2 images][chunk width | 1]
     if (!guard_pass(guard)) return;
@@ -243,11 +243,11 @@ __global__ void __launch_bounds__(256) pack_error_kernel(const float* __restrict
     if (rowin && cw > 0) {
         // flat over (r = fl*2 + image, x): narrow maps keep all lanes busy (a 7-pixel row per wave instruction did not)
         // (the loads of kLoadBatch items go out before the first is stored, branch free: see load_phase in dau_common.hpp)
-        auto fill = [&](auto bfc) {
-            constexpr bool BF = decltype(bfc)::value;
+        auto fill = [&](auto actc) {
+            constexpr int AF = decltype(actc)::value;
             const int total = 64 * cw;
             for (int t0 = threadIdx.x; t0 < total; t0 += blockDim.x * kLoadBatch) {
-                typename RawAct<BF>::type v[kLoadBatch];
+                typename RawAct<AF>::type v[kLoadBatch];
                 int rr[kLoadBatch];
                 bool okk[kLoadBatch];
 #pragma unroll
@@ -258,7 +258,7 @@ __global__ void __launch_bounds__(256) pack_error_kernel(const float* __restrict
                     const int f = fb * kDF + (r >> 1), n = 2 * np + (r & 1);
                     const bool ok = f < F && n < N;
                     const long src = (((long)(ok ? n : 0) * F + (ok ? f : 0)) * H + y) * W + xa0;
-                    v[u] = load_raw<BF>(dy, src + x);
+                    v[u] = load_raw<AF>(dy, src + x);
                     okk[u] = ok;
                 }
 #pragma unroll
@@ -268,7 +268,7 @@ __global__ void __launch_bounds__(256) pack_error_kernel(const float* __restrict
                 }
             }
         };
-        if (bf16) fill(std::true_type{}); else fill(std::false_type{});
+        with_act(act, fill);
     }
     __syncthreads();
     float* out = ep + ((((size_t)np * nfb + fb) * EY + Y) * EX + X0) * (kDF * 2);
@@ -287,7 +287,7 @@ struct Blur4Args {
     const float* taps;
     float* xk;
     int N, C, cstride, H, W, k, Hp, Wp;
-    int bf16;                   // input is bfloat16
+    int act;                    // storage format of the input (ActFormat)
     int ppb, items;             // windows per workgroup (small maps) and windows in total
     unsigned lds_item_floats;   // LDS floats per window
     int WY, WX, nwy, nwx;       // output window (rows x columns of the Hp x Wp plane) and windows per plane
@@ -333,7 +333,6 @@ __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
     const bool real = c < Creal;
     const int cs = real ? c : 0;
     const long p0 = ((long)n0 * Creal + cs) * H * W, p1 = ((long)(n1 < a.N ? n1 : n0) * Creal + cs) * H * W;   // element offsets
-    const bool bf16 = a.bf16 != 0;
     const float m0 = real ? 1.0f : 0.0f;
     const float m1 = (real && n1 < a.N) ? 1.0f : 0.0f;
     // rows x cols of work for this window's waves: a wave per row when the rows are wide, a flat index when they are narrow
@@ -346,15 +345,15 @@ __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
         }
     };
     // raw window -> LDS, the loads of a batch in flight together (load_phase, dau_common.hpp)
-    auto fill = [&](auto bfc) {
-        constexpr bool BF = decltype(bfc)::value;
-        struct Raw2 { typename RawAct<BF>::type v0, v1; };
+    auto fill = [&](auto actc) {
+        constexpr int AF = decltype(actc)::value;
+        struct Raw2 { typename RawAct<AF>::type v0, v1; };
         load_phase<Raw2>(lh, lw, wave, nw, lane,
             [&](int r, int xl) {
                 const int yy = oy0 - kr + r, xx = ox0 - kr + xl;
                 const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
                 const long off = in ? (long)yy * W + xx : 0;            // outside the image: element 0 (valid), discarded
-                return Raw2{load_raw<BF>(a.in, p0 + off), load_raw<BF>(a.in, p1 + off)};
+                return Raw2{load_raw<AF>(a.in, p0 + off), load_raw<AF>(a.in, p1 + off)};
             },
             [&](int r, int xl, Raw2 v) {
                 const int yy = oy0 - kr + r, xx = ox0 - kr + xl;
@@ -362,7 +361,7 @@ __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
                 A[r * lw + xl] = f2{mask_act(m0 * act_of(v.v0), in), mask_act(m1 * act_of(v.v1), in)};
             });
     };
-    if (bf16) fill(std::true_type{}); else fill(std::false_type{});
+    with_act(a.act, fill);
     __syncthreads();
     for_each(lh, ow, [&](int r, int x) {
         const int yy = oy0 - kr + r;
@@ -1346,14 +1345,14 @@ auto blur4_pack_for(int blur_k) {
 
 // x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, bool bf16, float* xk, const Guard& guard) {
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard) {
     int wy, wx; size_t blur_lds;
     blur4_plan(blur_k, Hp, Wp, &wy, &wx, &blur_lds);
     auto kern = blur4_pack_for(blur_k);
     Blur4Args b{};
     b.guard = guard;
     b.in = x; b.taps = filters + kTaps1dOffset; b.xk = xk;
-    b.N = N; b.C = C; b.cstride = cstride; b.H = H; b.W = W; b.k = blur_k; b.Hp = Hp; b.Wp = Wp; b.bf16 = bf16 ? 1 : 0;
+    b.N = N; b.C = C; b.cstride = cstride; b.H = H; b.W = W; b.k = blur_k; b.Hp = Hp; b.Wp = Wp; b.act = act;
     b.WY = wy; b.WX = wx; b.nwy = (Hp + wy - 1) / wy; b.nwx = (Wp + wx - 1) / wx;
     // small windows: several per workgroup, so that the 512 threads have rows to share
     const int elems = wy * wx;
@@ -1378,7 +1377,7 @@ bool blur4_pack_fits(int blur_k, int Hp, int Wp) {
     return blur_lds <= 150 * 1024;
 }
 
-bool tiled_dot_configure(const Shape& sh, int R, int blur_k, bool bf16, int ignore, TiledDotConfig* cfg) {
+bool tiled_dot_configure(const Shape& sh, int R, int blur_k, int act, int ignore, TiledDotConfig* cfg) {
     // timing experiments: DAU_DOT_AS1 (one input channel per wave), DAU_DOT_NBUF=1 (one error tile), DAU_DOT_DEBUG
     const bool as1 = DAU_TUNE_SET("DAU_DOT_AS1");
     const bool one_tile = DAU_TUNE_INT("DAU_DOT_NBUF", 2) == 1;
@@ -1397,7 +1396,7 @@ bool tiled_dot_configure(const Shape& sh, int R, int blur_k, bool bf16, int igno
     }
     TiledDotConfig c{};
     c.sh = sh; c.R = R; c.blur_k = blur_k; c.NP = (sh.N + 1) / 2; c.variant = g.npass; c.windows = g.nsub1 * g.nsub1;
-    c.bf16 = bf16; c.ignore = ignore;
+    c.act = act; c.ignore = ignore;
     c.ring = g.nsub1 > 1 && g.nbuf == 1 && DAU_TUNE_INT("DAU_DOT_RING", 1) != 0;
     c.as1 = as1; c.one_tile = one_tile; c.rounds = rounds; c.rw8 = rw8; c.region_cols = g.RW; c.region_rows = g.RH; c.debug = DAU_TUNE_INT("DAU_DOT_DEBUG", 0);
     *cfg = c;
@@ -1427,10 +1426,10 @@ void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& c, const float* x, 
         const size_t lds = (size_t)64 * (cwmax | 1) * 4;
         const int nxc = (g.EX + kPackErrorChunk - 1) / kPackErrorChunk;
         hipLaunchKernelGGL(pack_error_kernel, dim3(c.NP * g.nfb * g.EY * nxc), dim3(256), lds, st, dy, s.N, s.F, s.H, s.W, g.Rp, g.EX,
-                           g.EY, g.nfb, drop_col, drop_row, c.bf16 ? 1 : 0, reinterpret_cast<float*>(ws + l.ep_off), guard);
+                           g.EY, g.nfb, drop_col, drop_row, c.act, reinterpret_cast<float*>(ws + l.ep_off), guard);
     }
     // channel slots beyond S (padding of the last input-channel block) are written as zero planes by the kernel
-    launch_blur4_pack(st, x, filters, s.N, s.S, s_pad, s.H, s.W, g.Hp, g.Wp, c.blur_k, c.bf16, reinterpret_cast<float*>(ws + l.xk_off), guard);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s_pad, s.H, s.W, g.Hp, g.Wp, c.blur_k, c.act, reinterpret_cast<float*>(ws + l.xk_off), guard);
     if (g.nsub1 > 1) {
         const DotGeometry::Pass& ps = g.pass[0];
         hipLaunchKernelGGL(dot_worklist_kernel, dim3(g.nsub1 * g.nsub1 * g.nfb * ps.nsb), dim3(1024), 0, st, table_bare, s.S, s.G, s.F,

@@ -211,7 +211,7 @@ struct BlurPackArgs {
     const float* taps;
     float* staged;
     int mirrored, N, C, H, W, R, k;
-    int bf16;                   // input is bfloat16 (DAU_FLAG_IO_BF16)
+    int act;                    // storage format of the input (ActFormat)
     int cy, cx;                 // offset-window centre (0 unless the bucket is cut into windows)
     int ph, pw, npx, npy;
     int rows, pitch, cols, strip_cols;
@@ -268,7 +268,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
     auto gy = [&](int i) { return K ? gyr[i] : gyp[i]; };
     const int n0 = 2 * np, n1 = 2 * np + 1;
     const long p0 = ((long)n0 * C + c) * H * W, p1 = ((long)(n1 < a.N ? n1 : n0) * C + c) * H * W;   // element offsets
-    const bool bf16 = a.bf16 != 0;
     const float m1 = n1 < a.N ? 1.0f : 0.0f;      // odd batch: the second image of the last pair is zero
     // rows x cols of work for this plane's waves: a wave per row when the rows are wide, a flat index when they are narrow
     // (a 7-pixel row would leave most of a wave idle)
@@ -282,15 +281,15 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
         }
     };
     // raw window -> LDS, the loads of a batch in flight together (load_phase, dau_common.hpp)
-    auto fill = [&](auto bfc) {
-        constexpr bool BF = decltype(bfc)::value;
-        struct Raw2 { typename RawAct<BF>::type v0, v1; };
+    auto fill = [&](auto actc) {
+        constexpr int AF = decltype(actc)::value;
+        struct Raw2 { typename RawAct<AF>::type v0, v1; };
         load_phase<Raw2>(lh, lw, wave, nw, lane,
             [&](int r, int xl) {
                 const int yy = ya0 - kr + r, xx = xa0 - kr + xl;
                 const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
                 const long off = in ? (long)yy * W + xx : 0;            // outside the image: element 0 (valid), discarded
-                return Raw2{load_raw<BF>(a.in, p0 + off), load_raw<BF>(a.in, p1 + off)};
+                return Raw2{load_raw<AF>(a.in, p0 + off), load_raw<AF>(a.in, p1 + off)};
             },
             [&](int r, int xl, Raw2 v) {
                 const int yy = ya0 - kr + r, xx = xa0 - kr + xl;
@@ -298,7 +297,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
                 A[r * lw + xl] = f2{mask_act(act_of(v.v0), in), mask_act(m1 * act_of(v.v1), in)};
             });
     };
-    if (bf16) fill(std::true_type{}); else fill(std::false_type{});
+    with_act(a.act, fill);
     __syncthreads();
     for_each(lh, bw, [&](int r, int x) {
         const int yy = ya0 - kr + r;
@@ -427,7 +426,7 @@ struct GatherArgs {
     unsigned strip_off;        // byte offset of the transposed strip inside a plane
     unsigned zpitch;           // epilogue Z-plane pitch (floats)
     int accumulate;            // 1: add to out (second and later offset-window passes)
-    int bf16;                  // out is bfloat16 (DAU_FLAG_IO_BF16)
+    int act;                   // storage format of out (ActFormat)
     int debug;                 // timing experiments only (DAU_GATHER_DEBUG): 1 = no plane refills after the first two
     int binned;                // window pass: every channel's slot count comes from its slice's count words
     Guard guard;
@@ -586,7 +585,8 @@ __device__ __forceinline__ void unit_group(f4 (&acc)[KP][2], unsigned ut_addr0, 
 
 // Whole per-wave program for one PART (the part only selects which tiles the wave owns, so that all
 // LDS immediates are compile-time constants; every wave runs the same number of barriers).
-template <class T, int PART>
+// H16: out is binary16 (a compile-time instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
+template <class T, int PART, bool H16>
 __device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int lane, int wave, int fi) {
     // lagged kernels: the waves of the second half (SIMD partners of the first) run one unit behind (GatherTraits::NB)
     const bool lag = T::LAGGED && wave >= T::kWaves / 2;
@@ -760,13 +760,17 @@ __device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int
                 const float* zf = zs + (size_t)kf * zchan + (unsigned)y * zpitch + x;
                 const float v = zf[0] + zf[zplane + 1] + zf[2 * zplane + zpitch] + zf[3 * zplane + zpitch + 1];
                 if (npp < npp_total && n < a.N && f < a.Cout && gy < a.H && gx < a.W)
-                    store_act(a.out, ((long)n * a.Cout + f) * plane_out + (long)gy * a.W + gx, v, a.bf16 != 0, a.accumulate != 0);
+                {
+                    const long o = ((long)n * a.Cout + f) * plane_out + (long)gy * a.W + gx;
+                    if constexpr (H16) store_act_t<kActF16>(a.out, o, v, a.accumulate != 0);
+                    else store_act(a.out, o, v, a.act != 0, a.accumulate != 0);          // act: kActF32 or kActBF16
+                }
             }
         }
     }
 }
 
-template <class T>
+template <class T, bool H16>
 __global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const GatherArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (!guard_pass(a.guard)) return;
@@ -774,10 +778,10 @@ __global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const GatherAr
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int part = wave % SPLIT, fi = wave / SPLIT;
-    if (SPLIT == 1 || part == 0) gather_body<T, 0>(a, smem, lane, wave, fi);
-    else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1>(a, smem, lane, wave, fi); }
-    else if (SPLIT == 3 || part == 2) { if constexpr (SPLIT > 2) gather_body<T, 2>(a, smem, lane, wave, fi); }
-    else { if constexpr (SPLIT > 3) gather_body<T, 3>(a, smem, lane, wave, fi); }
+    if (SPLIT == 1 || part == 0) gather_body<T, 0, H16>(a, smem, lane, wave, fi);
+    else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1, H16>(a, smem, lane, wave, fi); }
+    else if (SPLIT == 3 || part == 2) { if constexpr (SPLIT > 2) gather_body<T, 2, H16>(a, smem, lane, wave, fi); }
+    else { if constexpr (SPLIT > 3) gather_body<T, 3, H16>(a, smem, lane, wave, fi); }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -786,50 +790,51 @@ __global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const GatherAr
 namespace {
 
 // a == nullptr: raise the kernel's dynamic-LDS limit (once per plan and device, tiled_gather_init); else launch
+// h16: the instantiation with binary16 output (DAU_FLAG_IO_F16)
 template <class T>
-void launch_variant(hipStream_t st, const GatherArgs* a, int grid, size_t lds) {
-    auto kern = gather_mfma_kernel<T>;
+void launch_variant(hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16) {
+    auto kern = h16 ? gather_mfma_kernel<T, true> : gather_mfma_kernel<T, false>;
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, *a);
 }
 
-void dispatch_variant(int variant, hipStream_t st, const GatherArgs* a, int grid, size_t lds) {
+void dispatch_variant(int variant, hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16) {
     switch (variant) {
-        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds); break;
-        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds); break;
-        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds); break;
-        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds); break;
-        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds); break;
-        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds); break;
-        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds); break;
+        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16); break;
+        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16); break;
+        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds, h16); break;
+        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds, h16); break;
+        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds, h16); break;
+        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds, h16); break;
+        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds, h16); break;
 #ifdef DAU_TUNING
-        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds); break;
+        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds, h16); break;
 #endif
-        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds); break;
-        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds); break;
-        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds); break;
-        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds); break;
-        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds); break;
-        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds); break;
-        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds); break;
-        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds); break;
-        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds); break;
-        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds); break;
-        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds); break;
+        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds, h16); break;
+        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds, h16); break;
+        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds, h16); break;
+        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds, h16); break;
+        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds, h16); break;
+        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds, h16); break;
+        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds, h16); break;
+        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds, h16); break;
+        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds, h16); break;
+        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds, h16); break;
+        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds, h16); break;
 #ifdef DAU_TUNING
-        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds); break;
+        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds, h16); break;
 #endif
 #ifdef DAU_TUNING
-        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds); break;
+        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds, h16); break;
 #endif
-        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds); break;
-        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds); break;
-        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds); break;
+        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
+        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
+        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
 #ifdef DAU_TUNING                // explicit-request rows (Variant::tuning != 0) exist in the tuning build only
-        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds); break;
-        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds); break;
-        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds); break;
-        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds); break;
+        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16); break;
+        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16); break;
+        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16); break;
+        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16); break;
 #endif
         default: break;
     }
@@ -867,7 +872,7 @@ size_t lds_bytes(const TiledConfig& c, const Geometry& g) {
 
 }  // namespace
 
-bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, TiledConfig* cfg) {
+bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, TiledConfig* cfg) {
     const Geometry g = make_geometry(H, W, R, G, N, Cout);
     if (g.variant < 0) return false;
     TiledConfig c{};
@@ -876,7 +881,7 @@ bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R
     c.rows = g.rows; c.pitch = g.pitch; c.tiles_x = g.tx; c.tiles_y = g.ty; c.tile_w = g.tw; c.fblock = g.fb; c.variant = g.variant;
     c.patches = g.npx * g.npy; c.stack = g.sk; c.windows = g.nwin1 * g.nwin1;
     c.debug = DAU_TUNE_INT("DAU_GATHER_DEBUG", 0);
-    c.bf16 = bf16 ? 1 : 0;
+    c.act = act;
     if (lds_bytes(c, g) > 160 * 1024) return false;
     // blur_pack keeps both raw planes (+ blur halo) and the horizontally filtered rows in LDS
     if (blur_pack_lds_bytes(g, blur_k, (g.rows + blur_pack_bands(g, blur_k) - 1) / blur_pack_bands(g, blur_k)) > 150 * 1024) return false;
@@ -891,7 +896,7 @@ size_t tiled_gather_workspace_bytes(const TiledConfig& c) {
 }
 
 void tiled_gather_init(const TiledConfig& c) {
-    dispatch_variant(c.variant, nullptr, nullptr, 0, 0);
+    dispatch_variant(c.variant, nullptr, nullptr, 0, 0, c.act == kActF16);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur_pack_for(c.blur_k)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -912,7 +917,7 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
     // centre of this pass's offset window: staged (row, col) of a patch is the image at (py*ph - Rt + cy + row, ...)
     const int cy = -c.R + g.Rt + 2 * g.Rt * (window / g.nwin1), cx = -c.R + g.Rt + 2 * g.Rt * (window % g.nwin1);
     b.mirrored = mirrored ? 1 : 0; b.N = c.N; b.C = c.Cin; b.H = c.H; b.W = c.W; b.R = g.Rt; b.k = c.blur_k;
-    b.cy = cy; b.cx = cx; b.bf16 = c.bf16;
+    b.cy = cy; b.cx = cx; b.act = c.act;
     b.ph = g.ph; b.pw = g.pw; b.npx = g.npx; b.npy = g.npy;
     b.rows = g.rows; b.pitch = g.pitch; b.cols = g.cols; b.strip_cols = g.edge ? 2 * g.Rt + 1 : 0;
     b.plane_floats = g.plane_bytes / 4;
@@ -956,7 +961,7 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.out = out;
     a.npx = g.npx; a.npy = g.npy; a.ph = g.ph; a.pw = g.pw;
     a.N = c.N; a.Cin = c.Cin; a.Cout = c.Cout; a.G = c.G; a.H = c.H; a.W = c.W; a.R = g.Rt;
-    a.accumulate = accumulate ? 1 : 0; a.bf16 = c.bf16;
+    a.accumulate = accumulate ? 1 : 0; a.act = c.act;
     a.nfb = (c.Cout + g.fb - 1) / g.fb;
     a.plane_bytes = (unsigned)g.plane_bytes;
     a.strip_off = (unsigned)g.strip_off;
@@ -967,7 +972,7 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.debug = c.debug;
     const int grid = ((c.NP * c.patches + g.sk - 1) / g.sk) * a.nfb;
     const size_t lds = lds_bytes(c, g);
-    dispatch_variant(c.variant, st, &a, grid, lds);
+    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16);
 }
 
 }  // namespace dau

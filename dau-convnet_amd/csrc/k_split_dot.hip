@@ -136,8 +136,8 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
     if (threadIdx.x < 4) atomicMax(&xmax[s * kNumK + threadIdx.x], __float_as_uint(red[threadIdx.x][0]));
 }
 
-// max |dy| per output channel: grid (F, split)
-__global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split,
+// max |dy| per output channel: grid (F, split); dy is fp32 or f16 (act)
+__global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
                                                           unsigned* __restrict__ emax, const Guard guard) {
     if (!guard_pass(guard)) return;
     const int f = blockIdx.x % F, part = blockIdx.x / F;
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restric
     for (long i = part * 256L + threadIdx.x; i < total; i += 256L * split) {
         const long n = i / HW, p = i - n * HW;
         float a;
-        if (finite_abs(dy[((size_t)n * F + f) * HW + p], &a)) m = fmaxf(m, a);
+        if (finite_abs(load_act(dy, ((long)n * F + f) * HW + p, act), &a)) m = fmaxf(m, a);
     }
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     if ((threadIdx.x & 63) == 0) atomicMax(&emax[f], __float_as_uint(m));
@@ -202,10 +202,11 @@ __global__ void __launch_bounds__(256) sd_stage_x_kernel(const float* __restrict
     }
 }
 
-// ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W]: one thread per (oct, fb, Vy, Vx), the 16 channels of the block
+// ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W] (fp32 or f16: act): one thread per (oct, fb, Vy, Vx), the 16 channels
+// of the block.  An f16 dy times the power-of-two scale is its own hi limb; its lo limb is zero.
 __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
                                                          int F, int H, int W, int octs, int nfb, int EYs, int EXs, int drop_col,
-                                                         int drop_row, h8* __restrict__ es, const Guard guard) {
+                                                         int drop_row, int act, h8* __restrict__ es, const Guard guard) {
     if (!guard_pass(guard)) return;
     const long total = (long)octs * nfb * EYs * EXs;
     const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
@@ -225,7 +226,7 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int n = oct * 8 + i;
-                const float v = (in && f < F && n < N) ? dy[(((size_t)n * F + f) * H + y) * W + x] : 0.0f;
+                const float v = (in && f < F && n < N) ? load_act(dy, (((long)n * F + f) * H + y) * W + x, act) : 0.0f;
                 _Float16 h, l;
                 split_limbs(v * sc, &h, &l);
                 hi[i] = h; lo[i] = l;
@@ -483,8 +484,8 @@ void dispatch_sd(int RW, hipStream_t st, const SdArgs* a, int grid) {
 
 }  // namespace
 
-bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig* cfg) {
-    if (bf16) return false;
+bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg) {
+    if (act == kActBF16) return false;
     // the region width whose ring of error-window rows fits the LDS (RW <= 12) with the least work: the q columns (W + 1) padded
     // to a multiple of RW, plus about two K steps' worth of per-item cost (barrier, bilinear epilogue) per region
     int best = 0;
@@ -497,7 +498,7 @@ bool split_dot_configure(const Shape& sh, int blur_k, bool bf16, SplitDotConfig*
     if ((size_t)(2 * kSdRH + 2 * kSdR) * (best + 2 * kSdR) * 512 > 160 * 1024) return false;
     if (!blur4_pack_fits(blur_k, sh.H, sh.W)) return false;
     SplitDotConfig c{};
-    c.sh = sh; c.blur_k = blur_k; c.RW = best;
+    c.sh = sh; c.blur_k = blur_k; c.RW = best; c.act = act;
     const SdGeom g = sd_geom(c);
     // 32-bit LDS / lane offsets; h8 offsets of the staged planes stay in size_t
     if ((long)g.EXs * 512 * 32 > (1L << 31)) return false;
@@ -523,16 +524,16 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     float* xk = reinterpret_cast<float*>(ws + l.xk_off);
     (void)hipMemsetAsync(xmax, 0, (size_t)(s.S * kNumK + s.F) * 4, st);
     (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, false, xk, guard);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard);
     const int HW = s.H * s.W;
     const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
     hipLaunchKernelGGL(sd_absmax_x_kernel, dim3(s.S * xsplit), dim3(256), 0, st, xk, g.NP, s.S, HW, xsplit, xmax, guard);
     const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
-    hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, emax, guard);
+    hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
     hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
                        reinterpret_cast<h8*>(ws + l.xs_off), guard);
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3(4096), dim3(256), 0, st, dy, emax, s.N, s.F, s.H, s.W, g.octs, g.nfb, g.EYs, g.EXs,
-                       drop_col, drop_row, reinterpret_cast<h8*>(ws + l.es_off), guard);
+                       drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
 }
 
 void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table, float* r4, void* workspace, const Guard& guard) {

@@ -26,6 +26,7 @@ FLAG_DENSE_WGRAD_NEVER = 1 << 7    # with FLAG_DENSE_BF16: parameter gradients a
 FLAG_DENSE_WGRAD_ALWAYS = 1 << 8   # with FLAG_DENSE_BF16: dense parameter gradients from one unit per channel on (default: three)
 FLAG_DENSE_SPLIT_F16 = 1 << 9      # gather-sum passes of calls with |mu| <= 2 / 3 / 4 as a densified two-limb f16 MFMA GEMM at fp32 accuracy, whatever G
 FLAG_NO_DENSE_SPLIT = 1 << 10      # never (default: the radii that pay for the plan's unit count)
+FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernels and arithmetic, parameters and their gradients float32
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED = 0, 1, 2
 PASS_FORWARD, PASS_BACKWARD = 1, 2
@@ -165,7 +166,7 @@ class Plan(object):
         else:
             _check(lib.dau_conv_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
         self.N, self.S, self.F, self.G, self.H, self.W = N, S, F, G, H, W
-        self.io_dtype = torch.bfloat16 if int(flags) & FLAG_IO_BF16 else torch.float32
+        self.io_dtype = torch.bfloat16 if int(flags) & FLAG_IO_BF16 else torch.float16 if int(flags) & FLAG_IO_F16 else torch.float32
         info = _Info()
         _check(lib.dau_conv_plan_get_info(self._h, ctypes.byref(info)))
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}

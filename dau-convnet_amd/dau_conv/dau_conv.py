@@ -69,6 +69,10 @@ def _get_plan(x, w, settings):
             # calls whose offsets lie within +-4: the gather-sum passes (and, from three units on, the parameter gradients)
             # as densified bf16 MFMA GEMMs
             flags |= _capi.FLAG_DENSE_BF16
+    elif x.dtype == torch.float16:
+        # float16 activations (autocast, .half()): the members and the arithmetic of the fp32 plan, 16-bit loads and stores;
+        # fp32 parameters.  dense_bf16 does not apply, as for fp32 input
+        flags |= _capi.FLAG_IO_F16
     # the two-limb f16 dense gather-sum (fp32 accuracy): None = the library's choice (the radii that pay for this unit count)
     if settings["dense_split"] is True and not (flags & _capi.FLAG_DENSE_BF16):
         flags |= _capi.FLAG_DENSE_SPLIT_F16
@@ -150,9 +154,16 @@ def _c(t):
     return t.contiguous() if not t.is_contiguous() else t
 
 
+def _f32(t):
+    """A parameter of another floating dtype (model.half(), model.bfloat16()) as float32: differentiable, so autograd hands its
+    gradient back in the parameter's own dtype; float32 tensors pass unchanged."""
+    return t.float() if t.is_floating_point() and t.dtype != torch.float32 else t
+
+
 def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_ALL, **attrs):
-    """DAUConvGrad op -> (grad_input, grad_weights, grad_mu1, grad_mu2, grad_sigma)."""
+    """DAUConvGrad op -> (grad_input, grad_weights, grad_mu1, grad_mu2, grad_sigma).  The parameter gradients are float32."""
     attrs.setdefault("component_border_bound", 0.0)  # the only default that differs (dau_conv_grad_op.cpp:37)
+    weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
     plan = _get_plan(input, weights, st)
     _check_before(plan, st["check_offsets"])
@@ -223,7 +234,9 @@ def _data_parallel_backward(plan, input, grad, weights, mu1, mu2, sigma, need, g
 
 
 def dau_conv(input, weights, mu1, mu2, sigma, **attrs):
-    """DAUConv op: output[n,f] = sum_{s,g} w * bilinear(blur_sigma(input[n,s]), . + (mu2, mu1)); differentiable."""
+    """DAUConv op: output[n,f] = sum_{s,g} w * bilinear(blur_sigma(input[n,s]), . + (mu2, mu1)); differentiable.
+    input (and so output) float32, bfloat16 or float16; the parameters are used as float32 whatever their floating dtype."""
+    weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
     return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
 
@@ -395,6 +408,11 @@ class DAUConv2d(nn.Module):
     activations rounded to bf16, fp32 sums) and, from three units per channel on, their
     parameter gradients as dense cross-correlations on the same cores -- the whole step about 2x faster than the exact
     path at six units, at the bf16 tolerance.
+    Activations may be float32, bfloat16 or float16; the output has the input's dtype.  float16 input (torch.autocast("cuda"),
+    GradScaler training, `model.half()`) runs the kernels and the fp32 arithmetic of a float32 layer with 16-bit loads and stores
+    (DAU_FLAG_IO_F16); the layer casts nothing under autocast.  Parameters of any floating dtype are used as float32 and get
+    their gradients in their own dtype.  The bias is added after the op with ordinary type promotion: a float16 (or bfloat16)
+    output plus a float32 bias gives a float32 result; after `.half()` the bias is float16 and so is the result.
     `process_group` (a torch.distributed group, or True for the default one): batch-sharded data parallelism INSIDE the
     layer's backward -- the raw parameter-gradient sums of the local shard are all-reduced (one flat [4,S,G,F] buffer, RCCL
     over xGMI with backend "nccl") while the input gradient is computed, and the elementwise tail runs on the reduced sums;

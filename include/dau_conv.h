@@ -36,7 +36,7 @@
  *   dau_conv_last_error               DAUException::what (include/dau_conv/util/common.hpp:40-66)
  *
  * Tensor layouts (identical to the reference): activations NCHW contiguous float32 (or,
- * with DAU_FLAG_IO_BF16, bfloat16 storage of x, y, dy, dx -- arithmetic stays fp32);
+ * with DAU_FLAG_IO_BF16 / DAU_FLAG_IO_F16, bfloat16 / binary16 storage of x, y, dy, dx -- arithmetic stays fp32);
  * parameters and their gradients [1,S,G,F] contiguous float32 (f fastest); sigma is a
  * full [1,S,G,F] tensor whose element 0 is used (base_dau_conv_layer.hpp:266-275).
  *
@@ -125,7 +125,7 @@ enum {
                                                split into two binary16 limbs (hi + lo, 22 significant bits; products hi*hi + lo*hi +
                                                hi*lo, fp32 sums, k_dense_split.hip): fp32 accuracy -- the same parity bar as the exact
                                                gather, measured margins in profiles/ -- at 3 * taps / 16 of the fp32 rate per (pixel,
-                                               channel pair) instead of 4 G.  float32 or bfloat16 activations; the call's offsets decide
+                                               channel pair) instead of 4 G.  float32, bfloat16 or float16 activations; the call's offsets decide
                                                on the device which member runs; every other call keeps the exact kernels.
                                                The parameter gradients of fp32, interpolating, 2-D calls within +-4 likewise run as a
                                                two-limb f16 GEMM with the four kinds x four bilinear corners as rows (k_split_dot.hip,
@@ -134,6 +134,13 @@ enum {
                                                the parameter-gradient member where blocks of four units are at least 3/4 full: G = 3, 4, 7, 8, ...).
                                                This flag: all members whatever the unit count.                             */
     DAU_FLAG_NO_DENSE_SPLIT = 1 << 10,      /* never: always the exact fp32 gather and gather-dot (excludes DAU_FLAG_DENSE_SPLIT_F16) */
+    DAU_FLAG_IO_F16 = 1 << 11,              /* x, y, dy, dx are IEEE binary16 arrays (passed through the float* parameters, as with
+                                               DAU_FLAG_IO_BF16); parameters, their gradients, the raw sums of
+                                               dau_conv_backward_param_sums and all arithmetic stay fp32.  The plan runs exactly
+                                               the members, and the arithmetic, of the fp32 plan of the same desc on the widened
+                                               input; results are stored rounded to nearest even (f16 subnormals kept, beyond
+                                               65504 +-inf, a NaN stays a NaN), once per offset-window pass.  Needs the tiled
+                                               kernels; excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and its qualifiers.   */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
