@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -75,58 +76,93 @@ int edge_disabled(int size) {
 
 }  // namespace
 
-// The tiled kernels of one offset bucket.  A plan holds one set per bucket up to the static one (the bucket
-// max_kernel_size allows); which set runs is decided per call from the actual max|mu| (see run_sets below).
-struct BucketSet {
-    int bucket = 0;
-    bool fwd_ok = false, dot_ok = false;
-    TiledConfig tiled_fwd;   // gather-sum y  : S -> F
-    TiledConfig tiled_dx;    // gather-sum dx : F -> S
-    TiledDotConfig tiled_dot;
-    // DAU_FLAG_DENSE_BF16, bucket 4 only: the gather-sum passes run as a densified bf16 implicit GEMM (k_dense_bf16.hip)
-    bool dense_ok = false;
-    // ... and, from three units on (DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS: never / from one unit on), the parameter gradients as
-    // dense correlations on the same matrix cores (k_dense_wgrad.hip)
-    bool wgrad_ok = false;
-    WgradConfig wgrad;
-    DenseConfig dense_fwd, dense_dx;
-    // ... and the same two forms for calls whose offsets lie within +-3 (7 x 7 taps / displacements instead of 9 x 9; the call's
-    // device guard decides between the two: (-1, 3] and (3, 4])
-    bool dense3_ok = false, wgrad3_ok = false;
-    DenseConfig dense3_fwd, dense3_dx;
-    WgradConfig wgrad3;
-    // bucket 4 only: calls whose offsets lie within +-2 / +-3 / +-4 run the gather-sum passes as the two-limb f16 GEMM of that
-    // radius (k_dense_split.hip: fp32 accuracy; index r - 2); the call's device guard decides, everything else takes the exact
-    // kernels.  Which radii a plan holds: those that pay for its unit count (split_pays below), all / none by flag.
-    bool split_ok[3] = {false, false, false};
-    DenseConfig split_fwd[3], split_dx[3];
-    bool any_split() const { return split_ok[0] || split_ok[1] || split_ok[2]; }
-    // bucket 4 only: calls whose offsets lie within +-4 run the parameter gradients as the two-limb f16 GEMM with the bilinear
-    // corners as rows (k_split_dot.hip: fp32 accuracy); the call's device guard (-1, 4] decides, the exact gather-dot takes the rest
-    bool sdot_ok = false;
-    SplitDotConfig sdot;
-    // Batch slabs.  Every pass stages its whole input before it gathers; where that staged copy would exceed the workspace
-    // budget (DAU_WORKSPACE_BUDGET_GB at plan creation, default 12: only the 512 x 512 configurations get there) the pass
-    // runs slab by slab over the batch -- the configs above are made for `slab_*` images, the passes loop -- so that the
-    // workspace holds one slab's staged copy.  Forward and dx are per-image; the parameter sums add up over the slabs.
-    int slab_gather = 0, slab_dot = 0;     // images per slab (the whole batch unless the budget says otherwise)
+// The members of a set: the ways it can run a pass.  The exact tiled kernels exist in every bucket, the others in bucket 4 only.
+// Within a pass kind the order is the order in which pick_candidates enqueues the members that go ahead of the bucket sets.
+enum Member {
+    kTiledGather,                // gather-sum (y and dx): the exact tiled kernels of the set's bucket
+    kSplit2, kSplit3, kSplit4,   // ... the two-limb f16 dense GEMM of radius 2 / 3 / 4 (k_dense_split.hip: fp32 accuracy)
+    kBf16R3, kBf16R4,            // ... the densified bf16 implicit GEMM of radius 3 / 4 (k_dense_bf16.hip; DAU_FLAG_DENSE_BF16)
+    kTiledDot,                   // parameter gradients: the exact tiled gather-dot
+    kSplitDot,                   // ... the two-limb f16 GEMM with the bilinear corners as rows (k_split_dot.hip: fp32 accuracy)
+    kWgradR3, kWgradR4,          // ... the bf16 dense correlations of radius 3 / 4 (k_dense_wgrad.hip; DAU_FLAG_DENSE_BF16)
+    kNumMembers
 };
-constexpr int kBuckets[] = {4, 8, 16, 18, 20, 24, 32};
-constexpr int kNumBuckets = 7;
+enum PassKind { kGatherSum, kGatherDot };
+// the offsets a bucket-4 member covers (its device guard's upper end)
+constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 3, 4, 0, 4, 3, 4};
+constexpr int kFirst[2] = {kTiledGather, kTiledDot}, kEnd[2] = {kTiledDot, kNumMembers};   // the members of a pass kind
+// The radius-4 bf16 member runs in place of its set's exact kernels; every other non-exact member has an arithmetic of its own
+// and goes ahead of the bucket sets under its own guard.
+constexpr int kDense4[2] = {kBf16R4, kWgradR4};
+constexpr bool goes_ahead(int m) { return m != kTiledGather && m != kTiledDot && m != kBf16R4 && m != kWgradR4; }
 
-// the two-limb f16 dense gather-sum, one set of entry points per offset radius (index r - 2)
-struct SplitFns {
+// gather-sum directions, which are also their profile slots: y from x (S -> F) and dx from the error (F -> S)
+enum Dir { kFwd, kDx };
+
+// the dense gather-sum members kSplit2 .. kBf16R4, one set of entry points each (index m - kSplit2)
+struct DenseFns {
     bool (*configure)(int, int, int, int, int, int, int, int, int, DenseConfig*);
     size_t (*workspace_bytes)(const DenseConfig&);
     void (*init)(const DenseConfig&);
     void (*prepare)(hipStream_t, const DenseConfig&, const float*, const float*, bool, const UnitRef*, void*, const Guard&);
     void (*run)(hipStream_t, const DenseConfig&, float*, void*, const Guard&);
 };
-const SplitFns kSplit[3] = {
+const DenseFns kDense[] = {
     {s2::split_gather_configure, s2::split_gather_workspace_bytes, s2::split_gather_init, s2::split_gather_prepare, s2::split_gather_run},
     {s3::split_gather_configure, s3::split_gather_workspace_bytes, s3::split_gather_init, s3::split_gather_prepare, s3::split_gather_run},
     {s4::split_gather_configure, s4::split_gather_workspace_bytes, s4::split_gather_init, s4::split_gather_prepare, s4::split_gather_run},
+    {r3::dense_gather_configure, r3::dense_gather_workspace_bytes, r3::dense_gather_init, r3::dense_gather_prepare, r3::dense_gather_run},
+    {r4::dense_gather_configure, r4::dense_gather_workspace_bytes, r4::dense_gather_init, r4::dense_gather_prepare, r4::dense_gather_run},
 };
+constexpr int kNumDense = kBf16R4 - kSplit2 + 1;
+// the bf16 dense parameter-gradient members kWgradR3, kWgradR4 (index m - kWgradR3)
+struct WgradFns {
+    bool (*configure)(const Shape&, int, bool, WgradConfig*);
+    size_t (*workspace_bytes)(const WgradConfig&);
+    void (*init)(const WgradConfig&);
+    void (*run)(hipStream_t, const WgradConfig&, const float*, const float*, const float*, const UnitRef*, int, int, float*, void*,
+                const Guard&, int);
+};
+const WgradFns kWgrad[] = {
+    {r3::dense_wgrad_configure, r3::dense_wgrad_workspace_bytes, r3::dense_wgrad_init, r3::dense_wgrad_run},
+    {r4::dense_wgrad_configure, r4::dense_wgrad_workspace_bytes, r4::dense_wgrad_init, r4::dense_wgrad_run},
+};
+
+// The kernels of one offset bucket.  A plan holds one set per bucket up to the static one (the bucket max_kernel_size allows);
+// which set and member run is decided per call from the actual max|mu| (pick_candidates below).
+struct BucketSet {
+    int bucket = 0;
+    bool has[kNumMembers] = {};   // the members this set holds
+    TiledConfig tiled[2];         // [Dir]
+    DenseConfig dense[kNumDense][2];
+    TiledDotConfig tiled_dot;
+    SplitDotConfig sdot;
+    WgradConfig wgrad[2];
+    // Batch slabs.  Every pass stages its whole input before it gathers; where that staged copy would exceed the workspace
+    // budget (DAU_WORKSPACE_BUDGET_GB at plan creation, default 12: only the 512 x 512 configurations get there) the pass
+    // runs slab by slab over the batch -- the configs above are made for `slab_*` images, the passes loop -- so that the
+    // workspace holds one slab's staged copy.  Forward and dx are per-image; the parameter sums add up over the slabs.
+    // Only the exact kernels and the dense gather-sum members run in slabs.
+    int slab_gather = 0, slab_dot = 0;     // images per slab (the whole batch unless the budget says otherwise)
+};
+constexpr int kBuckets[] = {4, 8, 16, 18, 20, 24, 32};
+constexpr int kNumBuckets = 7;
+
+// workspace a set's gather-sum members need in one direction, and its parameter-gradient members
+size_t gather_bytes(const BucketSet& bs, int dir) {
+    size_t need = bs.has[kTiledGather] ? tiled_gather_workspace_bytes(bs.tiled[dir]) : 0;
+    for (int m = kSplit2; m <= kBf16R4; ++m)
+        if (bs.has[m]) need = std::max(need, kDense[m - kSplit2].workspace_bytes(bs.dense[m - kSplit2][dir]));
+    return need;
+}
+size_t dot_bytes(const BucketSet& bs) {
+    size_t need = bs.has[kTiledDot] ? tiled_dot_workspace_bytes(bs.tiled_dot) : 0;
+    if (bs.has[kSplitDot]) need = std::max(need, split_dot_workspace_bytes(bs.sdot));
+    for (int m = kWgradR3; m <= kWgradR4; ++m)
+        if (bs.has[m]) need = std::max(need, kWgrad[m - kWgradR3].workspace_bytes(bs.wgrad[m - kWgradR3]));
+    return need;
+}
+
 // Does the dense form of radius r pay against the exact gather?  MFMA work per pass in fp32-rate MAC units: the dense GEMM runs
 // (2r+1)^2 taps x 3 limb products at 16x the fp32 rate over the PADDED tile (8-row / 8-column blocks, 128 output channels, 16 input
 // channels) plus its staging, at ~55 % of the f16 roof; the exact gather 4 MACs per live unit at ~60 % of the fp32 roof on maps
@@ -161,6 +197,8 @@ struct dau_conv_plan {
     mutable std::mutex attrs_mutex;
     const BucketSet& top() const { return sets[nsets - 1]; }
     long units() const { return (long)sh.S * sh.G * sh.F; }
+    // bytes per activation element: float32, or bfloat16 / binary16 behind the float* of the ABI
+    size_t esize() const { return (d.flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4; }
     // optional benchmark timing (dau_conv_profile_begin/_end); mutable because the passes take a const plan
     mutable bool profiling = false;
     mutable std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events[DAU_PROFILE_SLOTS];
@@ -194,80 +232,78 @@ struct ProfScope {
     }
 };
 
-// The bucket sets one call enqueues.  Without a hint (first call, dynamic selection off) it is the static set, unguarded.
-// With a hint -- max|mu| of the most recent completed call, read from pinned host memory without a sync -- it is the
-// smallest set that covers the hint, guarded by (-1, R_hint], followed by the static set guarded by (R_hint, inf): the
-// device decides between them from the max|mu| of THIS call, so results never depend on the hint.  This replaces the
-// reference's blocking amax + D2H copy per call (dau_conv_op.cpp:223-253) and makes a layer with a large
-// max_kernel_size but small offsets run the small-offset kernels (the reference's tests rely on that,
-// dau_conv_test.py:433,436).
+// The candidates one call enqueues: a set, the member of it that runs, and the device guard under which it runs.  Without a
+// hint (first call, dynamic selection off) it is the static set, unguarded.  With a hint -- max|mu| of the most recent completed
+// call, read from pinned host memory without a sync -- it is the smallest set that covers the hint, guarded by (-1, R_hint],
+// followed by the static set guarded by (R_hint, inf): the device decides between them from the max|mu| of THIS call, so
+// results never depend on the hint.  This replaces the reference's blocking amax + D2H copy per call (dau_conv_op.cpp:223-253)
+// and makes a layer with a large max_kernel_size but small offsets run the small-offset kernels (the reference's tests rely on
+// that, dau_conv_test.py:433,436).
 struct Candidate {
     const BucketSet* set;
     Guard guard;
-    bool r3 = false;          // the set's radius-3 dense bf16 member (sets[0] only)
-    int split_r = 0;          // 2, 3, 4: the set's two-limb f16 dense member of that radius (sets[0], gather-sum passes only)
-    bool sdot = false;        // the set's two-limb f16 gather-dot member (sets[0], parameter-gradient pass only)
+    int member;   // Member
 };
 
 // dau_conv_last_status has just reported the whole mirror: forget it, sticky record included.
 void clear_host_status(const dau_conv_plan* p) {
     if (!p->host_status) return;
-    volatile unsigned* h = reinterpret_cast<volatile unsigned*>(p->host_status);
-    h[2] = 0u; h[1] = 0u; h[0] = 0u; h[4] = 0u; h[5] = 0u;
+    volatile HostStatus* h = p->host_status;
+    h->valid = 0u; h->nan_seen = 0u; h->max_abs_mu_bits = 0u; h->bad_max_abs_mu_bits = 0u; h->bad_nan_seen = 0u;
 }
 // dau_conv_check_status has just reported the status of ONE workspace's call: forget the "most recent call" part, and of the sticky
 // record only what is this very report (the same out-of-range maximum, the NaN flag if this call had one) -- it may also hold the
 // not-yet-reported error of another layer or stream that shares the plan, which dau_conv_last_status must still see.
 void clear_reported_status(const dau_conv_plan* p, unsigned max_bits, bool nan_seen) {
     if (!p->host_status) return;
-    volatile unsigned* h = reinterpret_cast<volatile unsigned*>(p->host_status);
-    h[2] = 0u; h[1] = 0u; h[0] = 0u;
-    if (h[4] == max_bits) h[4] = 0u;
-    if (nan_seen) h[5] = 0u;
+    volatile HostStatus* h = p->host_status;
+    h->valid = 0u; h->nan_seen = 0u; h->max_abs_mu_bits = 0u;
+    if (h->bad_max_abs_mu_bits == max_bits) h->bad_max_abs_mu_bits = 0u;
+    if (nan_seen) h->bad_nan_seen = 0u;
 }
 
-// pass_kind: 0 = gather-sum (needs fwd_ok), 1 = gather-dot (needs dot_ok)
-// A plan with DAU_FLAG_DENSE_BF16 has one member whose ARITHMETIC differs (bucket 4: bf16 products): that member is enqueued,
-// guarded by (-1, 4], on every call, hint or no hint, so that which arithmetic a call gets depends on its own offsets only.
-// The dense forms exist for |mu| <= 3 as well (49 taps instead of 81): that member goes first, guarded by (-1, 3].
+// the error a reported status carries (DAU_OK: none)
+int status_error(const dau_conv_plan* p, float mx, bool nan_seen) {
+    if (nan_seen) return fail(DAU_FAILED_PRECONDITION, "DAUConvOp ERROR: got NaN value in offset (mu1,mu2) variable");
+    if (mx > (float)p->bucket)
+        return fail(DAU_INVALID_ARGUMENT,
+                    "DAUConvOp ERROR: actual offsets (%.3f) larger than what max_kernel_size=%d allows (setup max_kernel_size "
+                    "and dau_unit_border_bound correctly to avoid this)",
+                    mx, p->d.max_kernel_size);
+    return DAU_OK;
+}
+
+// The members whose ARITHMETIC differs (split, bf16-dense) go first, smallest radius first, on every call, hint or no hint, so that
+// which arithmetic a call gets depends on its own offsets only.  A set that holds the radius-4 bf16 member runs it in place of
+// its exact kernels: as the static set of a one-bucket plan, as the hinted set, or guarded by (lo, 4] ahead of them.
 constexpr int kMaxCandidates = 6;
-int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int pass_kind, Candidate out[kMaxCandidates]) {
+int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
-    out[0] = Candidate{top, Guard{nullptr, 0.0f, 0.0f}};
+    const BucketSet* s0 = &p->sets[0];
+    auto member_of = [&](const BucketSet* b) { return b->has[kDense4[kind]] ? kDense4[kind] : kFirst[kind]; };
+    out[0] = Candidate{top, Guard{nullptr, 0.0f, 0.0f}, member_of(top)};
     if (!p->dynamic) return 1;
-    const BucketSet& s0 = p->sets[0];
-    const bool d3 = pass_kind == 0 ? s0.dense3_ok : s0.wgrad3_ok;
-    const bool split = pass_kind == 0 && s0.any_split();
-    const bool sdot = pass_kind == 1 && s0.sdot_ok;
-    if (p->nsets < 2 && !d3 && !split && !sdot) return 1;
-    const BucketSet* dense = (pass_kind == 0 ? s0.dense_ok : s0.wgrad_ok) ? &s0 : nullptr;
     const BucketSet* hinted = nullptr;
     if (p->host_status && p->nsets >= 2) {
-        const volatile unsigned* h = reinterpret_cast<const volatile unsigned*>(p->host_status);
+        const volatile HostStatus* h = p->host_status;
         float mx = -1.0f;
-        if (h[2] == 1u && h[1] == 0u) {
-            const unsigned bits = h[0];
+        if (h->valid == 1u && h->nan_seen == 0u) {
+            const unsigned bits = h->max_abs_mu_bits;
             std::memcpy(&mx, &bits, sizeof(float));
         }
         if (mx >= 0.0f)
-            for (int i = 0; i + 1 < p->nsets && !hinted; ++i) {
-                const BucketSet& b = p->sets[i];
-                if (mx <= (float)b.bucket && (pass_kind == 0 ? b.fwd_ok : b.dot_ok)) hinted = &b;
-            }
+            for (int i = 0; i + 1 < p->nsets && !hinted; ++i)
+                if (mx <= (float)p->sets[i].bucket && p->sets[i].has[kFirst[kind]]) hinted = &p->sets[i];
     }
     int n = 0;
     float lo = -1.0f;
-    // the members with an arithmetic of their own are candidates of EVERY call (hint or no hint), smallest radius first: which
-    // arithmetic a call gets depends on its own offsets only
-    if (split)
-        for (int r = 2; r <= 4; ++r)
-            if (s0.split_ok[r - 2]) { out[n] = Candidate{&s0, Guard{dev_status, lo, (float)r}}; out[n++].split_r = r; lo = (float)r; }
-    if (sdot) { out[n] = Candidate{&s0, Guard{dev_status, lo, 4.0f}}; out[n++].sdot = true; lo = 4.0f; }
-    if (d3) { out[n] = Candidate{&s0, Guard{dev_status, lo, 3.0f}}; out[n++].r3 = true; lo = 3.0f; }
-    if (dense && hinted != dense && dense != top) { out[n++] = Candidate{dense, Guard{dev_status, lo, (float)dense->bucket}}; lo = (float)dense->bucket; }
-    if (hinted && lo < (float)hinted->bucket) { out[n++] = Candidate{hinted, Guard{dev_status, lo, (float)hinted->bucket}}; lo = (float)hinted->bucket; }
+    auto add = [&](const BucketSet* b, int member, float hi) { out[n++] = Candidate{b, Guard{dev_status, lo, hi}, member}; lo = hi; };
+    for (int m = kFirst[kind]; m < kEnd[kind]; ++m)
+        if (goes_ahead(m) && s0->has[m]) add(s0, m, (float)kRadius[m]);
+    if (s0->has[kDense4[kind]] && hinted != s0 && s0 != top) add(s0, kDense4[kind], (float)s0->bucket);
+    if (hinted && lo < (float)hinted->bucket) add(hinted, member_of(hinted), (float)hinted->bucket);
     if (n == 0) return 1;                                    // no hint, nothing dense: the static set, unguarded
-    out[n++] = Candidate{top, Guard{dev_status, lo, INFINITY}};
+    add(top, member_of(top), INFINITY);
     return n;
 }
 
@@ -283,30 +319,41 @@ int ensure_attrs(const dau_conv_plan* p) {
     if (p->attrs_devices.load(std::memory_order_relaxed) & bit) return DAU_OK;
     (void)hipGetLastError();
     for (int i = 0; i < p->nsets; ++i) {
-        if (p->sets[i].fwd_ok) { tiled_gather_init(p->sets[i].tiled_fwd); tiled_gather_init(p->sets[i].tiled_dx); }
-        if (p->sets[i].dot_ok) tiled_dot_init(p->sets[i].tiled_dot);
-        if (p->sets[i].dense_ok) { r4::dense_gather_init(p->sets[i].dense_fwd); r4::dense_gather_init(p->sets[i].dense_dx); }
-        if (p->sets[i].wgrad_ok) r4::dense_wgrad_init(p->sets[i].wgrad);
-        if (p->sets[i].dense3_ok) { r3::dense_gather_init(p->sets[i].dense3_fwd); r3::dense_gather_init(p->sets[i].dense3_dx); }
-        if (p->sets[i].wgrad3_ok) r3::dense_wgrad_init(p->sets[i].wgrad3);
-        if (p->sets[i].sdot_ok) split_dot_init(p->sets[i].sdot);
-        for (int r = 0; r < 3; ++r)
-            if (p->sets[i].split_ok[r]) { kSplit[r].init(p->sets[i].split_fwd[r]); kSplit[r].init(p->sets[i].split_dx[r]); }
+        const BucketSet& bs = p->sets[i];
+        for (int m = 0; m < kNumMembers; ++m) {
+            if (!bs.has[m]) continue;
+            if (m == kTiledGather) for (int dir : {kFwd, kDx}) tiled_gather_init(bs.tiled[dir]);
+            else if (m <= kBf16R4) for (int dir : {kFwd, kDx}) kDense[m - kSplit2].init(bs.dense[m - kSplit2][dir]);
+            else if (m == kTiledDot) tiled_dot_init(bs.tiled_dot);
+            else if (m == kSplitDot) split_dot_init(bs.sdot);
+            else kWgrad[m - kWgradR3].init(bs.wgrad[m - kWgradR3]);
+        }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
-            return fail(DAU_INTERNAL, "raising the dynamic-LDS limit of the bucket-%d kernels failed: %s", p->sets[i].bucket,
+            return fail(DAU_INTERNAL, "raising the dynamic-LDS limit of the bucket-%d kernels failed: %s", bs.bucket,
                         hipGetErrorString(e));
     }
     p->attrs_devices.fetch_or(bit, std::memory_order_release);
     return DAU_OK;
 }
 
+// workspace of the tiled passes: the largest need of any set (the candidates run one after the other in the same memory)
+size_t tiled_gather_bytes(const dau_conv_plan* p, int dir) {
+    size_t need = 0;
+    for (int i = 0; i < p->nsets; ++i) need = std::max(need, gather_bytes(p->sets[i], dir));
+    return need;
+}
+size_t tiled_dot_bytes(const dau_conv_plan* p) {
+    size_t need = 0;
+    for (int i = 0; i < p->nsets; ++i) need = std::max(need, dot_bytes(p->sets[i]));
+    return need;
+}
+
 struct FwdWs {
     Status* status;
     float* filters;
     UnitRef* table;
-    float* xb;          // direct: blurred input, NCHW
-    void* tiled;        // tiled: staged planes + packed units
+    void* gather;       // tiled: staged planes + packed units; direct: blurred input, NCHW
     size_t bytes;
 };
 
@@ -316,19 +363,8 @@ FwdWs carve_forward(const dau_conv_plan* p, void* ws) {
     w.status = c.take<Status>(1);
     w.filters = c.take<float>(kFilterFloats);
     w.table = c.take<UnitRef>(p->units());
-    if (p->algo_fwd == DAU_ALGO_TILED) {
-        size_t need = 0;
-        for (int i = 0; i < p->nsets; ++i) {
-            if (p->sets[i].fwd_ok) need = std::max(need, tiled_gather_workspace_bytes(p->sets[i].tiled_fwd));
-            if (p->sets[i].dense_ok) need = std::max(need, r4::dense_gather_workspace_bytes(p->sets[i].dense_fwd));
-            if (p->sets[i].dense3_ok) need = std::max(need, r3::dense_gather_workspace_bytes(p->sets[i].dense3_fwd));
-            for (int r = 0; r < 3; ++r)
-                if (p->sets[i].split_ok[r]) need = std::max(need, kSplit[r].workspace_bytes(p->sets[i].split_fwd[r]));
-        }
-        w.tiled = c.take<char>(need);
-    } else {
-        w.xb = c.take<float>((size_t)p->sh.N * p->sh.S * p->sh.H * p->sh.W);
-    }
+    if (p->algo_fwd == DAU_ALGO_TILED) w.gather = c.take<char>(tiled_gather_bytes(p, kFwd));
+    else w.gather = c.take<float>((size_t)p->sh.N * p->sh.S * p->sh.H * p->sh.W);
     w.bytes = c.off;
     return w;
 }
@@ -340,8 +376,7 @@ struct BwdWs {
     UnitRef* table_t;      // [F][G][S], negated offsets, times w  (input gradient)
     float* r4;             // [4][S][G][F]
     float* xk4;            // direct: [N*S][4][H][W]
-    float* eb;             // direct: blurred error, NCHW
-    void* tiled_dx;
+    void* gather_dx;       // tiled: staged planes + packed units; direct: blurred error, NCHW
     void* tiled_dot;
     size_t bytes;
 };
@@ -355,34 +390,54 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
     w.table_bare = c.take<UnitRef>(p->units());
     w.table_t = c.take<UnitRef>(p->units());
     w.r4 = c.take<float>(kNumK * p->units());
-    if (p->algo_bwd == DAU_ALGO_TILED) {
-        size_t need = 0;
-        for (int i = 0; i < p->nsets; ++i)
-            if (p->sets[i].dot_ok) need = std::max(need, tiled_dot_workspace_bytes(p->sets[i].tiled_dot));
-        for (int i = 0; i < p->nsets; ++i) {
-            if (p->sets[i].wgrad_ok) need = std::max(need, r4::dense_wgrad_workspace_bytes(p->sets[i].wgrad));
-            if (p->sets[i].wgrad3_ok) need = std::max(need, r3::dense_wgrad_workspace_bytes(p->sets[i].wgrad3));
-            if (p->sets[i].sdot_ok) need = std::max(need, split_dot_workspace_bytes(p->sets[i].sdot));
-        }
-        w.tiled_dot = c.take<char>(need);
-    } else {
-        w.xk4 = c.take<float>((size_t)kNumK * s.N * s.S * s.H * s.W);
-    }
-    if (p->algo_fwd == DAU_ALGO_TILED) {
-        size_t need = 0;
-        for (int i = 0; i < p->nsets; ++i) {
-            if (p->sets[i].fwd_ok) need = std::max(need, tiled_gather_workspace_bytes(p->sets[i].tiled_dx));
-            if (p->sets[i].dense_ok) need = std::max(need, r4::dense_gather_workspace_bytes(p->sets[i].dense_dx));
-            if (p->sets[i].dense3_ok) need = std::max(need, r3::dense_gather_workspace_bytes(p->sets[i].dense3_dx));
-            for (int r = 0; r < 3; ++r)
-                if (p->sets[i].split_ok[r]) need = std::max(need, kSplit[r].workspace_bytes(p->sets[i].split_dx[r]));
-        }
-        w.tiled_dx = c.take<char>(need);
-    } else {
-        w.eb = c.take<float>((size_t)s.N * s.F * s.H * s.W);
-    }
+    if (p->algo_bwd == DAU_ALGO_TILED) w.tiled_dot = c.take<char>(tiled_dot_bytes(p));
+    else w.xk4 = c.take<float>((size_t)kNumK * s.N * s.S * s.H * s.W);
+    if (p->algo_fwd == DAU_ALGO_TILED) w.gather_dx = c.take<char>(tiled_gather_bytes(p, kDx));
+    else w.gather_dx = c.take<float>((size_t)s.N * s.F * s.H * s.W);
     w.bytes = c.off;
     return w;
+}
+
+// One gather-sum pass: y from x (kFwd: S -> F, unit table [S][G][F]) or dx from the error (kDx: F -> S, mirrored Gaussian, table
+// [F][G][S] with negated offsets).  `ws`: the tiled workspace, or the direct path's blurred copy.
+void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float* in, float* out, const float* filters,
+                    const UnitRef* table, const Status* status, void* ws) {
+    const Shape& s = p->sh;
+    const int cin = dir == kFwd ? s.S : s.F, cout = dir == kFwd ? s.F : s.S;
+    const bool mirrored = dir == kDx;
+    if (p->profiling) ++p->prof_passes[dir];
+    if (p->algo_fwd != DAU_ALGO_TILED) {
+        launch_blur_direct(st, in, (long)s.N * cin, s.H, s.W, filters + (mirrored ? 5 : 0) * kFilterPlane, 1, p->blur_k,
+                           static_cast<float*>(ws));
+        ProfScope prof(p, dir, st);
+        launch_gather_sum_direct(st, static_cast<float*>(ws), table, s.N, cin, cout, s.G, s.H, s.W, out);
+        return;
+    }
+    Candidate cand[kMaxCandidates];
+    const int ncand = pick_candidates(p, status, kGatherSum, cand);
+    for (int ci = 0; ci < ncand; ++ci) {
+        const BucketSet& bs = *cand[ci].set;
+        const Guard& g = cand[ci].guard;
+        const int m = cand[ci].member;
+        for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {                 // one slab unless the staged copy exceeds the budget
+            const float* ins = slab_ptr(in, (size_t)n0 * cin * s.H * s.W, p->esize());
+            float* outs = slab_ptr(out, (size_t)n0 * cout * s.H * s.W, p->esize());
+            if (m == kTiledGather) {
+                const TiledConfig& cfg = bs.tiled[dir];
+                for (int window = 0; window < tiled_gather_windows(cfg); ++window) {   // one pass unless the bucket is 32
+                    tiled_gather_prepare(st, cfg, ins, filters, mirrored, table, ws, window, g);
+                    ProfScope prof(p, dir, st);
+                    tiled_gather_run(st, cfg, outs, ws, window > 0, g);
+                }
+            } else {                                                       // a dense member: one GEMM per slab
+                const DenseFns& fn = kDense[m - kSplit2];
+                const DenseConfig& cfg = bs.dense[m - kSplit2][dir];
+                fn.prepare(st, cfg, ins, filters, mirrored, table, ws, g);
+                ProfScope prof(p, dir, st);
+                fn.run(st, cfg, outs, ws, g);
+            }
+        }
+    }
 }
 
 }  // namespace
@@ -431,63 +486,66 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         return fail(DAU_INVALID_ARGUMENT, "sigma %.3f needs a %dx%d prefilter; at most %dx%d is supported", desc->sigma_hint,
                     blur_k, blur_k, kMaxBlurSupport, kMaxBlurSupport);
     if (desc->algo < DAU_ALGO_AUTO || desc->algo > DAU_ALGO_TILED) return fail(DAU_INVALID_ARGUMENT, "unknown algo");
+    const int flags = desc->flags;
+    const bool bf16 = (flags & DAU_FLAG_IO_BF16) != 0;
+    const bool f16 = (flags & DAU_FLAG_IO_F16) != 0;
+    if (f16 && (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_F16 excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
+    if ((flags & DAU_FLAG_DENSE_BF16) && !bf16)
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 needs DAU_FLAG_IO_BF16 (it is the bf16 layer's gather-sum)");
+    if ((flags & DAU_FLAG_DENSE_SPLIT_F16) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
+    if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
+        (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
 
-    dau_conv_plan* p = new (std::nothrow) dau_conv_plan();
+    std::unique_ptr<dau_conv_plan> p(new (std::nothrow) dau_conv_plan());
     if (!p) return fail(DAU_INTERNAL, "out of host memory");
     p->d = *desc;
     p->sh = Shape{desc->batch, desc->in_channels, desc->out_channels, desc->units_per_channel, desc->height, desc->width};
     p->bucket = bucket;
     p->blur_k = blur_k;
-    const bool ut = desc->flags & DAU_FLAG_UNIT_TESTING;
+    const bool ut = flags & DAU_FLAG_UNIT_TESTING;
     p->drop_col = ut ? edge_disabled(desc->width) : 0;
     p->drop_row = ut ? edge_disabled(desc->height) : 0;
 
     const Shape& s = p->sh;
-    const bool bf16 = (desc->flags & DAU_FLAG_IO_BF16) != 0;
-    const bool f16 = (desc->flags & DAU_FLAG_IO_F16) != 0;
     // storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does
     // (the staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ
     const int act = f16 ? kActF16 : bf16 ? kActBF16 : kActF32;
     const char* budget_env = getenv("DAU_WORKSPACE_BUDGET_GB");
     const double budget_bytes = (budget_env ? atof(budget_env) : 12.0) * 1e9;
+    const bool want_dense = (flags & DAU_FLAG_DENSE_BF16) && desc->algo != DAU_ALGO_DIRECT;
+    const bool split_forced = (flags & DAU_FLAG_DENSE_SPLIT_F16) != 0;
+    const bool split_allowed = !(flags & (DAU_FLAG_NO_DENSE_SPLIT | DAU_FLAG_DENSE_BF16)) && desc->algo != DAU_ALGO_DIRECT;
+    const int g_live = s.G - desc->number_units_ignore;
     for (int b : kBuckets) {
         if (b > bucket) break;
         BucketSet& bs = p->sets[p->nsets++];
         bs.bucket = b;
-        // slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
-        const bool want_dense = (desc->flags & DAU_FLAG_DENSE_BF16) && desc->algo != DAU_ALGO_DIRECT;
-        const bool split_forced = (desc->flags & DAU_FLAG_DENSE_SPLIT_F16) != 0;
-        const bool split_allowed = !(desc->flags & (DAU_FLAG_NO_DENSE_SPLIT | DAU_FLAG_DENSE_BF16)) && desc->algo != DAU_ALGO_DIRECT &&
-                                   DAU_TUNE_INT("DAU_DENSE_SPLIT", 1) != 0;
         auto configure_gather = [&](int n) {
-            bs.fwd_ok = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, act, &bs.tiled_fwd) &&
-                        tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, act, &bs.tiled_dx);
-            bs.dense_ok = want_dense && bs.fwd_ok &&
-                          r4::dense_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, bf16, &bs.dense_fwd) &&
-                          r4::dense_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, bf16, &bs.dense_dx);
-            bs.dense3_ok = bs.dense_ok && b == 4 && DAU_TUNE_INT("DAU_DENSE_R3", 1) != 0 &&
-                           r3::dense_gather_configure(n, s.S, s.F, s.G, s.H, s.W, 3, blur_k, bf16, &bs.dense3_fwd) &&
-                           r3::dense_gather_configure(n, s.F, s.S, s.G, s.H, s.W, 3, blur_k, bf16, &bs.dense3_dx);
-            size_t need = 0;
-            if (bs.fwd_ok) need = std::max(tiled_gather_workspace_bytes(bs.tiled_fwd), tiled_gather_workspace_bytes(bs.tiled_dx));
-            for (int r = 2; r <= 4; ++r) {
-                bool& ok = bs.split_ok[r - 2];
-                const int g_live = s.G - desc->number_units_ignore;
-                ok = split_allowed && bs.fwd_ok && b == 4 &&
-                     (split_forced || (split_pays(r, s.S, s.F, g_live, s.H, s.W) && split_pays(r, s.F, s.S, g_live, s.H, s.W))) &&
-                     kSplit[r - 2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &bs.split_fwd[r - 2]) &&
-                     kSplit[r - 2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &bs.split_dx[r - 2]);
-                if (ok) need = std::max(need, std::max(kSplit[r - 2].workspace_bytes(bs.split_fwd[r - 2]), kSplit[r - 2].workspace_bytes(bs.split_dx[r - 2])));
+            bs.has[kTiledGather] = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kFwd]) &&
+                                   tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kDx]);
+            // the dense members, bucket 4 only; downwards, as the bf16 radius-3 member needs the radius-4 one
+            for (int m = kBf16R4; m >= kSplit2; --m) {
+                const int r = kRadius[m];
+                bool want = b == 4 && bs.has[kTiledGather];
+                if (m == kBf16R4) want = want && want_dense;
+                else if (m == kBf16R3) want = want && bs.has[kBf16R4];
+                else want = want && split_allowed && (split_forced || (split_pays(r, s.S, s.F, g_live, s.H, s.W) &&
+                                                                       split_pays(r, s.F, s.S, g_live, s.H, s.W)));
+                DenseConfig* cfg = bs.dense[m - kSplit2];
+                bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
+                            kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
             }
-            if (bs.dense_ok) need = std::max(need, std::max(r4::dense_gather_workspace_bytes(bs.dense_fwd), r4::dense_gather_workspace_bytes(bs.dense_dx)));
-            if (bs.dense3_ok) need = std::max(need, std::max(r3::dense_gather_workspace_bytes(bs.dense3_fwd), r3::dense_gather_workspace_bytes(bs.dense3_dx)));
-            return need;
+            return std::max(gather_bytes(bs, kFwd), gather_bytes(bs, kDx));
         };
         auto configure_dot = [&](int n) {
             Shape sn = s; sn.N = n;
-            bs.dot_ok = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
-            return bs.dot_ok ? tiled_dot_workspace_bytes(bs.tiled_dot) : (size_t)0;
+            bs.has[kTiledDot] = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
+            return dot_bytes(bs);
         };
+        // slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
         auto pick_slab = [&](auto&& configure) {
             int chosen = s.N;
             for (int n = s.N; n >= 2; --n) {
@@ -500,60 +558,43 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         };
         bs.slab_gather = pick_slab(configure_gather);
         bs.slab_dot = pick_slab(configure_dot);
+        const bool whole_dot = b == 4 && bs.has[kTiledDot] && bs.slab_dot == s.N;
         {
-            // dense parameter gradients: the bf16 layer's bucket-4 set, whole batch in one slab, three or more units (its cost
+            // dense parameter gradients: the bf16-dense layer's bucket-4 set, whole batch in one slab, three or more units (its cost
             // does not depend on the unit count: 15.3 ms at the north-star size against 16.0 ms for the exact gather-dot of a
-            // four-unit block, 9.7 ms of two units); DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS: never / from one unit on
-            const int min_units = (desc->flags & DAU_FLAG_DENSE_WGRAD_NEVER) ? 1 << 30 : (desc->flags & DAU_FLAG_DENSE_WGRAD_ALWAYS) ? 1 : 3;
-            bs.wgrad_ok = want_dense && bf16 && b == 4 && bs.dense_ok && bs.dot_ok && bs.slab_dot == s.N && s.G >= min_units &&
-                          r4::dense_wgrad_configure(s, blur_k, bf16, &bs.wgrad) &&
-                          (double)r4::dense_wgrad_workspace_bytes(bs.wgrad) <= budget_bytes;
-            bs.wgrad3_ok = bs.wgrad_ok && bs.dense3_ok && r3::dense_wgrad_configure(s, blur_k, bf16, &bs.wgrad3) &&
-                           (double)r3::dense_wgrad_workspace_bytes(bs.wgrad3) <= budget_bytes;
+            // four-unit block, 9.7 ms of two units); DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS: never / from one unit on.  The radius-3
+            // form where the radius-4 one and the radius-3 gather-sum are there.
+            const int min_units = (flags & DAU_FLAG_DENSE_WGRAD_NEVER) ? 1 << 30 : (flags & DAU_FLAG_DENSE_WGRAD_ALWAYS) ? 1 : 3;
+            for (int m = kWgradR4; m >= kWgradR3; --m) {
+                const WgradFns& fn = kWgrad[m - kWgradR3];
+                WgradConfig& cfg = bs.wgrad[m - kWgradR3];
+                const bool want = m == kWgradR4 ? whole_dot && bs.has[kBf16R4] && s.G >= min_units : bs.has[kWgradR4] && bs.has[kBf16R3];
+                bs.has[m] = want && fn.configure(s, blur_k, bf16, &cfg) && (double)fn.workspace_bytes(cfg) <= budget_bytes;
+            }
         }
         {
             // two-limb f16 gather-dot: fp32 and f16 layers, bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default
             // where the blocks of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with
             // DAU_FLAG_DENSE_SPLIT_F16 whatever the unit count
-            const bool interp2d = (desc->flags & DAU_FLAG_USE_INTERPOLATION) && !(desc->flags & DAU_FLAG_SINGLE_DIM_KERNEL);
+            const bool interp2d = (flags & DAU_FLAG_USE_INTERPOLATION) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL);
             const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
-            bs.sdot_ok = split_allowed && !bf16 && b == 4 && interp2d && bs.dot_ok && bs.slab_dot == s.N && (split_forced || fill) &&
-                         split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
+            bs.has[kSplitDot] = split_allowed && !bf16 && whole_dot && interp2d && (split_forced || fill) &&
+                                split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
         }
     }
-    if (f16 && (desc->flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS))) {
-        delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_F16 excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
-    }
-    if ((desc->flags & DAU_FLAG_DENSE_BF16) && !bf16) {
-        delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 needs DAU_FLAG_IO_BF16 (it is the bf16 layer's gather-sum)");
-    }
-    if ((desc->flags & DAU_FLAG_DENSE_SPLIT_F16) && (desc->flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT))) {
-        delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
-    }
-    if ((desc->flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
-        (!(desc->flags & DAU_FLAG_DENSE_BF16) || (desc->flags & DAU_FLAG_DENSE_WGRAD_NEVER && desc->flags & DAU_FLAG_DENSE_WGRAD_ALWAYS))) {
-        delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
-    }
-    const bool fwd_ok = p->top().fwd_ok, dot_ok = p->top().dot_ok;
-    if ((bf16 || f16) && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok))) {
-        delete p;
+    const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
+    if ((bf16 || f16) && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
         return fail(DAU_INVALID_ARGUMENT, "%s needs the tiled kernels, which do not support this shape / algo",
                     f16 ? "DAU_FLAG_IO_F16" : "DAU_FLAG_IO_BF16");
-    }
-    if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) {
-        delete p;
-        return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
-    }
+    if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
     p->algo_fwd = (desc->algo != DAU_ALGO_DIRECT && fwd_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
     p->algo_bwd = (desc->algo != DAU_ALGO_DIRECT && dot_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
-    // dynamic bucket selection: tiled kernels, more than one bucket (or the two radii of the dense forms), not switched off (DAU_FLAG_STATIC_BUCKET; tuning build:
-    // DAU_DYNAMIC_BUCKET=0 in the environment at plan creation).  The pinned status mirror needs a device; without one
-    // (header-only checks on a CPU box) the plan simply has no hint.
-    p->dynamic = (p->nsets > 1 || p->sets[0].dense3_ok || p->sets[0].any_split() || p->sets[0].sdot_ok) && !(desc->flags & DAU_FLAG_STATIC_BUCKET) && DAU_TUNE_INT("DAU_DYNAMIC_BUCKET", 1) != 0 &&
+    // dynamic selection: tiled kernels, more than one bucket or a member that goes ahead of the sets, not switched off
+    // (DAU_FLAG_STATIC_BUCKET).  The pinned status mirror needs a device; without one (header-only checks on a CPU box) the plan
+    // simply has no hint.
+    bool ahead = false;
+    for (int m = 0; m < kNumMembers; ++m) ahead = ahead || (goes_ahead(m) && p->sets[0].has[m]);
+    p->dynamic = (p->nsets > 1 || ahead) && !(flags & DAU_FLAG_STATIC_BUCKET) &&
                  (p->algo_fwd == DAU_ALGO_TILED || p->algo_bwd == DAU_ALGO_TILED);
     void* hs = nullptr;
     // portable + mapped: a plan may be used on any device, and every device's prepare_units_kernel writes the mirror
@@ -563,7 +604,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     } else {
         (void)hipGetLastError();   // no device: not an error of this call
     }
-    *plan_out = p;
+    *plan_out = p.release();
     return DAU_OK;
 }
 
@@ -613,24 +654,27 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
     info->algo_backward = plan->algo_bwd;
     info->drop_last_col = plan->drop_col;
     info->drop_last_row = plan->drop_row;
-    info->gather_patch = plan->algo_fwd == DAU_ALGO_TILED ? plan->top().tiled_fwd.tiles_x * plan->top().tiled_fwd.tile_w : 0;
-    info->gather_stack = plan->algo_fwd == DAU_ALGO_TILED ? plan->top().tiled_fwd.stack : 0;
-    info->dot_windows = plan->algo_bwd == DAU_ALGO_TILED ? plan->top().tiled_dot.windows : 0;
-    info->gather_windows = plan->algo_fwd == DAU_ALGO_TILED ? plan->top().tiled_fwd.windows : 0;
+    const BucketSet& top = plan->top();
+    const bool* s0 = plan->sets[0].has;
+    const bool tiled_fwd = plan->algo_fwd == DAU_ALGO_TILED;
+    info->gather_patch = tiled_fwd ? top.tiled[kFwd].tiles_x * top.tiled[kFwd].tile_w : 0;
+    info->gather_stack = tiled_fwd ? top.tiled[kFwd].stack : 0;
+    info->dot_windows = plan->algo_bwd == DAU_ALGO_TILED ? top.tiled_dot.windows : 0;
+    info->gather_windows = tiled_fwd ? top.tiled[kFwd].windows : 0;
     info->bucket_sets = plan->dynamic ? plan->nsets : 1;
     // the dense member is bucket 4: reachable as the static set itself, or through the per-call selection
-    const bool dense_reachable = plan->sets[0].dense_ok && (plan->nsets == 1 || plan->dynamic);
-    info->gather_dense_bf16 = dense_reachable ? (plan->sets[0].wgrad_ok ? 2 : 1) : 0;
-    info->batch_slab_gather = plan->top().slab_gather;
-    info->batch_slab_dot = plan->top().slab_dot;
-    info->dot_region = plan->top().dot_ok ? plan->top().tiled_dot.region_cols * 100 + plan->top().tiled_dot.region_rows : 0;
-    info->gather_fblock = plan->algo_fwd == DAU_ALGO_TILED ? plan->top().tiled_fwd.fblock : 0;
-    info->gather_variant = plan->algo_fwd == DAU_ALGO_TILED ? plan->top().tiled_fwd.variant : -1;
-    info->dense_bf16_radius3 = dense_reachable && plan->dynamic && plan->sets[0].dense3_ok ? (plan->sets[0].wgrad3_ok ? 2 : 1) : 0;
+    const bool dense_reachable = s0[kBf16R4] && (plan->nsets == 1 || plan->dynamic);
+    info->gather_dense_bf16 = dense_reachable ? (s0[kWgradR4] ? 2 : 1) : 0;
+    info->batch_slab_gather = top.slab_gather;
+    info->batch_slab_dot = top.slab_dot;
+    info->dot_region = top.has[kTiledDot] ? top.tiled_dot.region_cols * 100 + top.tiled_dot.region_rows : 0;
+    info->gather_fblock = tiled_fwd ? top.tiled[kFwd].fblock : 0;
+    info->gather_variant = tiled_fwd ? top.tiled[kFwd].variant : -1;
+    info->dense_bf16_radius3 = dense_reachable && plan->dynamic && s0[kBf16R3] ? (s0[kWgradR3] ? 2 : 1) : 0;
     info->gather_dense_split = 0;
-    if (plan->dynamic && plan->algo_fwd == DAU_ALGO_TILED)
-        for (int r = 2; r <= 4; ++r)
-            if (plan->sets[0].split_ok[r - 2]) info->gather_dense_split |= 1 << r;
+    if (plan->dynamic && tiled_fwd)
+        for (int m = kSplit2; m <= kSplit4; ++m)
+            if (s0[m]) info->gather_dense_split |= 1 << kRadius[m];
     return DAU_OK;
 }
 
@@ -649,54 +693,12 @@ int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const
     if (workspace_bytes < ws.bytes)
         return fail(DAU_INVALID_ARGUMENT, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const Shape& s = p->sh;
     if (int rc = ensure_attrs(p)) return rc;
     DAU_HIP(hipMemsetAsync(ws.status, 0, sizeof(Status), st));
     launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters);
-    launch_prepare_units(st, w, mu1, mu2, s, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table, ws.status,
+    launch_prepare_units(st, w, mu1, mu2, p->sh, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table, ws.status,
                          p->host_status);
-    if (p->algo_fwd == DAU_ALGO_TILED) {
-        Candidate cand[kMaxCandidates];
-        const int ncand = pick_candidates(p, ws.status, 0, cand);
-        if (p->profiling) ++p->prof_passes[0];
-        const size_t esize = (p->d.flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
-        for (int ci = 0; ci < ncand; ++ci) {
-            const BucketSet& bs = *cand[ci].set;
-            for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {             // one slab unless the staged copy exceeds the budget
-                const float* xs = slab_ptr(x, (size_t)n0 * s.S * s.H * s.W, esize);
-                float* ys = slab_ptr(y, (size_t)n0 * s.F * s.H * s.W, esize);
-                if (const int r = cand[ci].split_r) {                      // offsets within +-r: two-limb f16 GEMM, fp32 accuracy
-                    kSplit[r - 2].prepare(st, bs.split_fwd[r - 2], xs, ws.filters, false, ws.table, ws.tiled, cand[ci].guard);
-                    ProfScope prof(p, 0, st);
-                    kSplit[r - 2].run(st, bs.split_fwd[r - 2], ys, ws.tiled, cand[ci].guard);
-                    continue;
-                }
-                if (cand[ci].r3) {                                         // bf16 layer, offsets within +-3: 7 x 7 dense kernel
-                    r3::dense_gather_prepare(st, bs.dense3_fwd, xs, ws.filters, false, ws.table, ws.tiled, cand[ci].guard);
-                    ProfScope prof(p, 0, st);
-                    r3::dense_gather_run(st, bs.dense3_fwd, ys, ws.tiled, cand[ci].guard);
-                    continue;
-                }
-                if (bs.dense_ok) {                                         // bf16 layer, offsets within +-4: dense implicit GEMM
-                    r4::dense_gather_prepare(st, bs.dense_fwd, xs, ws.filters, false, ws.table, ws.tiled, cand[ci].guard);
-                    ProfScope prof(p, 0, st);
-                    r4::dense_gather_run(st, bs.dense_fwd, ys, ws.tiled, cand[ci].guard);
-                    continue;
-                }
-                const TiledConfig& cfg = bs.tiled_fwd;
-                for (int window = 0; window < tiled_gather_windows(cfg); ++window) {   // one pass unless the bucket is 32
-                    tiled_gather_prepare(st, cfg, xs, ws.filters, false, ws.table, ws.tiled, window, cand[ci].guard);
-                    ProfScope prof(p, 0, st);
-                    tiled_gather_run(st, cfg, ys, ws.tiled, window > 0, cand[ci].guard);
-                }
-            }
-        }
-    } else {
-        launch_blur_direct(st, x, (long)s.N * s.S, s.H, s.W, ws.filters + 0 * kFilterPlane, 1, p->blur_k, ws.xb);
-        if (p->profiling) ++p->prof_passes[0];
-        ProfScope prof(p, 0, st);
-        launch_gather_sum_direct(st, ws.xb, ws.table, s.N, s.S, s.F, s.G, s.H, s.W, y);
-    }
+    run_gather_sum(p, st, kFwd, x, y, ws.filters, ws.table, ws.status, ws.gather);
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;
 }
@@ -708,39 +710,32 @@ namespace {
 int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const float* dy, const float* mu1,
                    const float* mu2, const BwdWs& ws, float* r4, int kinds) {
     const Shape& s = p->sh;
-    const int flags = p->d.flags;
-    launch_prepare_units(st, nullptr, mu1, mu2, s, p->d.number_units_ignore, flags, p->bucket, false, ws.table_bare,
+    launch_prepare_units(st, nullptr, mu1, mu2, s, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table_bare,
                          ws.status, p->host_status);
     if (p->profiling) ++p->prof_passes[2];
     if (p->algo_bwd == DAU_ALGO_TILED) {
         Candidate cand[kMaxCandidates];
-        const int ncand = pick_candidates(p, ws.status, 1, cand);
-        const size_t esize = (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
+        const int ncand = pick_candidates(p, ws.status, kGatherDot, cand);
         for (int ci = 0; ci < ncand; ++ci) {
             const BucketSet& bs = *cand[ci].set;
-            const TiledDotConfig& cfg = bs.tiled_dot;
-            if (cand[ci].sdot) {                                               // offsets within +-4: two-limb f16 GEMM, fp32 accuracy
-                split_dot_prepare(st, bs.sdot, x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, cand[ci].guard);
+            const Guard& g = cand[ci].guard;
+            const int m = cand[ci].member;
+            if (m == kSplitDot) {                                              // the whole batch in one pass
+                split_dot_prepare(st, bs.sdot, x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
                 ProfScope prof(p, 2, st);
-                split_dot_run(st, bs.sdot, ws.table_bare, r4, ws.tiled_dot, cand[ci].guard);
-                continue;
-            }
-            if (cand[ci].r3) {                                                 // offsets within +-3: 49 displacements
+                split_dot_run(st, bs.sdot, ws.table_bare, r4, ws.tiled_dot, g);
+            } else if (m == kWgradR3 || m == kWgradR4) {                       // likewise
                 ProfScope prof(p, 2, st);
-                r3::dense_wgrad_run(st, bs.wgrad3, x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4, ws.tiled_dot, cand[ci].guard, kinds);
-                continue;
-            }
-            if (bs.wgrad_ok) {                                                 // bf16 layer, offsets within +-4, many units
-                ProfScope prof(p, 2, st);
-                r4::dense_wgrad_run(st, bs.wgrad, x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4, ws.tiled_dot, cand[ci].guard, kinds);
-                continue;
-            }
-            for (int n0 = 0; n0 < s.N; n0 += bs.slab_dot) {                // the sums of the slabs add up in r4
-                tiled_dot_prepare(st, cfg, slab_ptr(x, (size_t)n0 * s.S * s.H * s.W, esize),
-                                  slab_ptr(dy, (size_t)n0 * s.F * s.H * s.W, esize), ws.filters, ws.table_bare, p->drop_col,
-                                  p->drop_row, ws.tiled_dot, cand[ci].guard);
-                ProfScope prof(p, 2, st);
-                tiled_dot_run(st, cfg, r4, ws.tiled_dot, cand[ci].guard, n0 > 0);
+                kWgrad[m - kWgradR3].run(st, bs.wgrad[m - kWgradR3], x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4,
+                                         ws.tiled_dot, g, kinds);
+            } else {
+                for (int n0 = 0; n0 < s.N; n0 += bs.slab_dot) {            // the sums of the slabs add up in r4
+                    tiled_dot_prepare(st, bs.tiled_dot, slab_ptr(x, (size_t)n0 * s.S * s.H * s.W, p->esize()),
+                                      slab_ptr(dy, (size_t)n0 * s.F * s.H * s.W, p->esize()), ws.filters, ws.table_bare,
+                                      p->drop_col, p->drop_row, ws.tiled_dot, g);
+                    ProfScope prof(p, 2, st);
+                    tiled_dot_run(st, bs.tiled_dot, r4, ws.tiled_dot, g, n0 > 0);
+                }
             }
         }
     } else {
@@ -789,47 +784,7 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
         const bool fresh = !(need_mask & param_mask);     // this call has not looked at the offsets yet
         launch_prepare_units(st, w, mu1, mu2, s, 0, flags, p->bucket, true, ws.table_t, fresh ? ws.status : nullptr,
                              p->host_status);
-        if (p->profiling) ++p->prof_passes[1];
-        if (p->algo_fwd == DAU_ALGO_TILED) {
-            Candidate cand[kMaxCandidates];
-            const int ncand = pick_candidates(p, ws.status, 0, cand);
-            const size_t esize = (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4;
-            for (int ci = 0; ci < ncand; ++ci) {
-                const BucketSet& bs = *cand[ci].set;
-                for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {
-                    const float* dys = slab_ptr(dy, (size_t)n0 * s.F * s.H * s.W, esize);
-                    float* dxs = slab_ptr(dx, (size_t)n0 * s.S * s.H * s.W, esize);
-                    if (const int r = cand[ci].split_r) {
-                        kSplit[r - 2].prepare(st, bs.split_dx[r - 2], dys, ws.filters, true, ws.table_t, ws.tiled_dx, cand[ci].guard);
-                        ProfScope prof(p, 1, st);
-                        kSplit[r - 2].run(st, bs.split_dx[r - 2], dxs, ws.tiled_dx, cand[ci].guard);
-                        continue;
-                    }
-                    if (cand[ci].r3) {
-                        r3::dense_gather_prepare(st, bs.dense3_dx, dys, ws.filters, true, ws.table_t, ws.tiled_dx, cand[ci].guard);
-                        ProfScope prof(p, 1, st);
-                        r3::dense_gather_run(st, bs.dense3_dx, dxs, ws.tiled_dx, cand[ci].guard);
-                        continue;
-                    }
-                    if (bs.dense_ok) {
-                        r4::dense_gather_prepare(st, bs.dense_dx, dys, ws.filters, true, ws.table_t, ws.tiled_dx, cand[ci].guard);
-                        ProfScope prof(p, 1, st);
-                        r4::dense_gather_run(st, bs.dense_dx, dxs, ws.tiled_dx, cand[ci].guard);
-                        continue;
-                    }
-                    const TiledConfig& cfg = bs.tiled_dx;
-                    for (int window = 0; window < tiled_gather_windows(cfg); ++window) {
-                        tiled_gather_prepare(st, cfg, dys, ws.filters, true, ws.table_t, ws.tiled_dx, window, cand[ci].guard);
-                        ProfScope prof(p, 1, st);
-                        tiled_gather_run(st, cfg, dxs, ws.tiled_dx, window > 0, cand[ci].guard);
-                    }
-                }
-            }
-        } else {
-            launch_blur_direct(st, dy, (long)s.N * s.F, s.H, s.W, ws.filters + 5 * kFilterPlane, 1, p->blur_k, ws.eb);
-            ProfScope prof(p, 1, st);
-            launch_gather_sum_direct(st, ws.eb, ws.table_t, s.N, s.F, s.S, s.G, s.H, s.W, dx);
-        }
+        run_gather_sum(p, st, kDx, dy, dx, ws.filters, ws.table_t, ws.status, ws.gather_dx);
     }
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;
@@ -872,13 +827,7 @@ int dau_conv_check_status(const dau_conv_plan* p, void* stream, const void* work
     std::memcpy(&mx, &h.max_abs_mu_bits, sizeof(float));
     if (max_abs_mu_out) *max_abs_mu_out = mx;
     if (h.nan_seen || mx > (float)p->bucket) clear_reported_status(p, h.max_abs_mu_bits, h.nan_seen != 0);   // reported here
-    if (h.nan_seen) return fail(DAU_FAILED_PRECONDITION, "DAUConvOp ERROR: got NaN value in offset (mu1,mu2) variable");
-    if (mx > (float)p->bucket)
-        return fail(DAU_INVALID_ARGUMENT,
-                    "DAUConvOp ERROR: actual offsets (%.3f) larger than what max_kernel_size=%d allows (setup max_kernel_size "
-                    "and dau_unit_border_bound correctly to avoid this)",
-                    mx, p->d.max_kernel_size);
-    return DAU_OK;
+    return status_error(p, mx, h.nan_seen != 0);
 }
 
 int dau_conv_last_status(const dau_conv_plan* p, float* max_abs_mu_out, int32_t* valid_out) {
@@ -886,12 +835,12 @@ int dau_conv_last_status(const dau_conv_plan* p, float* max_abs_mu_out, int32_t*
     if (max_abs_mu_out) *max_abs_mu_out = 0.0f;
     if (valid_out) *valid_out = 0;
     if (!p->host_status) return DAU_OK;
-    const volatile unsigned* h = reinterpret_cast<const volatile unsigned*>(p->host_status);
-    if (h[2] != 1u && h[4] == 0u && h[5] == 0u) return DAU_OK;   // no call has completed yet
+    const volatile HostStatus* h = p->host_status;
+    if (h->valid != 1u && h->bad_max_abs_mu_bits == 0u && h->bad_nan_seen == 0u) return DAU_OK;   // no call has completed yet
     // the sticky record first: the worst status of ANY completed call since the last report (a later good call of another
     // layer sharing this plan must not hide it); then the most recent call
-    const unsigned bad_bits = h[4], bad_nan = h[5];
-    unsigned bits = h[0], nan_seen = h[1] | bad_nan;
+    const unsigned bad_bits = h->bad_max_abs_mu_bits, bad_nan = h->bad_nan_seen;
+    unsigned bits = h->max_abs_mu_bits, nan_seen = h->nan_seen | bad_nan;
     if (bad_bits > bits) bits = bad_bits;                // non-negative float bits order like unsigned integers
     float mx;
     std::memcpy(&mx, &bits, sizeof(float));
@@ -899,13 +848,7 @@ int dau_conv_last_status(const dau_conv_plan* p, float* max_abs_mu_out, int32_t*
     if (valid_out) *valid_out = 1;
     // a bad status is reported once: the mirror goes back to "nothing reported" until the next call completes
     if (nan_seen || mx > (float)p->bucket) clear_host_status(p);
-    if (nan_seen) return fail(DAU_FAILED_PRECONDITION, "DAUConvOp ERROR: got NaN value in offset (mu1,mu2) variable");
-    if (mx > (float)p->bucket)
-        return fail(DAU_INVALID_ARGUMENT,
-                    "DAUConvOp ERROR: actual offsets (%.3f) larger than what max_kernel_size=%d allows (setup max_kernel_size "
-                    "and dau_unit_border_bound correctly to avoid this)",
-                    mx, p->d.max_kernel_size);
-    return DAU_OK;
+    return status_error(p, mx, nan_seen != 0);
 }
 
 int dau_conv_filters(const dau_conv_plan* p, void* stream, const float* sigma, float* filters_out) {

@@ -53,7 +53,7 @@ struct DenseConfig {
 // 7 x 7): the same source compiled twice (Makefile); `R` of configure must be the namespace's radius.
 #define DAU_DECLARE_DENSE_GATHER(NS)                                                                                           \
     namespace NS {                                                                                                            \
-    bool dense_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, DenseConfig* cfg); \
+    bool dense_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, DenseConfig* cfg);  \
     size_t dense_gather_workspace_bytes(const DenseConfig& cfg);                                                              \
     void dense_gather_init(const DenseConfig& cfg);                                                                           \
     /* prepare: dense kernel synthesis from the unit table ([Cin][G][Cout]) + blurred bf16 staging of `in`; run: the GEMM */  \

@@ -620,8 +620,8 @@ void stage_rows_plan(const DenseConfig& c, int* RB, int* nbands, size_t* lds) {
 
 }  // namespace
 
-bool dense_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, bool bf16, DenseConfig* cfg) {
-    if (R != kDR || !bf16) return false;          // the 9 x 9 dense kernel covers offsets within +-4; bf16 layers only
+bool dense_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, DenseConfig* cfg) {
+    if (R != kDR || act != kActBF16) return false;  // the 9 x 9 dense kernel covers offsets within +-4; bf16 layers only
     DenseConfig c{};
     c.N = N; c.Cin = Cin; c.Cout = Cout; c.G = G; c.H = H; c.W = W; c.R = R; c.blur_k = blur_k; c.act = kActBF16;
     const DenseGeom g = dense_geometry(c);
