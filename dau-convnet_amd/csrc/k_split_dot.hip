@@ -20,6 +20,10 @@
 //    rows, the items walking down column strips so that each copies only its RH new rows, one item ahead.  A wave owns
 //    2 input channels x 4 units = 8 tiles of 16 units (s, g, the block's 16 f) for the whole kernel.  Lane group j = row j of
 //    the region, K step = one column: every address is a per-lane base plus an immediate.
+//  * A operand.  A lane's row is m = 4 k + 2 dy + dx: at K step c + 1 the lane with dx = 0 needs the 32 bytes its quad neighbour
+//    (dx = 1) held at step c.  Each Xk column is therefore loaded once per wave, per PAIR of K steps, and the odd step's fragment
+//    is built from the neighbour's registers with one select and one quad-permute DPP move per dword (no LDS traffic):
+//    RW / 2 + 1 loads per item, channel and limb instead of RW (the + 1: column RW of the item's own rows for the last step).
 //  * Bank conflicts.  The LDS window is position-major with the 16 output channels of a position in consecutive 16-byte groups, so
 //    the bank group of a ds_read_b128 is (lane % 16) whatever the unit's displacement: every read phase of 16 lanes touches 16
 //    distinct groups.  The unit-to-lane placement (lane % 16 = f % 16) is conflict-free by construction; no placement table.
@@ -86,7 +90,8 @@ SdLayout sd_layout(const SplitDotConfig& c, const SdGeom& g) {
     size_t off = 0;
     l.maxes_off = off; off += rup((size_t)(s.S * kNumK + s.F) * 4);
     l.xk_off = off; off += rup((size_t)g.NP * s.S * s.H * s.W * 32);                              // blur4_pack output, fp32
-    l.xs_off = off; off += rup((size_t)g.octs * s.S * kNumK * g.XTr * g.XTc * 32);
+    // + one position: the pair load of column Wq (sd_next_col) reads, unused, the position after the last plane's last column
+    l.xs_off = off; off += rup((size_t)g.octs * s.S * kNumK * g.XTr * g.XTc * 32 + 32);
     l.es_off = off; off += rup((size_t)g.octs * g.nfb * g.EYs * g.EXs * 512);
     l.partial_off = off; off += rup((size_t)g.chunks * kNumK * s.S * s.G * s.F * 4);
     l.total = off;
@@ -258,6 +263,20 @@ __device__ __forceinline__ void sd_glds16(const char* src, unsigned dst) {
                  : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
 }
 
+// The A fragment of the next K step from those of a pair of steps: a lane offers its quad neighbour the column that lane needs
+// (`cur` if it holds dx = 1, `nxt`, the pair after, if it holds dx = 0) and takes what the neighbour offers (lanes 2 q <-> 2 q + 1)
+#ifndef DAU_SD_STEP_LOADS
+__device__ __forceinline__ h8 sd_next_col(h8 cur, h8 nxt, int dx) {
+    typedef int i4s __attribute__((ext_vector_type(4)));
+    const i4s c = __builtin_bit_cast(i4s, cur), n = __builtin_bit_cast(i4s, nxt);
+    i4s r;
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+        r[d] = __builtin_amdgcn_update_dpp(0, dx ? c[d] : n[d], 0xB1 /* quad_perm:[1,0,3,2] */, 0xF, 0xF, true);
+    return __builtin_bit_cast(h8, r);
+}
+#endif
+
 // RW: columns per region (K steps per item).  The error window of an item is WR = RH + 2R rows x RW + 2R columns x 512 B; the
 // LDS holds a RING of WR + RH rows.  The items of a chunk walk DOWN a column strip of regions (one image octet), so the window of
 // the next item is the current one moved down by RH rows: its RH new rows are copied into the ring's RH free slots while the
@@ -275,7 +294,12 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
     constexpr unsigned RB = WL * 512;                    // bytes per window row
     constexpr int kRowPieces = (RB + 1023) / 1024;       // 1 KiB pieces per row (a whole number: WL is even)
     static_assert((kRing & (kRing - 1)) == 0, "ring slot = (origin + row) & (kRing - 1)");
-    static_assert(RW % 2 == 0, "A fragment sets by the parity of the K step");
+    static_assert(RW % 2 == 0, "A fragment sets by the parity of the K step / of the pair of K steps");
+#ifdef DAU_SD_STEP_LOADS
+    constexpr int kSdAStride = 2;                        // 16-byte units between the two A sets at the start of an item: a column
+#else
+    constexpr int kSdAStride = 4;                        // a pair of columns
+#endif
     static_assert((size_t)kRing * RB <= 160 * 1024, "the ring fills the LDS");
     int t = blockIdx.x;
     const int gb = t % a.ngb; t /= a.ngb;
@@ -355,15 +379,24 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
         }
 #endif
     };
-    // A fragments, two K steps ahead: set p holds the steps of parity p (RW is even); the last two steps of an item fetch the
-    // first two of the next item (software pipeline)
+    // A fragments.  A lane's row is m = 4 k + 2 dy + dx, so at K step c + 1 the lane with dx = 0 needs the 32 bytes its quad
+    // neighbour (dx = 1) held at step c: the columns are loaded per PAIR of K steps.  Pair r of an item is P_r = X[row j + dy,
+    // column 2 r + dx]; step 2 r uses it as is, step 2 r + 1 takes the neighbour's P_r (dx = 0) or P_{r + 1} (dx = 1): one select
+    // and one quad-permute DPP move per dword (sd_next_col), no LDS traffic.  Set p holds the pairs of parity p; a set is
+    // reloaded with pair r + 2 once pair r's odd-step fragment is built: two K steps ahead, as the per-step loads were.  The
+    // last odd step needs column RW of the item's own rows (the next item is the region below): pair RW / 2, of which only the
+    // dx = 0 lanes' half is used (XTc = Wq + 1 holds that column; the dx = 1 lanes read one position on, inside the staging's
+    // padding).  RW / 2 + 1 loads per item, channel and limb instead of RW.  The last pair fetches the first two pairs of the
+    // next item into sets 0 and 1 (software pipeline).
+    // -DDAU_SD_STEP_LOADS (tuning builds) keeps one load per K step, set p holding the steps of parity p: the same fragments
+    // into the same MFMAs, bit for bit.
     h8 ahi[2][kSdAS], alo[2][kSdAS];
     if (it0 < it1) {
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int i = 0; i < kSdAS; ++i) {
-                const h8* ap = a.xs + item_off(it0) + (size_t)p * 2 + aoff[i];
+                const h8* ap = a.xs + item_off(it0) + (size_t)p * kSdAStride + aoff[i];
                 ahi[p][i] = ap[0]; alo[p][i] = ap[1];
             }
     }
@@ -404,13 +437,14 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
         for (int i = 0; i < kSdAS; ++i)
 #pragma unroll
             for (int gg = 0; gg < kSdGT; ++gg) part[i][gg] = f4s{0.0f, 0.0f, 0.0f, 0.0f};
-        // One K step per iteration (unrolled over the item, hipcc hoists loads of later steps until it spills).  Inside a step
-        // the two input channels are two groups of 12 MFMAs; the B fragments of group i + 1 are read from LDS while group i
-        // runs, and the A fragments of channel i for the next step are requested once group i has issued (sched barriers pin it).
+        // Inside a K step the two input channels are two groups of 12 MFMAs; the B fragments of group i + 1 are read from LDS
+        // while group i runs, and what follows the MFMAs of group i (the odd step's fragment, the loads of channel i) is issued
+        // while they run (sched barriers pin it).  The item is not unrolled whole: hipcc hoists loads of later steps until it
+        // spills.
 #ifdef DAU_SD_DIAG_NOA
-#define SD_LOAD_A(P, i)
+#define SD_LOAD_A(P, i, an)
 #else
-#define SD_LOAD_A(P, i) { const h8* ap = a.xs + an + aoff[i]; ahi[P][i] = ap[0]; alo[P][i] = ap[1]; }
+#define SD_LOAD_A(P, i, an) { const h8* ap = a.xs + (an) + aoff[i]; ahi[P][i] = ap[0]; alo[P][i] = ap[1]; }
 #endif
 #define SD_READ_B(i, bh, bl)                                                                                    \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
@@ -418,33 +452,76 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
         bh[gg] = *reinterpret_cast<const h8*>(bp);                                                              \
         bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                                        \
     }
-#define SD_GROUP(P, i, bh, bl)                                                                                  \
+        // group i of a K step: the MFMAs on the fragment (AH, AL), then AFTER, between two sched barriers
+#define SD_GROUP(i, AH, AL, bh, bl, AFTER)                                                                      \
     __builtin_amdgcn_sched_barrier(0);                                                                          \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[P][i], bh[gg], part[i][gg], 0, 0, 0);          \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[P][i], bh[gg], part[i][gg], 0, 0, 0);          \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[P][i], bl[gg], part[i][gg], 0, 0, 0);          \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, bh[gg], part[i][gg], 0, 0, 0);                 \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, bh[gg], part[i][gg], 0, 0, 0);                 \
+        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, bl[gg], part[i][gg], 0, 0, 0);                 \
     }                                                                                                           \
-    SD_LOAD_A(P, i)                                                                                             \
+    AFTER                                                                                                       \
     __builtin_amdgcn_sched_barrier(0);
-        // K step kk with the A set of its parity P; the set then fetches step kk + 2 (of the next item past the last step)
-#define SD_STEP(P, kk)                                                                                          \
+#define SD_STEP(kk, AH, AL, AFTER0, AFTER1)                                                                     \
     {                                                                                                           \
         const int k = (kk);                                                                                     \
         h8 b0h[kSdGT], b0l[kSdGT], b1h[kSdGT], b1l[kSdGT];                                                      \
-        const size_t an = k + 2 < RW ? ioff + (size_t)(k + 2) * 2 : ioff_next + (size_t)(k + 2 - RW) * 2;       \
-        (void)an;                                                                                               \
         SD_READ_B(0, b0h, b0l)                                                                                  \
         SD_READ_B(1, b1h, b1l)                                                                                  \
-        SD_GROUP(P, 0, b0h, b0l)                                                                                \
-        SD_GROUP(P, 1, b1h, b1l)                                                                                \
+        SD_GROUP(0, AH[0], AL[0], b0h, b0l, AFTER0)                                                             \
+        SD_GROUP(1, AH[1], AL[1], b1h, b1l, AFTER1)                                                             \
     }
         static_assert(kSdAS == 2, "two groups per K step");
+#ifdef DAU_SD_STEP_LOADS
+        // K step kk with the A set of its parity P; the set then fetches step kk + 2 (of the next item past the last step)
+#define SD_STEP1(P, kk)                                                                                         \
+    {                                                                                                           \
+        const size_t an = (kk) + 2 < RW ? ioff + (size_t)((kk) + 2) * 2 : ioff_next + (size_t)((kk) + 2 - RW) * 2; \
+        (void)an;                                                                                               \
+        SD_STEP(kk, ahi[P], alo[P], SD_LOAD_A(P, 0, an), SD_LOAD_A(P, 1, an))                                   \
+    }
 #pragma unroll 1
         for (int k2 = 0; k2 < RW; k2 += 2) {
-            SD_STEP(0, k2)
-            SD_STEP(1, k2 + 1)
+            SD_STEP1(0, k2)
+            SD_STEP1(1, k2 + 1)
         }
+#undef SD_STEP1
+#else
+        // Pair r = K steps 2 r, 2 r + 1, its columns in set P.  Group i of the even step builds the odd step's fragment of
+        // channel i from the two sets and then reloads set P with pair r + 2 of the item (r + 2 <= RW / 2).
+        h8 aqh[kSdAS], aql[kSdAS];
+#define SD_NEXT_COL(P, i)                                                                                       \
+    aqh[i] = sd_next_col(ahi[P][i], ahi[1 - (P)][i], adx);                                                      \
+    aql[i] = sd_next_col(alo[P][i], alo[1 - (P)][i], adx);
+#define SD_PAIR(P, rr)                                                                                          \
+    {                                                                                                           \
+        const size_t an = ioff + (size_t)((rr) + 2) * 4;                                                        \
+        (void)an;                                                                                               \
+        SD_STEP(2 * (rr), ahi[P], alo[P], SD_NEXT_COL(P, 0) SD_LOAD_A(P, 0, an), SD_NEXT_COL(P, 1) SD_LOAD_A(P, 1, an)) \
+        SD_STEP(2 * (rr) + 1, aqh, aql, , )                                                                     \
+    }
+        // the item's last pair: both sets are free once the odd step's fragment is built, and fetch pairs 0 and 1 of the next item
+#define SD_PAIR_LAST(P, rr)                                                                                     \
+    {                                                                                                           \
+        SD_STEP(2 * (rr), ahi[P], alo[P], SD_NEXT_COL(P, 0) SD_LOAD_A(0, 0, ioff_next), SD_NEXT_COL(P, 1) SD_LOAD_A(0, 1, ioff_next)) \
+        SD_STEP(2 * (rr) + 1, aqh, aql, SD_LOAD_A(1, 0, ioff_next + 4), SD_LOAD_A(1, 1, ioff_next + 4))         \
+    }
+        constexpr int kPairs = RW / 2, kLoopPairs = (kPairs - 1) / 2 * 2;   // the loop takes two pairs (one per set) at a time
+#pragma unroll 1
+        for (int r2 = 0; r2 < kLoopPairs; r2 += 2) {
+            SD_PAIR(0, r2)
+            SD_PAIR(1, r2 + 1)
+        }
+        if constexpr (kPairs - kLoopPairs == 2) {
+            SD_PAIR(0, kPairs - 2)
+            SD_PAIR_LAST(1, kPairs - 1)
+        } else {
+            SD_PAIR_LAST(0, kPairs - 1)
+        }
+#undef SD_NEXT_COL
+#undef SD_PAIR
+#undef SD_PAIR_LAST
+#endif
 #undef SD_READ_B
 #undef SD_GROUP
 #undef SD_LOAD_A
