@@ -107,10 +107,12 @@ void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& cfg, const float* x
 void tiled_dot_run(hipStream_t st, const TiledDotConfig& cfg, float* r4, void* workspace, const Guard& guard, bool accumulate);
 void tiled_dot_init(const TiledDotConfig& cfg);
 
-// The four derivative-filtered copies of x, staged position-major (k_gather_dot.hip): x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4][2]
+// The four derivative-filtered copies of x, staged position-major (k_gather_dot.hip): x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4][2].
+// kmax (optional, [cstride][4 kinds] float bits, zeroed by the caller): max |value| per (channel, kind) over the finite values,
+// taken while they are written (a kernel instantiation of its own: callers that pass none run the plain one)
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard);
-void blur4_pack_init(int blur_k);
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax = nullptr);
+void blur4_pack_init(int blur_k, bool kmax = false);
 bool blur4_pack_fits(int blur_k, int Hp, int Wp);
 
 // r4[k][u] = sum over the slabs of partial[slab][k][u] in double (the gather-dot's deterministic reduction, k_gather_dot.hip)

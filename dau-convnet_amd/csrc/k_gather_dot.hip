@@ -286,6 +286,7 @@ struct Blur4Args {
     const float* in;
     const float* taps;
     float* xk;
+    unsigned* kmax;             // KMAX kernels: max |value| per (channel, kind) over the finite values stored (float bits)
     int N, C, cstride, H, W, k, Hp, Wp;
     int act;                    // storage format of the input (ActFormat)
     int ppb, items;             // windows per workgroup (small maps) and windows in total
@@ -295,7 +296,10 @@ struct Blur4Args {
 };
 
 // K: compile-time prefilter support (taps live in SGPRs, tap loops unrolled); K = 0: any support
-template <int K>
+// KMAX: also take max |value| per (channel, kind) of what is stored, over finite values only (the scales of the two-limb
+// gather-dot, k_split_dot.hip: the values are in registers here, a pass of its own would read all of XK back).  A wave works
+// on one window, so on one channel: it reduces its four maxima across its lanes and lane 0 issues one atomicMax per kind.
+template <int K, bool KMAX>
 __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!guard_pass(a.guard)) return;
@@ -379,6 +383,15 @@ __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
     });
     __syncthreads();
     f8* out = reinterpret_cast<f8*>(a.xk) + ((size_t)np * a.cstride + c) * a.Hp * a.Wp;
+    // KMAX: the maxima are kept as keys (bits << 1) + 2^24: the shift drops the sign, and the addition wraps an Inf / NaN
+    // (exponent 255) below the key of zero, so that an unsigned maximum passes over it: one v_lshl_add_u32 per value, one
+    // v_max3_u32 per pair.  What kmax holds so far is read here, long before it is needed (below).
+    constexpr unsigned kKeyZero = 1u << 24;
+    unsigned km[4] = {kKeyZero, kKeyZero, kKeyZero, kKeyZero}, seen[4] = {0u, 0u, 0u, 0u};
+    if constexpr (KMAX) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) seen[q] = __hip_atomic_load(a.kmax + c * kNumK + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     for_each(active ? oh : 0, ow, [&](int yr, int xc) {
         const int yy = oy0 + yr, xx = ox0 + xc;
         f2 dw = {0.0f, 0.0f}, d1 = {0.0f, 0.0f}, d2 = {0.0f, 0.0f}, ds = {0.0f, 0.0f};
@@ -394,7 +407,24 @@ __global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
             }
         }
         out[(size_t)yy * a.Wp + xx] = f8{dw.x, dw.y, d1.x, d1.y, d2.x, d2.y, ds.x, ds.y};
+        if constexpr (KMAX) {
+            const f2 kv[4] = {dw, d1, d2, ds};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                km[q] = max(max(km[q], (__float_as_uint(kv[q].x) << 1) + kKeyZero), (__float_as_uint(kv[q].y) << 1) + kKeyZero);
+        }
     });
+    if constexpr (KMAX) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            unsigned m = km[q];
+            for (int o = 32; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+            // a maximum only grows: a value that does not exceed what was there when the workgroup began changes nothing (a
+            // stale, smaller reading only costs the atomic) -- most waves issue none, and none waits for one
+            const unsigned bits = (m - kKeyZero) >> 1;
+            if (lane == 0 && bits > seen[q]) atomicMax(a.kmax + c * kNumK + q, bits);
+        }
+    }
 }
 
 // per-lane parameters: params[sub][s][gb][gp][fb][lane][8] = {b00, b01, b10, b11, base, 0, 0, 0}
@@ -1337,21 +1367,26 @@ void dispatch_dot(bool binned, bool ring, int RW, int RH, int GP, int AS, hipStr
     }
 }
 
-auto blur4_pack_for(int blur_k) {
-    return blur_k == 7 ? blur4_pack_kernel<7> : blur_k == 5 ? blur4_pack_kernel<5> : blur_k == 9 ? blur4_pack_kernel<9> : blur4_pack_kernel<0>;
+template <bool KMAX>
+const void* blur4_pack_pick(int blur_k) {
+    auto kern = blur_k == 7 ? blur4_pack_kernel<7, KMAX> : blur_k == 5 ? blur4_pack_kernel<5, KMAX>
+              : blur_k == 9 ? blur4_pack_kernel<9, KMAX> : blur4_pack_kernel<0, KMAX>;
+    return reinterpret_cast<const void*>(kern);
 }
+const void* blur4_pack_for(int blur_k, bool kmax = false) { return kmax ? blur4_pack_pick<true>(blur_k) : blur4_pack_pick<false>(blur_k); }
 
 }  // namespace
 
-// x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1
+// x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1;
+// kmax != nullptr: kmax[cstride][4 kinds] (float bits, zeroed by the caller) receives max |value| over the finite values
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard) {
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax) {
     int wy, wx; size_t blur_lds;
     blur4_plan(blur_k, Hp, Wp, &wy, &wx, &blur_lds);
-    auto kern = blur4_pack_for(blur_k);
+    const void* kern = blur4_pack_for(blur_k, kmax != nullptr);
     Blur4Args b{};
     b.guard = guard;
-    b.in = x; b.taps = filters + kTaps1dOffset; b.xk = xk;
+    b.in = x; b.taps = filters + kTaps1dOffset; b.xk = xk; b.kmax = kmax;
     b.N = N; b.C = C; b.cstride = cstride; b.H = H; b.W = W; b.k = blur_k; b.Hp = Hp; b.Wp = Wp; b.act = act;
     b.WY = wy; b.WX = wx; b.nwy = (Hp + wy - 1) / wy; b.nwx = (Wp + wx - 1) / wx;
     // small windows: several per workgroup, so that the 512 threads have rows to share
@@ -1360,7 +1395,8 @@ void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int
     while (b.ppb > 1 && b.ppb * blur_lds > 64 * 1024) b.ppb /= 2;
     b.items = ((N + 1) / 2) * b.nwy * b.nwx * cstride;
     b.lds_item_floats = (unsigned)(blur_lds / 4);
-    hipLaunchKernelGGL(kern, dim3((b.items + b.ppb - 1) / b.ppb), dim3(512), b.ppb * blur_lds, st, b);
+    void* params[] = {&b};
+    (void)hipLaunchKernel(kern, dim3((b.items + b.ppb - 1) / b.ppb), dim3(512), params, b.ppb * blur_lds, st);
 }
 void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, long n, int G, int F, int g_split, int slabs0,
                        int slabs1, int zero_from, bool accumulate, float* r4, const Guard& guard) {
@@ -1368,8 +1404,8 @@ void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, lon
     hipLaunchKernelGGL(dot_reduce_kernel, dim3(rgrid), dim3(256), 0, st, partial, partial_f32, n, G, F, g_split, slabs0, slabs1,
                        zero_from, accumulate ? 1 : 0, r4, guard);
 }
-void blur4_pack_init(int blur_k) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur4_pack_for(blur_k)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+void blur4_pack_init(int blur_k, bool kmax) {
+    (void)hipFuncSetAttribute(blur4_pack_for(blur_k, kmax), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 bool blur4_pack_fits(int blur_k, int Hp, int Wp) {
     int wy, wx; size_t blur_lds;
@@ -1411,7 +1447,7 @@ void tiled_dot_init(const TiledDotConfig& c) {
     const DotGeometry g = make_dot_geometry(c.sh, c.R, c.as1, c.one_tile, c.rounds, c.rw8);
     for (int i = 0; i < g.npass; ++i) dispatch_dot(g.nsub1 > 1, c.ring, g.RW, g.RH, g.pass[i].GP, g.pass[i].AS, nullptr, nullptr, 0, 0);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pack_error_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur4_pack_for(c.blur_k)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(blur4_pack_for(c.blur_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& c, const float* x, const float* dy, const float* filters,

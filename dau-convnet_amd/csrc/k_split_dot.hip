@@ -111,6 +111,11 @@ __device__ __forceinline__ bool finite_abs(float v, float* a) {
     return *a <= FLT_MAX;
 }
 
+// max |Xk| per (input channel, kind) is taken by blur4_pack itself while it writes XK (launch_blur4_pack's kmax).
+// -DDAU_SD_STAGE_REF (libdau_conv_hip_stage_ref.so of `make tuning`) keeps the staging that came before: this pass over XK and
+// the sd_stage_e_kernel with one thread per position -- the bit-exact reference of tests/test_gpu_split_dot_stage_fused.py and
+// the A side of kernel-level timings.
+#ifdef DAU_SD_STAGE_REF
 // max |Xk| per (input channel, kind) over the fp32 staging of blur4_pack ([NP][S][H][W][4 kinds][2 images]): grid (S, split)
 __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restrict__ xk, int NP, int S, int HW, int split,
                                                           unsigned* __restrict__ xmax, const Guard guard) {
@@ -140,6 +145,7 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
     }
     if (threadIdx.x < 4) atomicMax(&xmax[s * kNumK + threadIdx.x], __float_as_uint(red[threadIdx.x][0]));
 }
+#endif
 
 // max |dy| per output channel: grid (F, split); dy is fp32 or f16 (act)
 __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
@@ -207,8 +213,64 @@ __global__ void __launch_bounds__(256) sd_stage_x_kernel(const float* __restrict
     }
 }
 
-// ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W] (fp32 or f16: act): one thread per (oct, fb, Vy, Vx), the 16 channels
-// of the block.  An f16 dy times the power-of-two scale is its own hi limb; its lo limb is zero.
+// ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W] (fp32 or f16: act).  An f16 dy times the power-of-two scale is its own
+// hi limb; its lo limb is zero.
+#ifndef DAU_SD_STAGE_REF
+// A workgroup writes one window row (oct, fb, Vy) -- a column tile of it where the row is wider than kSeTX positions.  A thread
+// takes one (channel, x) of the row's image part: its eight loads (the octet's images) run along x across the lanes, it scales
+// and splits in registers and puts the two 16-byte pieces of its eight values where they go in the row's image in LDS; then
+// the workgroup copies the image out, 16 bytes per lane, consecutive lanes to consecutive addresses.  Halo rows and columns
+// (the edge rule's dropped row / column included) are plain zero stores.  The 32 pieces of a position are permuted by
+// (position & 7), so that the eight lanes of a ds_write_b128 group (eight consecutive x, one channel) reach all 32 banks.
+constexpr int kSeTX = 80;               // window columns per workgroup: 40 KiB of LDS, four workgroups per CU
+__global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
+                                                         int F, int H, int W, int nfb, int EYs, int EXs, int nct, int TX,
+                                                         int drop_col, int drop_row, int act, h8* __restrict__ es,
+                                                         const Guard guard) {
+    __shared__ h8 tile[kSeTX * 32];
+    if (!guard_pass(guard)) return;
+    int t = blockIdx.x;
+    const int ct = t % nct; t /= nct;
+    const int vy = t % EYs; t /= EYs;
+    const int fb = t % nfb;
+    const int oct = t / nfb;
+    const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
+    const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
+    const int y = vy - (kSdR + 1);
+    // its columns inside the image: [c0, c1)
+    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    const int nd = max(c1 - c0, 0);
+    for (int i = threadIdx.x; i < kSdFB * nd; i += 256) {
+        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdR + 1), lx = vx - vx0;
+        const int f = fb * kSdFB + fl;
+        const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
+        float v[8];
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int img = oct * 8 + n;
+            v[n] = (f < F && img < N) ? load_act(dy, (((long)img * F + f) * H + y) * W + x, act) : 0.0f;
+        }
+        h8 hi, lo;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            _Float16 h, l;
+            split_limbs(v[n] * sc, &h, &l);
+            hi[n] = h; lo[n] = l;
+        }
+        tile[lx * 32 + (fl ^ (lx & 7))] = hi;
+        tile[lx * 32 + ((kSdFB + fl) ^ (lx & 7))] = lo;
+    }
+    if (nd > 0) __syncthreads();                         // (nd is the same for the whole workgroup)
+    h8* dst = es + ((((size_t)oct * nfb + fb) * EYs + vy) * EXs + vx0) * 32;
+    for (int q = threadIdx.x; q < nvx * 32; q += 256) {
+        const int lx = q >> 5, vx = vx0 + lx;
+        h8 piece = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (vx >= c0 && vx < c1) piece = tile[lx * 32 + ((q & 31) ^ (lx & 7))];
+        dst[q] = piece;
+    }
+}
+#else
+// (the earlier form) one thread per (oct, fb, Vy, Vx), the 16 channels of the block
 __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
                                                          int F, int H, int W, int octs, int nfb, int EYs, int EXs, int drop_col,
                                                          int drop_row, int act, h8* __restrict__ es, const Guard guard) {
@@ -240,6 +302,7 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
         }
     }
 }
+#endif
 
 struct SdArgs {
     const h8* xs;
@@ -587,7 +650,11 @@ size_t split_dot_workspace_bytes(const SplitDotConfig& c) { return sd_layout(c, 
 
 void split_dot_init(const SplitDotConfig& c) {
     dispatch_sd(c.RW, nullptr, nullptr, 0);
+#ifndef DAU_SD_STAGE_REF
+    blur4_pack_init(c.blur_k, true);
+#else
     blur4_pack_init(c.blur_k);
+#endif
 }
 
 void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, const float* dy, const float* filters,
@@ -601,16 +668,26 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     float* xk = reinterpret_cast<float*>(ws + l.xk_off);
     (void)hipMemsetAsync(xmax, 0, (size_t)(s.S * kNumK + s.F) * 4, st);
     (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard);
     const int HW = s.H * s.W;
+#ifndef DAU_SD_STAGE_REF
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax);
+#else
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard);
     const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
     hipLaunchKernelGGL(sd_absmax_x_kernel, dim3(s.S * xsplit), dim3(256), 0, st, xk, g.NP, s.S, HW, xsplit, xmax, guard);
+#endif
     const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
     hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
     hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
                        reinterpret_cast<h8*>(ws + l.xs_off), guard);
+#ifndef DAU_SD_STAGE_REF
+    const int nct = (g.EXs + kSeTX - 1) / kSeTX, tx = (g.EXs + nct - 1) / nct;    // column tiles of a window row, evenly wide
+    hipLaunchKernelGGL(sd_stage_e_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F, s.H,
+                       s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+#else
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3(4096), dim3(256), 0, st, dy, emax, s.N, s.F, s.H, s.W, g.octs, g.nfb, g.EYs, g.EXs,
                        drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+#endif
 }
 
 void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table, float* r4, void* workspace, const Guard& guard) {
