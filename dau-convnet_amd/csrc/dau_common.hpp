@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <cmath>
 #include <cstdint>
 #include <type_traits>
 #include "dau_conv.h"
@@ -141,8 +142,12 @@ constexpr int kFilterFloats = kTaps1dOffset + kNumTap1d * kTapPitch;
 struct Status {
     unsigned int max_abs_mu_bits;  // float bits of max(|mu1|,|mu2|); valid because |x| bits order like uints
     unsigned int nan_seen;
+    // pad[0]: ticket counter of prepare_units_kernel's workgroups.  pad[1]: bits 0..30 the live units with max(|mu1|,|mu2|) > 3
+    // ("outlier units", counted by prepare_units_kernel), bit 31 set by the ring pass of a call whose gather-sum ran as the
+    // radius-3 GEMM plus ring (k_dense_ring.hip; dau_conv_gather_outlier_status reports both)
     unsigned int pad[2];
 };
+constexpr unsigned kRingTakenBit = 0x80000000u;
 
 // Pinned host mirror of a plan (written by the last workgroup of prepare_units_kernel, read by dau_conv_last_status and as
 // the next call's offset-bucket hint): the most recent completed call's status, and the sticky record of bad ones.
@@ -156,14 +161,20 @@ struct HostStatus {
 // two candidate buckets; every kernel of a set starts with guard_pass() and returns at once unless the actual max|mu|
 // falls into (lo, hi] -- exactly one set does the work, without a device->host sync (the reference blocks on a D2H copy
 // of the amax for this, dau_conv_op.cpp:229-253).  status == nullptr: unguarded.
+// A guard may also ask for the call's outlier-unit count (Status.pad[1]) to lie in [cnt_lo, cnt_hi] while max|mu| <= cnt_upto
+// (the default range means "any"): the radius-3 + ring member runs below a count limit, the members that share its offset range
+// above it.
 struct Guard {
     const Status* status;
     float lo, hi;
+    unsigned cnt_lo = 0u, cnt_hi = 0xffffffffu;
+    float cnt_upto = INFINITY;
 };
 __device__ __forceinline__ bool guard_pass(const Guard& g) {
     if (!g.status) return true;
     const float mx = __uint_as_float(g.status->max_abs_mu_bits);
-    return mx > g.lo && mx <= g.hi;
+    const unsigned cnt = g.status->pad[1] & ~kRingTakenBit;
+    return mx > g.lo && mx <= g.hi && (mx > g.cnt_upto || (cnt >= g.cnt_lo && cnt <= g.cnt_hi));
 }
 
 // One prepared unit for the gather kernels: integer displacement and the four
@@ -183,9 +194,10 @@ void launch_synth_filters(hipStream_t st, const float* sigma_dev, int k, int fla
 void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k, int flags, float* planes6);
 // k_units.hip
 // host_status (may be null): pinned host copy of the status block, written by the last workgroup to finish
+// count_ignore: the units left out of the status block's outlier count (-1: `ignore`; the input-gradient table ignores no unit)
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
-                          Status* status, HostStatus* host_status);
+                          Status* status, HostStatus* host_status, int count_ignore = -1);
 void launch_finalize_grads(hipStream_t st, const float* r4, const float* w, Shape sh, int ignore, float lr,
                            int need_mask, bool single_dim, float* dw, float* dmu1, float* dmu2, float* dsigma);
 // k_direct.hip  (DAU_ALGO_DIRECT: plain kernels, any shape)

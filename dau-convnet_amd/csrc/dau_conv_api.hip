@@ -144,7 +144,16 @@ struct BucketSet {
     // workspace holds one slab's staged copy.  Forward and dx are per-image; the parameter sums add up over the slabs.
     // Only the exact kernels and the dense gather-sum members run in slabs.
     int slab_gather = 0, slab_dot = 0;     // images per slab (the whole batch unless the budget says otherwise)
+    // DAU_FLAG_DENSE_SPLIT_OUTLIERS (bucket 4, with kSplit3): calls within +-4 whose units beyond +-3 number at most ring_limit run
+    // their gather-sum as the radius-3 GEMM plus the ring pass (k_dense_ring.hip) -- kSplit3's kernels under a guard of their own
+    bool ring = false;
+    unsigned ring_limit = 0;
+    RingConfig ringcfg[2];        // [Dir]
 };
+// The outlier-unit count up to which the radius-3 + ring member runs, in thousandths of the plan's live units: the largest tested
+// fraction at which its two gather-sum passes took at most 0.9 x what the members it stands in for take on the same inputs
+// -- 1 %: 0.79 x at 0.1 %, 0.89 x at 1 %, 1.14 x at 3 % at the north-star layer (profiles/r9_ab_dense_outliers.jsonl).
+constexpr int kRingLimitPermille = 10;
 constexpr int kBuckets[] = {4, 8, 16, 18, 20, 24, 32};
 constexpr int kNumBuckets = 7;
 
@@ -153,6 +162,8 @@ size_t gather_bytes(const BucketSet& bs, int dir) {
     size_t need = bs.has[kTiledGather] ? tiled_gather_workspace_bytes(bs.tiled[dir]) : 0;
     for (int m = kSplit2; m <= kBf16R4; ++m)
         if (bs.has[m]) need = std::max(need, kDense[m - kSplit2].workspace_bytes(bs.dense[m - kSplit2][dir]));
+    // the ring list and the fp32 partial sums of the slab, behind the radius-3 form's own workspace
+    if (bs.ring) need = std::max(need, s3::split_gather_workspace_bytes(bs.dense[kSplit3 - kSplit2][dir]) + ring_workspace_bytes(bs.ringcfg[dir]));
     return need;
 }
 size_t dot_bytes(const BucketSet& bs) {
@@ -243,6 +254,7 @@ struct Candidate {
     const BucketSet* set;
     Guard guard;
     int member;   // Member
+    bool ring = false;   // kSplit3 with the ring pass (BucketSet::ring)
 };
 
 // dau_conv_last_status has just reported the whole mirror: forget it, sticky record included.
@@ -276,7 +288,9 @@ int status_error(const dau_conv_plan* p, float mx, bool nan_seen) {
 // The members whose ARITHMETIC differs (split, bf16-dense) go first, smallest radius first, on every call, hint or no hint, so that
 // which arithmetic a call gets depends on its own offsets only.  A set that holds the radius-4 bf16 member runs it in place of
 // its exact kernels: as the static set of a one-bucket plan, as the hinted set, or guarded by (lo, 4] ahead of them.
-constexpr int kMaxCandidates = 6;
+// With the radius-3 + ring member: it shares the offsets (3, 4] with what follows it -- the radius-4 member, the hinted or the static
+// set -- and the call's outlier-unit count tells them apart: the ring member at most ring_limit, the others more (or offsets beyond 4).
+constexpr int kMaxCandidates = 7;
 int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
     const BucketSet* s0 = &p->sets[0];
@@ -297,9 +311,21 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
     }
     int n = 0;
     float lo = -1.0f;
-    auto add = [&](const BucketSet* b, int member, float hi) { out[n++] = Candidate{b, Guard{dev_status, lo, hi}, member}; lo = hi; };
-    for (int m = kFirst[kind]; m < kEnd[kind]; ++m)
-        if (goes_ahead(m) && s0->has[m]) add(s0, m, (float)kRadius[m]);
+    bool with_ring = false;
+    auto add = [&](const BucketSet* b, int member, float hi) {
+        Guard g{dev_status, lo, hi};
+        if (with_ring && lo < 4.0f) { g.cnt_lo = s0->ring_limit + 1; g.cnt_upto = 4.0f; }
+        out[n++] = Candidate{b, g, member};
+        lo = hi;
+    };
+    for (int m = kFirst[kind]; m < kEnd[kind]; ++m) {
+        if (!(goes_ahead(m) && s0->has[m])) continue;
+        add(s0, m, (float)kRadius[m]);
+        if (m == kSplit3 && s0->ring) {
+            out[n++] = Candidate{s0, Guard{dev_status, 3.0f, 4.0f, 0u, s0->ring_limit}, kSplit3, true};
+            with_ring = true;
+        }
+    }
     if (s0->has[kDense4[kind]] && hinted != s0 && s0 != top) add(s0, kDense4[kind], (float)s0->bucket);
     if (hinted && lo < (float)hinted->bucket) add(hinted, member_of(hinted), (float)hinted->bucket);
     if (n == 0) return 1;                                    // no hint, nothing dense: the static set, unguarded
@@ -328,6 +354,7 @@ int ensure_attrs(const dau_conv_plan* p) {
             else if (m == kSplitDot) split_dot_init(bs.sdot);
             else kWgrad[m - kWgradR3].init(bs.wgrad[m - kWgradR3]);
         }
+        if (bs.ring) ring_init();
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return fail(DAU_INTERNAL, "raising the dynamic-LDS limit of the bucket-%d kernels failed: %s", bs.bucket,
@@ -401,7 +428,7 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
 // One gather-sum pass: y from x (kFwd: S -> F, unit table [S][G][F]) or dx from the error (kDx: F -> S, mirrored Gaussian, table
 // [F][G][S] with negated offsets).  `ws`: the tiled workspace, or the direct path's blurred copy.
 void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float* in, float* out, const float* filters,
-                    const UnitRef* table, const Status* status, void* ws) {
+                    const UnitRef* table, Status* status, void* ws) {
     const Shape& s = p->sh;
     const int cin = dir == kFwd ? s.S : s.F, cout = dir == kFwd ? s.F : s.S;
     const bool mirrored = dir == kDx;
@@ -419,6 +446,10 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
         const BucketSet& bs = *cand[ci].set;
         const Guard& g = cand[ci].guard;
         const int m = cand[ci].member;
+        const bool ring = cand[ci].ring;
+        // the ring member's list and partial sums lie behind the radius-3 form's workspace; the list is built once per pass
+        void* ring_ws = ring ? static_cast<char*>(ws) + s3::split_gather_workspace_bytes(bs.dense[kSplit3 - kSplit2][dir]) : nullptr;
+        if (ring) ring_build_list(st, bs.ringcfg[dir], table, ring_ws, g);
         for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {                 // one slab unless the staged copy exceeds the budget
             const float* ins = slab_ptr(in, (size_t)n0 * cin * s.H * s.W, p->esize());
             float* outs = slab_ptr(out, (size_t)n0 * cout * s.H * s.W, p->esize());
@@ -434,7 +465,12 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
                 const DenseConfig& cfg = bs.dense[m - kSplit2][dir];
                 fn.prepare(st, cfg, ins, filters, mirrored, table, ws, g);
                 ProfScope prof(p, dir, st);
-                fn.run(st, cfg, outs, ws, g);
+                if (ring) {                                                // the ring pass, then the GEMM whose epilogue adds its sums
+                    ring_run(st, bs.ringcfg[dir], s3::split_gather_staged(cfg, ws), ring_ws, status, g);
+                    s3::split_gather_run_add(st, cfg, outs, ring_partial(bs.ringcfg[dir], ring_ws), ws, g);
+                } else {
+                    fn.run(st, cfg, outs, ws, g);
+                }
             }
         }
     }
@@ -495,6 +531,8 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 needs DAU_FLAG_IO_BF16 (it is the bf16 layer's gather-sum)");
     if ((flags & DAU_FLAG_DENSE_SPLIT_F16) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
+    if ((flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_OUTLIERS excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
     if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
         (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
@@ -519,6 +557,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     const bool split_forced = (flags & DAU_FLAG_DENSE_SPLIT_F16) != 0;
     const bool split_allowed = !(flags & (DAU_FLAG_NO_DENSE_SPLIT | DAU_FLAG_DENSE_BF16)) && desc->algo != DAU_ALGO_DIRECT;
     const int g_live = s.G - desc->number_units_ignore;
+    const long live_units = (long)s.S * s.F * g_live, ignored_units = (long)s.S * s.F * desc->number_units_ignore;
     for (int b : kBuckets) {
         if (b > bucket) break;
         BucketSet& bs = p->sets[p->nsets++];
@@ -537,6 +576,13 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                 DenseConfig* cfg = bs.dense[m - kSplit2];
                 bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
                             kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
+            }
+            // radius 3 + ring: where the radius-3 member is; its list holds the entries of ring_limit live units and of the ignored ones
+            // (the input-gradient table ignores no unit, and the count leaves them out)
+            bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
+            if (bs.ring) {
+                bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
+                for (int dir : {kFwd, kDx}) ring_configure(bs.dense[kSplit3 - kSplit2][dir], (long)bs.ring_limit + ignored_units, &bs.ringcfg[dir]);
             }
             return std::max(gather_bytes(bs, kFwd), gather_bytes(bs, kDx));
         };
@@ -596,6 +642,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     for (int m = 0; m < kNumMembers; ++m) ahead = ahead || (goes_ahead(m) && p->sets[0].has[m]);
     p->dynamic = (p->nsets > 1 || ahead) && !(flags & DAU_FLAG_STATIC_BUCKET) &&
                  (p->algo_fwd == DAU_ALGO_TILED || p->algo_bwd == DAU_ALGO_TILED);
+    if (!p->dynamic || p->algo_fwd != DAU_ALGO_TILED) p->sets[0].ring = false;   // no per-call selection: the flag is inert
     void* hs = nullptr;
     // portable + mapped: a plan may be used on any device, and every device's prepare_units_kernel writes the mirror
     if (hipHostMalloc(&hs, sizeof(HostStatus), hipHostMallocPortable | hipHostMallocMapped) == hipSuccess && hs) {
@@ -675,6 +722,7 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
     if (plan->dynamic && tiled_fwd)
         for (int m = kSplit2; m <= kSplit4; ++m)
             if (s0[m]) info->gather_dense_split |= 1 << kRadius[m];
+    if (plan->sets[0].ring) info->gather_dense_split |= 1 << 5;
     return DAU_OK;
 }
 
@@ -783,7 +831,7 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
         // parameters read as [F,G,S] and negated offsets (base_dau_conv_layer.cu:299-325)
         const bool fresh = !(need_mask & param_mask);     // this call has not looked at the offsets yet
         launch_prepare_units(st, w, mu1, mu2, s, 0, flags, p->bucket, true, ws.table_t, fresh ? ws.status : nullptr,
-                             p->host_status);
+                             p->host_status, p->d.number_units_ignore);
         run_gather_sum(p, st, kDx, dy, dx, ws.filters, ws.table_t, ws.status, ws.gather_dx);
     }
     DAU_HIP(hipPeekAtLastError());
@@ -828,6 +876,17 @@ int dau_conv_check_status(const dau_conv_plan* p, void* stream, const void* work
     if (max_abs_mu_out) *max_abs_mu_out = mx;
     if (h.nan_seen || mx > (float)p->bucket) clear_reported_status(p, h.max_abs_mu_bits, h.nan_seen != 0);   // reported here
     return status_error(p, mx, h.nan_seen != 0);
+}
+
+int dau_conv_gather_outlier_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* outlier_units,
+                                   int32_t* ring_taken) {
+    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    Status h;
+    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
+    if (outlier_units) *outlier_units = (int32_t)(h.pad[1] & ~kRingTakenBit);
+    if (ring_taken) *ring_taken = (h.pad[1] & kRingTakenBit) ? 1 : 0;
+    return DAU_OK;
 }
 
 int dau_conv_last_status(const dau_conv_plan* p, float* max_abs_mu_out, int32_t* valid_out) {

@@ -80,6 +80,35 @@ DAU_DECLARE_SPLIT_GATHER(s2)
 DAU_DECLARE_SPLIT_GATHER(s3)
 DAU_DECLARE_SPLIT_GATHER(s4)
 
+// Radius 3 with outliers (DAU_FLAG_DENSE_SPLIT_OUTLIERS): a call whose offsets reach into (3, 4] in few units runs the radius-3
+// GEMM on the corners inside 7 x 7 (split_densify_kernel drops the others) plus a list-driven fp32 pass over the corners on the
+// ring |tap| = 4 (k_dense_ring.hip), whose sums the GEMM's epilogue adds before the store.
+struct SplitStaged {          // the radius-3 form's staged input, for the ring pass
+    const float* sx;          // device: power-of-two scale of the staged limbs
+    const _Float16* xs;       // XS[n][chunk][limb][half][Hs][Ws][8]: staged position (r, c) = image (r - 3, c - 3)
+    int Hs, Ws, nchunk;
+};
+namespace s3 {
+SplitStaged split_gather_staged(const DenseConfig& cfg, const void* workspace);
+// split_gather_run with partial[N][Cout][H][W] (fp32) added to the sums before the store's one rounding
+void split_gather_run_add(hipStream_t st, const DenseConfig& cfg, float* out, const float* partial, void* workspace, const Guard& guard);
+}
+struct RingConfig {
+    int N, Cin, Cout, G, H, W;
+    int nchunk;               // 16-channel chunks of Cin
+    int capacity;             // entries the list holds (3 per outlier unit the member's guard admits)
+};
+void ring_configure(const DenseConfig& dense, long max_outlier_units, RingConfig* cfg);
+size_t ring_workspace_bytes(const RingConfig& cfg);
+// once per pass: the CSR list of (input channel, ring tap, summed weight) entries per (16-channel chunk, output channel) cell, from the
+// pass's unit table ([Cin][G][Cout]) by count -> exclusive scan -> fill (deterministic)
+void ring_build_list(hipStream_t st, const RingConfig& cfg, const UnitRef* table, void* workspace, const Guard& guard);
+// once per batch slab: partial[n][f][y][x] = sum over the entries e of cell (., f) of w_e * Xb[n, c_e, y + dy_e, x + dx_e], Xb from the
+// staged limbs; marks the status block (kRingTakenBit)
+void ring_run(hipStream_t st, const RingConfig& cfg, const SplitStaged& staged, void* workspace, Status* status, const Guard& guard);
+float* ring_partial(const RingConfig& cfg, void* workspace);
+void ring_init();             // once per plan and device: raises the pass's dynamic-LDS limit
+
 struct TiledDotConfig {
     Shape sh;
     int R, blur_k;

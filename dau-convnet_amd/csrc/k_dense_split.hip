@@ -478,6 +478,7 @@ struct SplitArgs {
     const _Float16* wsd;
     const SplitScales* sc;
     float* out;               // [N][Cout][H][W], f32, bf16 or f16
+    const float* partial;     // ADD instantiations: [N][Cout][H][W] fp32, added to the sums before the store's rounding
     int N, Cout, CoutP, H, W, Hs, Ws, nchunk, ncb, nrb, out_act;   // out_act: ActFormat of out
     int col0;                 // first column of this launch's blocks (a row is covered by blocks of NSUB and of NSUB - 1 tiles)
     int row0;                 // first row of this launch's row blocks (a map whose height leaves 1 .. 4 rows after its 8-row blocks
@@ -493,7 +494,8 @@ struct SplitArgs {
 // SIMD, so the SIMD's work is NSUB tiles).  For maps whose width is 1 .. 4 columns more than a multiple of eight (28 = 7 x 4: no padded
 // columns where 4 x 8 tiles pad to 32).
 // H16: out is binary16 (an instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
-template <int NSUB, int RG = 2, bool TT = false, bool H16 = false>
+// ADD (radius 3 only): the epilogue adds the fp32 partial sums of the ring pass (k_dense_ring.hip) before the one rounding of the store
+template <int NSUB, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
 __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     static_assert(!TT || RG == 2, "tall tiles: blocks of eight rows");
     constexpr int TW = TT ? 4 : 8;                           // columns of a tile
@@ -561,6 +563,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     const int prr = TT ? nn >> 2 : nn >> 3, pcc = TT ? nn & 3 : nn & 7;   // this lane's position inside a tile
     // (kernel arguments the epilogue uses, read once: inside the lambda hipcc reloads them from the argument segment at every store)
     float* const out_ptr = a.out;
+    const float* const part_ptr = a.partial;
     const bool out_bf16 = a.out_act != 0;                   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
     auto body = [&](auto ntc) __attribute__((always_inline)) {
@@ -674,7 +677,11 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
                 const int f = fb * kDFB + fw * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
                 if (f < out_c) {
                     const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
-                    if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv, false);
+                    if constexpr (ADD) {
+                        const float v = sum[j][i] * inv + part_ptr[o];
+                        if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
+                        else store_act(out_ptr, o, v, out_bf16, false);
+                    } else if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv, false);
                     else store_act(out_ptr, o, sum[j][i] * inv, out_bf16, false);
                 }
             }
@@ -699,33 +706,36 @@ template <int NSUB, int RG, bool TT>
 constexpr size_t split_lds_bytes() { return 2 * (size_t)((4 * (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB)) + 63) / 64) * 1024; }
 
 template <int NSUB, int RG, bool TT = false>
-void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16) {
+void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool add) {
     auto kern = h16 ? split_gather_kernel<NSUB, RG, TT, true> : split_gather_kernel<NSUB, RG, TT, false>;
+#if DAU_SPLIT_R == 3
+    if (add) kern = h16 ? split_gather_kernel<NSUB, RG, TT, true, true> : split_gather_kernel<NSUB, RG, TT, false, true>;
+#endif
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     constexpr size_t lds = split_lds_bytes<NSUB, RG, TT>();      // (a comma inside the launch macro's arguments would split them)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, *a);
 }
 
-void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall = false) {
+void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall = false, bool add = false) {
     if (tall) {                                              // nsub = tiles of four columns: 5 or 7 (split_geometry)
-        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16);
-        else launch_split<7, 2, true>(st, a, grid, h16);
+        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16, add);
+        else launch_split<7, 2, true>(st, a, grid, h16, add);
         return;
     }
     if (rg == 1) {
         switch (nsub) {
-            case 1: launch_split<1, 1>(st, a, grid, h16); break;
-            case 2: launch_split<2, 1>(st, a, grid, h16); break;
-            case 3: launch_split<3, 1>(st, a, grid, h16); break;
-            default: launch_split<4, 1>(st, a, grid, h16); break;
+            case 1: launch_split<1, 1>(st, a, grid, h16, add); break;
+            case 2: launch_split<2, 1>(st, a, grid, h16, add); break;
+            case 3: launch_split<3, 1>(st, a, grid, h16, add); break;
+            default: launch_split<4, 1>(st, a, grid, h16, add); break;
         }
         return;
     }
     switch (nsub) {
-        case 1: launch_split<1, 2>(st, a, grid, h16); break;
-        case 2: launch_split<2, 2>(st, a, grid, h16); break;
-        case 3: launch_split<3, 2>(st, a, grid, h16); break;
-        default: launch_split<4, 2>(st, a, grid, h16); break;
+        case 1: launch_split<1, 2>(st, a, grid, h16, add); break;
+        case 2: launch_split<2, 2>(st, a, grid, h16, add); break;
+        case 3: launch_split<3, 2>(st, a, grid, h16, add); break;
+        default: launch_split<4, 2>(st, a, grid, h16, add); break;
     }
 }
 
@@ -780,9 +790,11 @@ void split_gather_init(const DenseConfig& c) {
     const bool h16 = c.act == kActF16;
     for (int rg = 1; rg <= 2; ++rg) {
         if (!(rg == 2 ? g.nrb8 : g.nrb4)) continue;
-        if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true); continue; }
-        dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0);
-        if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0);
+        for (int add = 0; add <= (kDR == 3 ? 1 : 0); ++add) {    // (the radius-3 form also exists with the ring pass's partial sums added)
+            if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true, add != 0); continue; }
+            dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0, false, add != 0);
+            if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0, false, add != 0);
+        }
     }
     (void)hipFuncSetAttribute(stage_for(c.blur_k, c.act), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
@@ -813,15 +825,18 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     (void)hipLaunchKernel(stage_for(c.blur_k, c.act), dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(kStageThreads), args, lds, st);
 }
 
-void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* workspace, const Guard& guard) {
+namespace {
+// partial != nullptr (radius 3): the ADD instantiations
+void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard) {
     const SplitGeom g = split_geometry(c);
+    const bool add = partial != nullptr;
     const bool h16 = c.act == kActF16;
     char* ws = static_cast<char*>(workspace);
     SplitArgs a{};
     a.sc = reinterpret_cast<const SplitScales*>(ws);
     a.xs = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes);
     a.wsd = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes + g.xs_bytes);
-    a.out = out;
+    a.out = out; a.partial = partial;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
     a.out_act = c.act; a.guard = guard;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
@@ -830,17 +845,38 @@ void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* wo
         a.row0 = rg == 2 ? 0 : g.nrb8 * kDRows;
         if (rg == 2 && g.tall) {                             // one column block of tall tiles
             a.ncb = 1; a.col0 = 0;
-            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true);
+            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true, add);
             continue;
         }
         a.ncb = g.nb_a; a.col0 = 0;
-        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB));
+        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB), false, add);
         if (g.nb_b) {
             a.ncb = g.nb_b; a.col0 = g.nb_a * g.nsub_a * 8;
-            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB));
+            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB), false, add);
         }
     }
 }
+}  // namespace
+
+void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* workspace, const Guard& guard) {
+    run_split(st, c, out, nullptr, workspace, guard);
+}
+
+#if DAU_SPLIT_R == 3
+void split_gather_run_add(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard) {
+    run_split(st, c, out, partial, workspace, guard);
+}
+
+SplitStaged split_gather_staged(const DenseConfig& c, const void* workspace) {
+    const SplitGeom g = split_geometry(c);
+    const char* ws = static_cast<const char*>(workspace);
+    SplitStaged s{};
+    s.sx = &reinterpret_cast<const SplitScales*>(ws)->sx;
+    s.xs = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes);
+    s.Hs = g.Hs; s.Ws = g.Ws; s.nchunk = g.nchunk;
+    return s;
+}
+#endif
 
 }  // namespace DAU_SPLIT_NS
 }  // namespace dau

@@ -26,9 +26,9 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
                                      const float* __restrict__ mu2, int S, int G, int F, int ignore,
                                      int flags, int bucket, int transposed_negated, int weight_mode,
                                      UnitRef* __restrict__ table, Status* __restrict__ status,
-                                     HostStatus* __restrict__ host_status) {
+                                     HostStatus* __restrict__ host_status, int count_ignore) {
     const long units = (long)S * G * F;
-    unsigned int local_max = 0, local_nan = 0;
+    unsigned int local_max = 0, local_nan = 0, local_out = 0;   // local_out: live units beyond +-3 (Status.pad[1])
     // the loop index is the DESTINATION slot, so that the 24-byte table entries are written in order; in the transposed
     // case the three parameter reads are the strided side instead (12 B per unit, served from L2)
     for (long dst = blockIdx.x * (long)blockDim.x + threadIdx.x; dst < units; dst += (long)gridDim.x * blockDim.x) {
@@ -41,6 +41,7 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
         if (is_nan) { local_nan = 1; m1 = 0.0f; m2 = 0.0f; }
         const float amax = fmaxf(fabsf(m1), fabsf(m2));
         local_max = max(local_max, __float_as_uint(amax));
+        local_out += (amax > 3.0f && g < G - count_ignore) ? 1u : 0u;
         // safety clamp: a displacement beyond the bucket would read outside the staged tile
         m1 = fminf(fmaxf(m1, -(float)bucket), (float)bucket);
         m2 = fminf(fmaxf(m2, -(float)bucket), (float)bucket);
@@ -57,18 +58,20 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
     }
     if (status) {
         // one atomic per workgroup: thousands of same-address atomics serialise in L2 and were most of this kernel's time
-        __shared__ unsigned int smax[16], snan[16];
+        __shared__ unsigned int smax[16], snan[16], sout[16];
         for (int m = 32; m >= 1; m >>= 1) {
             local_max = max(local_max, (unsigned int)__shfl_xor((int)local_max, m));
             local_nan |= (unsigned int)__shfl_xor((int)local_nan, m);
+            local_out += (unsigned int)__shfl_xor((int)local_out, m);
         }
         const int wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-        if ((threadIdx.x & 63) == 0) { smax[wave] = local_max; snan[wave] = local_nan; }
+        if ((threadIdx.x & 63) == 0) { smax[wave] = local_max; snan[wave] = local_nan; sout[wave] = local_out; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            for (int i = 1; i < nw; ++i) { local_max = max(local_max, smax[i]); local_nan |= snan[i]; }
+            for (int i = 1; i < nw; ++i) { local_max = max(local_max, smax[i]); local_nan |= snan[i]; local_out += sout[i]; }
             atomicMax(&status->max_abs_mu_bits, local_max);
             if (local_nan) atomicOr(&status->nan_seen, 1u);
+            if (local_out) atomicAdd(&status->pad[1], local_out);
             if (host_status) {
                 // the workgroup that finishes last mirrors the result into pinned host memory (read without a sync by
                 // dau_conv_last_status and as the next call's offset-bucket hint); pad[0] counts finished workgroups
@@ -92,13 +95,13 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
 
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
-                          Status* status, HostStatus* host_status) {
+                          Status* status, HostStatus* host_status, int count_ignore) {
     const long units = (long)sh.S * sh.G * sh.F;
     const int block = 256;
     const int grid = (int)((units + block - 1) / block < 512 ? (units + block - 1) / block : 512);
     hipLaunchKernelGGL(prepare_units_kernel, dim3(grid), dim3(block), 0, st, w, mu1, mu2, sh.S, sh.G, sh.F,
                        ignore, flags, bucket, transposed_negated ? 1 : 0, w == nullptr ? 1 : 0, table, status,
-                       status ? host_status : nullptr);
+                       status ? host_status : nullptr, count_ignore < 0 ? ignore : count_ignore);
 }
 
 // dw = r0 ; dmu1 = w*r1*lr ; dmu2 = w*r2*lr ; dsigma = w*r3 ; ignored units -> 0 ; NaN in dmu -> 0.

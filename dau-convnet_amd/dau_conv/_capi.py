@@ -26,6 +26,7 @@ FLAG_DENSE_WGRAD_NEVER = 1 << 7    # with FLAG_DENSE_BF16: parameter gradients a
 FLAG_DENSE_WGRAD_ALWAYS = 1 << 8   # with FLAG_DENSE_BF16: dense parameter gradients from one unit per channel on (default: three)
 FLAG_DENSE_SPLIT_F16 = 1 << 9      # gather-sum passes of calls with |mu| <= 2 / 3 / 4 as a densified two-limb f16 MFMA GEMM at fp32 accuracy, whatever G
 FLAG_NO_DENSE_SPLIT = 1 << 10      # never (default: the radii that pay for the plan's unit count)
+FLAG_DENSE_SPLIT_OUTLIERS = 1 << 12   # opt-in: calls within +-4 with few units beyond +-3 run the radius-3 two-limb GEMM plus a sparse ring pass
 FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernels and arithmetic, parameters and their gradients float32
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED = 0, 1, 2
@@ -85,6 +86,8 @@ def _load():
     lib.dau_conv_backward_param_sums.argtypes = [vp, vp] + [fp] * 6 + [vp, ctypes.c_size_t]
     lib.dau_conv_finalize_param_grads.argtypes = [vp, vp] + [fp] * 6 + [ctypes.c_int]
     lib.dau_conv_check_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
+    if hasattr(lib, "dau_conv_gather_outlier_status"):   # (an earlier build of the same ABI, loaded through DAU_CONV_LIB for an A/B run, lacks the query)
+        lib.dau_conv_gather_outlier_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     lib.dau_conv_last_status.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
     lib.dau_conv_filters.argtypes = [vp, vp, fp, fp]
     lib.dau_conv_unit_table.argtypes = [vp, vp, fp, fp, fp, ctypes.c_int, vp]
@@ -271,6 +274,15 @@ class Plan(object):
         with torch.cuda.device(dev):
             _check(lib.dau_conv_check_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(mx)))
         return mx.value
+
+    def outlier_status(self):
+        """Sync; -> (outlier_units, ring_taken) of the last call: the live units with max(|mu1|,|mu2|) > 3, and whether one of its
+        gather-sum passes ran as the radius-3 GEMM plus the ring pass (FLAG_DENSE_SPLIT_OUTLIERS) rather than another member."""
+        units, taken = ctypes.c_int32(), ctypes.c_int32()
+        dev = self._last_ws.device
+        with torch.cuda.device(dev):
+            _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
+        return units.value, bool(taken.value)
 
     def last_status(self):
         """No sync: max(|mu|) seen by the most recent COMPLETED call of this plan (None before any has completed);

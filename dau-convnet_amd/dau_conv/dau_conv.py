@@ -78,6 +78,9 @@ def _get_plan(x, w, settings):
         flags |= _capi.FLAG_DENSE_SPLIT_F16
     elif settings["dense_split"] is False:
         flags |= _capi.FLAG_NO_DENSE_SPLIT
+    # opt-in: calls within +-4 with few units beyond +-3 keep the radius-3 dense GEMM, plus a ring pass over those units' outer taps
+    if settings["dense_outliers"] and not (flags & (_capi.FLAG_DENSE_BF16 | _capi.FLAG_NO_DENSE_SPLIT)):
+        flags |= _capi.FLAG_DENSE_SPLIT_OUTLIERS
     key = (N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], flags, settings["algo"],
            _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"]), x.device.index)
     plan = _PLANS.get(key)
@@ -131,7 +134,8 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
               sigma_iteration_step=1, component_border_bound=1.0, sigma_lower_bound=0.3, merge_iteration_step=0,
               merge_threshold=1, unit_testing=False, mu_learning_rate_factor=1.0, single_dim_kernel=False,
               forbid_positive_dim1=False, use_interpolation=True, sigma_hint=None, check_offsets="async",
-              algo=_capi.ALGO_AUTO, dense_bf16=False, dense_split=None, process_group=None, grad_reduce="mean", name=None):
+              algo=_capi.ALGO_AUTO, dense_bf16=False, dense_split=None, process_group=None, grad_reduce="mean", name=None,
+              dense_outliers=False):
     if not unit_normalization or square_unit_normalization:
         raise _capi.InvalidArgumentError("only unit_normalization=True, square_unit_normalization=False is implemented")
     if sigma_hint is None:
@@ -146,8 +150,8 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
                 single_dim_kernel=bool(single_dim_kernel), forbid_positive_dim1=bool(forbid_positive_dim1),
                 use_interpolation=bool(use_interpolation), sigma_hint=float(sigma_hint),
                 check_offsets=mode, algo=int(algo), dense_bf16=bool(dense_bf16),
-                dense_split=(None if dense_split is None else bool(dense_split)), process_group=process_group,
-                grad_reduce=grad_reduce)
+                dense_split=(None if dense_split is None else bool(dense_split)), dense_outliers=bool(dense_outliers),
+                process_group=process_group, grad_reduce=grad_reduce)
 
 
 def _c(t):
@@ -343,7 +347,7 @@ class _DAUConvolution2d(object):
                  num_dau_units_ignore=0, mu_learning_rate_factor=500, dau_unit_border_bound=0.01,
                  dau_unit_sigma_bound=0.01, dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, check_offsets="async", algo=_capi.ALGO_AUTO,
-                 dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None):
+                 dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None, dense_outliers=False):
         if len(input_shape) != 4:
             raise ValueError("Only two dimensional DAUConv supported (rank-4 NCHW input).")
         if data_format is None or data_format == "NHWC":
@@ -371,6 +375,7 @@ class _DAUConvolution2d(object):
         self.algo = algo
         self.dense_bf16 = dense_bf16
         self.dense_split = dense_split
+        self.dense_outliers = dense_outliers
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
@@ -389,8 +394,8 @@ class _DAUConvolution2d(object):
                         forbid_positive_dim1=self.dau_aggregation_forbid_positive_dim1,
                         use_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing,
                         sigma_hint=sigma_hint, check_offsets=self.check_offsets, algo=self.algo,
-                        dense_bf16=self.dense_bf16, dense_split=self.dense_split, process_group=self.process_group,
-                        grad_reduce=self.grad_reduce, name=self.name)
+                        dense_bf16=self.dense_bf16, dense_split=self.dense_split, dense_outliers=self.dense_outliers,
+                        process_group=self.process_group, grad_reduce=self.grad_reduce, name=self.name)
 
 
 class DAUConv2d(nn.Module):
@@ -403,7 +408,10 @@ class DAUConv2d(nn.Module):
     False: never read the result back.  `dense_split` (None: the library's choice, True: always, False: never): calls whose
     offsets lie within +-2 / +-3 / +-4 run their two gather-sum passes as a densified GEMM on the f16 matrix cores with both
     operands split into two binary16 limbs -- fp32 accuracy (the exact kernels' parity bar), about 1.7x faster at four units per
-    channel pair; by default a plan holds the radii that pay for its unit count.  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
+    channel pair; by default a plan holds the radii that pay for its unit count.  `dense_outliers=True` (opt-in): a call whose
+    offsets reach beyond +-3 (up to +-4) in few units -- a trained layer's offsets drift to the +-3.99 clip of kernel 9 -- keeps the
+    radius-3 GEMM and gathers those units' outer taps in a sparse pass of its own, instead of moving the whole pass to the 9 x 9
+    member; same accuracy, no effect on calls within +-3 or with many such units.  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
     their forward and input-gradient passes as a densified bf16 matrix-core GEMM (DAU_FLAG_DENSE_BF16: taps and blurred
     activations rounded to bf16, fp32 sums) and, from three units per channel on, their
     parameter gradients as dense cross-correlations on the same cores -- the whole step about 2x faster than the exact
@@ -432,7 +440,8 @@ class DAUConv2d(nn.Module):
                  bias_constraint=None, trainable=True, mu_learning_rate_factor=500, dau_unit_border_bound=0.01,
                  dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False, dau_sigma_trainable=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, in_channels=None, check_offsets="async",
-                 algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None, **kwargs):
+                 algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None,
+                 dense_outliers=False, **kwargs):
         super(DAUConv2d, self).__init__()
         self.rank = 2
         self.filters = int(filters)
@@ -483,6 +492,7 @@ class DAUConv2d(nn.Module):
         self.algo = algo
         self.dense_bf16 = dense_bf16
         self.dense_split = dense_split
+        self.dense_outliers = dense_outliers
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         # odd number of units: add one dummy (zero weight, ignored) unit (dau_conv.py:317-329)
@@ -570,7 +580,8 @@ class DAUConv2d(nn.Module):
             dau_aggregation_forbid_positive_dim1=self.dau_aggregation_forbid_positive_dim1,
             dau_mu_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing, data_format="NCHW",
             name=self.name, check_offsets=self.check_offsets, algo=self.algo, dense_bf16=self.dense_bf16,
-            process_group=self.process_group, grad_reduce=self.grad_reduce, dense_split=self.dense_split)
+            process_group=self.process_group, grad_reduce=self.grad_reduce, dense_split=self.dense_split,
+            dense_outliers=self.dense_outliers)
         self.built = True
 
     def _var(self, key):
@@ -689,7 +700,7 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                sigma_initializer=None, sigma_regularizer=None, sigma_constraint=None, biases_initializer=zeros_initializer(),
                biases_regularizer=None, biases_constraint=None, dau_unit_border_bound=0.01, dau_sigma_trainable=False,
                dau_mu_interpolation=True, reuse=None, variables_collections=None, outputs_collections=None,
-               trainable=True, scope=None):
+               trainable=True, scope=None, dense_outliers=False):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -704,7 +715,8 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
         bias_regularizer=biases_regularizer, weight_constraint=weights_constraint, mu1_constraint=mu1_constraint,
         mu2_constraint=mu2_constraint, sigma_constraint=sigma_constraint, bias_constraint=biases_constraint,
         dau_unit_border_bound=dau_unit_border_bound, dau_sigma_trainable=dau_sigma_trainable,
-        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name))
+        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
+        dense_outliers=dense_outliers))
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))
@@ -721,7 +733,8 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                mu1_constraint=None, sigma_initializer=None, sigma_regularizer=None, sigma_constraint=None,
                biases_initializer=zeros_initializer(), biases_regularizer=None, dau_unit_border_bound=0.01,
                dau_sigma_trainable=False, dau_aggregation_forbid_positive_dim1=False, dau_mu_interpolation=True,
-               reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None):
+               reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
+               dense_outliers=False):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -736,7 +749,8 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
         mu1_constraint=mu1_constraint, sigma_constraint=sigma_constraint, dau_unit_border_bound=dau_unit_border_bound,
         dau_sigma_trainable=dau_sigma_trainable,
         dau_aggregation_forbid_positive_dim1=dau_aggregation_forbid_positive_dim1,
-        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name))
+        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
+        dense_outliers=dense_outliers))
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))

@@ -141,6 +141,16 @@ enum {
                                                input; results are stored rounded to nearest even (f16 subnormals kept, beyond
                                                65504 +-inf, a NaN stays a NaN), once per offset-window pass.  Needs the tiled
                                                kernels; excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and its qualifiers.   */
+    DAU_FLAG_DENSE_SPLIT_OUTLIERS = 1 << 12, /* opt-in: a call whose offsets reach into (3, 4] in FEW units keeps the radius-3 two-limb
+                                               GEMM for its gather-sum passes (y, dx).  The bilinear corners that land inside 7x7 stay
+                                               in the dense kernel; the corners on the ring |tap| = 4 (at most three per such unit)
+                                               are gathered by a list-driven fp32 pass of their own (k_dense_ring.hip) whose sums join
+                                               the GEMM's before the one rounding of the store.  The device takes this member when
+                                               max|mu| lies in (3, 4] and the units beyond +-3 are at most a fraction of the plan's
+                                               live units that is fixed at plan creation; every other call runs what it runs without
+                                               the flag.  Holds where the plan holds the radius-3 member (DAU_FLAG_DENSE_SPLIT_F16
+                                               forces that); inert elsewhere; excludes DAU_FLAG_NO_DENSE_SPLIT and DAU_FLAG_DENSE_BF16.
+                                               The parameter gradients are not affected.                                     */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
@@ -209,7 +219,8 @@ typedef struct dau_conv_plan_info {
     int32_t dense_bf16_radius3; /* DAU_FLAG_DENSE_BF16 plans: 1 if calls within +-3 take the 7x7 members (gather-sum), 2 if the parameter
                                    gradients do too (49 displacements); 0: the 9x9 members only */
     int32_t gather_dense_split; /* bit r (r = 2, 3, 4): calls whose offsets lie within +-r can run their gather-sum passes as the
-                                   two-limb f16 GEMM of that radius (0: never) */
+                                   two-limb f16 GEMM of that radius (0: never); bit 5: calls within +-4 with few units beyond +-3
+                                   can run theirs as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS) */
 } dau_conv_plan_info;
 
 DAU_API int dau_conv_abi_version(void);
@@ -254,6 +265,12 @@ DAU_API int dau_conv_finalize_param_grads(const dau_conv_plan *plan, void *strea
  * max_abs_mu_out (may be NULL) receives max(|mu1|,|mu2|). */
 DAU_API int dau_conv_check_status(const dau_conv_plan *plan, void *stream, const void *workspace,
                           float *max_abs_mu_out);
+
+/* Waits for `stream`, then reports of the last call that used `workspace`: outlier_units = the live units (those not among the
+ * number_units_ignore last of their channel pair) with max(|mu1|,|mu2|) > 3; ring_taken = 1 if a gather-sum pass of that call ran
+ * as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS), 0 if another member did the work.  Either may be NULL. */
+DAU_API int dau_conv_gather_outlier_status(const dau_conv_plan *plan, void *stream, const void *workspace,
+                                   int32_t *outlier_units, int32_t *ring_taken);
 
 /* The same report without waiting, from pinned host memory.  A NaN or an out-of-range offset seen by ANY completed call of
  * this plan since the last report is STICKY: it stays until this function (or dau_conv_check_status) has returned it once,
