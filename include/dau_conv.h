@@ -39,6 +39,9 @@
  * with DAU_FLAG_IO_BF16 / DAU_FLAG_IO_F16, bfloat16 / binary16 storage of x, y, dy, dx -- arithmetic stays fp32);
  * parameters and their gradients [1,S,G,F] contiguous float32 (f fastest); sigma is a
  * full [1,S,G,F] tensor whose element 0 is used (base_dau_conv_layer.hpp:266-275).
+ * Alignment: every pointer need only be aligned to its element type (4 bytes for float32, 2 bytes for the 16-bit activation
+ * formats) -- the kernels take their wider loads only where a base allows them, with the same results bit for bit -- so a
+ * contiguous slice of a larger tensor can be passed as it is; the workspace wants the 256 bytes a hipMalloc gives.
  *
  * Ownership: the caller owns every buffer, including one workspace per in-flight call.
  * A plan's configuration is immutable after creation, so concurrent calls on different
