@@ -84,7 +84,7 @@ DAU_DECLARE_SPLIT_GATHER(s4)
 // GEMM on the corners inside 7 x 7 (split_densify_kernel drops the others) plus a list-driven fp32 pass over the corners on the
 // ring |tap| = 4 (k_dense_ring.hip), whose sums the GEMM's epilogue adds before the store.
 struct SplitStaged {          // the radius-3 form's staged input, for the ring pass
-    const float* sx;          // device: power-of-two scale of the staged limbs
+    const float* sx;          // device, [N]: power-of-two scale of each image's staged limbs
     const _Float16* xs;       // XS[n][chunk][limb][half][Hs][Ws][8]: staged position (r, c) = image (r - 3, c - 3)
     int Hs, Ws, nchunk;
 };

@@ -164,7 +164,7 @@ __global__ void __launch_bounds__(kPassThreads) ring_pass_kernel(const RingPassA
     const int n = t / a.nrb;
     const int y0 = rb * kRows, x0 = cb * kCols, f0 = fb * kFB;
     const int nf = a.Cout - f0 < kFB ? a.Cout - f0 : kFB;
-    const float inv_sx = 1.0f / *a.sx;                       // a power of two
+    const float inv_sx = 1.0f / a.sx[n];                     // this image's scale: a power of two
     const long splane = (long)a.Hs * a.Ws;
     const unsigned lane_base = (unsigned)((wave * kTP + lane) * 4);
     const char* tile_b = reinterpret_cast<const char*>(tile);

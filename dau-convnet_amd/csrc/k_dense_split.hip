@@ -15,13 +15,16 @@
 // (include/dau_conv/dau_conv_impl/dau_conv_forward_core.hpp:804-1605, 1607-1732, 1858-2215) and caffe_gpu_convolve2
 // (src/dau_conv/util/convolve.cu:48-131), for calls whose offsets lie within +-R (the call's device guard decides).
 //
-// Power-of-two scales (binary16 has five exponent bits): sx brings max|x| to [2^13, 2^14), sw the bound G * max|w| of a dense
-// tap likewise; both come from a two-launch max reduction over the pass's input and its unit table, the epilogue multiplies
-// by 1 / (sx * sw).  Scaling by a power of two is exact, so the only effect is that the limbs cannot overflow and that values
-// down to 2^-17 of the maximum keep all 22 bits (smaller ones: an absolute error below 2^-39 of the maximum).
+// Power-of-two scales (binary16 has five exponent bits): sx[n] brings the largest finite |x| of IMAGE n to [2^13, 2^14), sw the
+// bound G * max|w| of a dense tap (finite units) likewise; both come from a two-launch max reduction over the pass's input and its
+// unit table, the epilogue multiplies by 1 / sw and then by 1 / sx[n].  Scaling by a power of two is exact, so the only effect is
+// that the limbs cannot overflow and that values down to 2^-17 of their image's maximum keep all 22 bits (smaller ones: an
+// absolute error below 2^-39 of that maximum).  One scale per image, not per call: y[n] (dx[n]) is a function of image n and the
+// parameters alone -- the same bits whatever its batch-mates hold and however the batch is cut into slabs -- and a non-finite
+// element (left out of the maxima; it passes through the arithmetic) reaches only the outputs of its own image that its taps touch.
 //
 // Layouts (HBM, all in the pass's workspace):
-//   header      SplitScales (max bits, scales)
+//   header      SplitScales (sw, 1 / sw), sx[N], 1 / sx[N], the partial maxima of the reduction
 //   XS[n][chunk][limb][half][Hs][Ws][8]  f16: Gaussian-blurred, scaled input; 16 input channels per chunk as two halves of 8
 //       (one 16-byte unit per position = the B fragment of one lane), limb 0 = hi, 1 = lo; staged position (r, c) = image
 //       (r-R, c-R), zero outside the image.
@@ -85,13 +88,22 @@ constexpr int kFlushRows = DAU_SPLIT_FLUSH_ROWS;
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// device-side scales of one pass (head of its workspace)
+// device-side scales of one pass (head of its workspace): this block, then sx[N] and 1 / sx[N] -- one power-of-two scale per IMAGE,
+// so that an image's limbs (and with them its outputs) depend on no other image of the batch -- then the partial maxima
 struct SplitScales {
-    unsigned max_x_bits, max_w_bits;    // float bits of max|input| and of max over the units of |w| (sum of the four tap weights)
-    float sx, sw, inv;                  // power-of-two scales of the activations / the dense taps, 1 / (sx * sw)
-    float pad[3];
+    unsigned max_w_bits;                // float bits of the max over the finite units of |w| (sum of the four tap weights)
+    float sw, inv_sw;                   // power-of-two scale of the dense taps and 1 / sw
+    float pad[5];
 };
-constexpr int kPartials = 1024;         // workgroups of the max reduction
+__host__ __device__ __forceinline__ const float* scales_sx(const SplitScales* sc) { return reinterpret_cast<const float*>(sc + 1); }
+__host__ __device__ __forceinline__ const float* scales_inv_sx(const SplitScales* sc, int N) { return reinterpret_cast<const float*>(sc + 1) + N; }
+constexpr int kPartials = 1024;         // workgroups of the max reduction (at least one per image: kPartials + N bounds them)
+// workgroups that share one image's maximum: all of kPartials over the batch, no more than the image has 1024-element pieces
+inline int absmax_groups_per_image(int N, long per) {
+    const long fit = std::max(1, kPartials / N), want = (per / 4 + 255) / 256 + 1;
+    return (int)std::min(fit, want);
+}
+inline size_t scales_bytes(int N) { return sizeof(SplitScales) + (size_t)2 * N * sizeof(float); }
 
 constexpr int kMaxSub = 4;              // 8-pixel tiles per column block (two accumulators per tile: see the header)
 struct SplitGeom {
@@ -132,7 +144,7 @@ SplitGeom split_geometry(const DenseConfig& c) {
     g.Ws = g.sub * 8 + kDSpan;
     g.nchunk = (c.Cin + 15) / 16;
     g.CoutP = (int)round_up(c.Cout, kDFB);
-    g.hdr_bytes = round_up(sizeof(SplitScales) + (size_t)2 * kPartials * sizeof(unsigned), 256);
+    g.hdr_bytes = round_up(scales_bytes(c.N) + (size_t)2 * (kPartials + c.N) * sizeof(unsigned), 256);
     // + 4 KiB: the window copy reads whole LDS-pitch rows, i.e. a few units past the last plane's last row
     g.xs_bytes = round_up((size_t)c.N * g.nchunk * 4 * g.Hs * g.Ws * 16 + 4096, 256);
     g.ws_bytes = round_up(((size_t)g.nchunk * kDTaps + 8) * 2 * g.CoutP * 32, 256);   // + look-ahead taps of the A stream
@@ -154,43 +166,66 @@ constexpr int lds_pitch_narrow(int ntiles) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// scales: max|input| and max|w| (two launches: per-workgroup maxima, then one workgroup reduces them and derives the scales)
+// scales: max|input| per image and max|w|, finite values only (two launches: per-workgroup maxima, then one workgroup per image --
+// and one for the units -- reduces them and derives the scales)
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restrict__ in, long count, int act, const UnitRef* __restrict__ table,
-                                                           long units, unsigned* __restrict__ partial, const Guard guard) {
+// float bits of |v| for the maximum over the FINITE values: Inf and NaN (0x7f800000 and above) count as 0
+__device__ __forceinline__ unsigned finite_bits(unsigned b) { return b < 0x7f800000u ? b : 0u; }
+
+// elements in front of the first one whose address is a multiple of `vec_bytes` (all of them where the base is not even a
+// multiple of the element size: scalar loads only)
+__device__ __forceinline__ long absmax_head(const void* p, long per, int elem_bytes, int vec_bytes) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (a % elem_bytes) return per;
+    const long head = (long)((vec_bytes - a % vec_bytes) % vec_bytes) / elem_bytes;
+    return head < per ? head : per;
+}
+
+// Workgroup (image n, share j of gpi): the maximum of the image's finite |values|.  An image's own base is in general not
+// aligned to a vector load (S * H * W = 7 * 9 * 6 elements): `head` scalar elements, whole four-element pieces from the first
+// aligned address, the tail scalar again -- a maximum does not depend on which load fetched an element.  Every workgroup also
+// takes its share of the unit table.
+__global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restrict__ in, long per, int gpi, int act, const UnitRef* __restrict__ table,
+                                                           long units, unsigned* __restrict__ partial, int cap, const Guard guard) {
     if (!guard_pass(guard)) return;
     unsigned mx = 0, mw = 0;
-    const long stride = (long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    const int n = blockIdx.x / gpi, j = blockIdx.x - n * gpi;
+    const long stride = (long)gpi * blockDim.x, t0 = j * (long)blockDim.x + threadIdx.x;
     if (act == kActF16) {
         // the widened values' bits, so that the maximum (and the scales) are those of the same input given as fp32
-        auto wide = [](unsigned h) { return __float_as_uint(f16_bits_to_float(h)) & 0x7fffffffu; };
-        const uint2* p = reinterpret_cast<const uint2*>(in);          // four f16 per load
-        const long n4 = reinterpret_cast<uintptr_t>(in) % 8 == 0 ? count / 4 : 0;
+        auto wide = [](unsigned h) { return finite_bits(__float_as_uint(f16_bits_to_float(h)) & 0x7fffffffu); };
+        const unsigned short* e = reinterpret_cast<const unsigned short*>(in) + n * per;
+        const long head = absmax_head(e, per, 2, 8), n4 = (per - head) / 4;
+        const uint2* p = reinterpret_cast<const uint2*>(e + head);    // four f16 per load
         for (long i = t0; i < n4; i += stride) {
             const uint2 v = p[i];
             mx = max(mx, max(max(wide(v.x & 0xffffu), wide(v.x >> 16)), max(wide(v.y & 0xffffu), wide(v.y >> 16))));
         }
-        for (long i = n4 * 4 + t0; i < count; i += stride) mx = max(mx, wide(reinterpret_cast<const unsigned short*>(in)[i]));
+        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, wide(e[i < head ? i : i + n4 * 4]));
     } else if (act == kActBF16) {
-        const uint2* p = reinterpret_cast<const uint2*>(in);          // four bf16 per load
-        const long n4 = reinterpret_cast<uintptr_t>(in) % 8 == 0 ? count / 4 : 0;
+        const unsigned short* e = reinterpret_cast<const unsigned short*>(in) + n * per;
+        const long head = absmax_head(e, per, 2, 8), n4 = (per - head) / 4;
+        const uint2* p = reinterpret_cast<const uint2*>(e + head);    // four bf16 per load
         for (long i = t0; i < n4; i += stride) {
             const uint2 v = p[i];
-            mx = max(mx, max(max((v.x << 16) & 0x7fffffffu, v.x & 0x7fff0000u), max((v.y << 16) & 0x7fffffffu, v.y & 0x7fff0000u)));
+            mx = max(mx, max(max(finite_bits((v.x << 16) & 0x7fffffffu), finite_bits(v.x & 0x7fff0000u)),
+                             max(finite_bits((v.y << 16) & 0x7fffffffu), finite_bits(v.y & 0x7fff0000u))));
         }
-        for (long i = n4 * 4 + t0; i < count; i += stride) mx = max(mx, ((unsigned)reinterpret_cast<const unsigned short*>(in)[i] << 16) & 0x7fffffffu);
+        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(((unsigned)e[i < head ? i : i + n4 * 4] << 16) & 0x7fffffffu));
     } else {
-        const uint4* p = reinterpret_cast<const uint4*>(in);
-        const long n4 = reinterpret_cast<uintptr_t>(in) % 16 == 0 ? count / 4 : 0;
+        const float* e = in + n * per;
+        const long head = absmax_head(e, per, 4, 16), n4 = (per - head) / 4;
+        const uint4* p = reinterpret_cast<const uint4*>(e + head);
         for (long i = t0; i < n4; i += stride) {
             const uint4 v = p[i];
-            mx = max(mx, max(max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), max(v.z & 0x7fffffffu, v.w & 0x7fffffffu)));
+            mx = max(mx, max(max(finite_bits(v.x & 0x7fffffffu), finite_bits(v.y & 0x7fffffffu)),
+                             max(finite_bits(v.z & 0x7fffffffu), finite_bits(v.w & 0x7fffffffu))));
         }
-        for (long i = n4 * 4 + t0; i < count; i += stride) mx = max(mx, __float_as_uint(in[i]) & 0x7fffffffu);
+        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(__float_as_uint(e[i < head ? i : i + n4 * 4]) & 0x7fffffffu));
     }
-    for (long u = t0; u < units; u += stride) {
+    for (long u = blockIdx.x * (long)blockDim.x + threadIdx.x; u < units; u += (long)gridDim.x * blockDim.x) {
         const UnitRef r = table[u];
-        mw = max(mw, __float_as_uint(fabsf(r.w00) + fabsf(r.w01) + fabsf(r.w10) + fabsf(r.w11)));
+        mw = max(mw, finite_bits(__float_as_uint(fabsf(r.w00) + fabsf(r.w01) + fabsf(r.w10) + fabsf(r.w11))));
     }
     __shared__ unsigned sx[4], sw[4];
     for (int m = 32; m >= 1; m >>= 1) { mx = max(mx, (unsigned)__shfl_xor((int)mx, m)); mw = max(mw, (unsigned)__shfl_xor((int)mw, m)); }
@@ -198,11 +233,12 @@ __global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restri
     __syncthreads();
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = max(max(sx[0], sx[1]), max(sx[2], sx[3]));
-        partial[kPartials + blockIdx.x] = max(max(sw[0], sw[1]), max(sw[2], sw[3]));
+        partial[cap + blockIdx.x] = max(max(sw[0], sw[1]), max(sw[2], sw[3]));
     }
 }
 
-// 2^(13 - floor(log2 m)) for a finite m > 0 (m * scale in [2^13, 2^14)), 1 otherwise (zeros; Inf / NaN pass through the arithmetic)
+// 2^(13 - floor(log2 m)) for a finite m > 0 (m * scale in [2^13, 2^14)), 1 otherwise (an image or a table without a finite
+// non-zero value; Inf / NaN pass through the arithmetic)
 __device__ __forceinline__ float limb_scale(float m) {
     if (!(m > 0.0f) || !(m < INFINITY)) return 1.0f;
     int e = ilogbf(m);
@@ -211,22 +247,29 @@ __device__ __forceinline__ float limb_scale(float m) {
     return ldexpf(1.0f, e);
 }
 
-__global__ void __launch_bounds__(256) split_scales_kernel(const unsigned* __restrict__ partial, int nparts, int G, SplitScales* __restrict__ out,
-                                                           const Guard guard) {
+// workgroup n < N: sx[n], 1 / sx[n] from the image's gpi partial maxima; workgroup N: sw, 1 / sw from all the workgroups' unit maxima
+__global__ void __launch_bounds__(256) split_scales_kernel(const unsigned* __restrict__ partial, int N, int gpi, int cap, int G,
+                                                           SplitScales* __restrict__ out, const Guard guard) {
     if (!guard_pass(guard)) return;
-    unsigned mx = 0, mw = 0;
-    for (int i = threadIdx.x; i < nparts; i += 256) { mx = max(mx, partial[i]); mw = max(mw, partial[kPartials + i]); }
-    __shared__ unsigned sx[4], sw[4];
-    for (int m = 32; m >= 1; m >>= 1) { mx = max(mx, (unsigned)__shfl_xor((int)mx, m)); mw = max(mw, (unsigned)__shfl_xor((int)mw, m)); }
-    if ((threadIdx.x & 63) == 0) { sx[threadIdx.x >> 6] = mx; sw[threadIdx.x >> 6] = mw; }
+    const int n = blockIdx.x;
+    const unsigned* src = n < N ? partial + (long)n * gpi : partial + cap;
+    const int cnt = n < N ? gpi : N * gpi;
+    unsigned m = 0;
+    for (int i = threadIdx.x; i < cnt; i += 256) m = max(m, src[i]);
+    __shared__ unsigned sm[4];
+    for (int k = 32; k >= 1; k >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, k));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
-        mx = max(max(sx[0], sx[1]), max(sx[2], sx[3]));
-        mw = max(max(sw[0], sw[1]), max(sw[2], sw[3]));
-        const float ax = __uint_as_float(mx), aw = __uint_as_float(mw);
-        const float s_x = limb_scale(ax), s_w = limb_scale(aw * (float)G);    // a dense tap sums at most G units
-        out->max_x_bits = mx; out->max_w_bits = mw;
-        out->sx = s_x; out->sw = s_w; out->inv = (1.0f / s_x) * (1.0f / s_w);
+        m = max(max(sm[0], sm[1]), max(sm[2], sm[3]));
+        float* sx = reinterpret_cast<float*>(out + 1);
+        if (n < N) {
+            const float s = limb_scale(__uint_as_float(m));
+            sx[n] = s; sx[N + n] = 1.0f / s;
+        } else {
+            const float s = limb_scale(__uint_as_float(m) * (float)G);    // a dense tap sums at most G units
+            out->max_w_bits = m; out->sw = s; out->inv_sw = 1.0f / s;
+        }
     }
 }
 
@@ -465,7 +508,7 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
     const int SR = (y1 - y0 + nw - 1) / nw;
     const int ya = y0 + wave * SR, yb = ya + SR < y1 ? ya + SR : y1;
     if (ya >= yb) return;
-    const float sx = a.sc->sx;
+    const float sx = scales_sx(a.sc)[n];                           // this image's scale (n is uniform over the workgroup)
     if (x1 - x0 <= 32) split_stage_walk<K, 4>(rawl, py, sx, lane & 31, (lane >> 5) * 4, ya, yb, y0, x0, x1, a.Ws, xhi, xlo);
     else split_stage_walk<K, 8>(rawl, py, sx, lane, 0, ya, yb, y0, x0, x1, a.Ws, xhi, xlo);
 }
@@ -665,7 +708,9 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
         for (int j = 0; j < NT; ++j) sum[j] += acc[j];     // the chain in progress
     }
     // epilogue: C/D layout of the 32x32 tile: column (pixel) = lane & 31, row (channel) = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
-    const float inv = a.sc->inv;
+    // the scales are undone by two exact power-of-two multiplies, 1 / sw then this image's 1 / sx[n]: their product may lie outside
+    // the fp32 range where the result does not
+    const float inv_w = a.sc->inv_sw, inv_x = scales_inv_sx(a.sc, a.N)[n];
     const int y = rowb + prow + prr;
     const long plane = (long)out_h * out_w;
 #pragma unroll
@@ -678,11 +723,11 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
                 if (f < out_c) {
                     const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
                     if constexpr (ADD) {
-                        const float v = sum[j][i] * inv + part_ptr[o];
+                        const float v = sum[j][i] * inv_w * inv_x + part_ptr[o];
                         if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
                         else store_act(out_ptr, o, v, out_bf16, false);
-                    } else if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv, false);
-                    else store_act(out_ptr, o, sum[j][i] * inv, out_bf16, false);
+                    } else if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv_w * inv_x, false);
+                    else store_act(out_ptr, o, sum[j][i] * inv_w * inv_x, out_bf16, false);
                 }
             }
         }
@@ -804,13 +849,13 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     const SplitGeom g = split_geometry(c);
     char* ws = static_cast<char*>(workspace);
     SplitScales* sc = reinterpret_cast<SplitScales*>(ws);
-    unsigned* partial = reinterpret_cast<unsigned*>(ws + sizeof(SplitScales));
+    unsigned* partial = reinterpret_cast<unsigned*>(ws + scales_bytes(c.N));
     _Float16* xs = reinterpret_cast<_Float16*>(ws + g.hdr_bytes);
     _Float16* wsd = reinterpret_cast<_Float16*>(ws + g.hdr_bytes + g.xs_bytes);
-    const long count = (long)c.N * c.Cin * c.H * c.W, units = (long)c.Cin * c.G * c.Cout;
-    const int nparts = (int)std::min<long>(kPartials, (count / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(split_absmax_kernel, dim3(nparts), dim3(256), 0, st, in, count, c.act, table, units, partial, guard);
-    hipLaunchKernelGGL(split_scales_kernel, dim3(1), dim3(256), 0, st, partial, nparts, c.G, sc, guard);
+    const long per = (long)c.Cin * c.H * c.W, units = (long)c.Cin * c.G * c.Cout;
+    const int gpi = absmax_groups_per_image(c.N, per), cap = kPartials + c.N;
+    hipLaunchKernelGGL(split_absmax_kernel, dim3(c.N * gpi), dim3(256), 0, st, in, per, gpi, c.act, table, units, partial, cap, guard);
+    hipLaunchKernelGGL(split_scales_kernel, dim3(c.N + 1), dim3(256), 0, st, partial, c.N, gpi, cap, c.G, sc, guard);
     hipLaunchKernelGGL(split_densify_kernel, dim3(g.nchunk * (g.CoutP / (kScT / 16))), dim3(kScT), 0, st, table, c.Cin, c.G, c.Cout, g.CoutP,
                        g.nchunk, sc, wsd, guard);
     SplitStageArgs s{};
@@ -871,7 +916,7 @@ SplitStaged split_gather_staged(const DenseConfig& c, const void* workspace) {
     const SplitGeom g = split_geometry(c);
     const char* ws = static_cast<const char*>(workspace);
     SplitStaged s{};
-    s.sx = &reinterpret_cast<const SplitScales*>(ws)->sx;
+    s.sx = scales_sx(reinterpret_cast<const SplitScales*>(ws));
     s.xs = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes);
     s.Hs = g.Hs; s.Ws = g.Ws; s.nchunk = g.nchunk;
     return s;

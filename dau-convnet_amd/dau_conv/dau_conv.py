@@ -408,7 +408,8 @@ class DAUConv2d(nn.Module):
     False: never read the result back.  `dense_split` (None: the library's choice, True: always, False: never): calls whose
     offsets lie within +-2 / +-3 / +-4 run their two gather-sum passes as a densified GEMM on the f16 matrix cores with both
     operands split into two binary16 limbs -- fp32 accuracy (the exact kernels' parity bar), about 1.7x faster at four units per
-    channel pair; by default a plan holds the radii that pay for its unit count.  `dense_outliers=True` (opt-in): a call whose
+    channel pair; by default a plan holds the radii that pay for its unit count.  Every image is scaled on its own, so an output
+    image (and its input gradient) depends only on that image and the parameters, never on its batch-mates.  `dense_outliers=True` (opt-in): a call whose
     offsets reach beyond +-3 (up to +-4) in few units -- a trained layer's offsets drift to the +-3.99 clip of kernel 9 -- keeps the
     radius-3 GEMM and gathers those units' outer taps in a sparse pass of its own, instead of moving the whole pass to the 9 x 9
     member; same accuracy, no effect on calls within +-3 or with many such units.  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run

@@ -53,6 +53,12 @@
  * dau_conv_backward OVERWRITES the gradient outputs (the reference op zero-fills them and
  * then accumulates, dau_conv_grad_op.cpp:202-205 -- same net result).
  *
+ * Images are independent.  y[n] and dx[n] depend only on image n of the input (x[n], dy[n]) and on the
+ * parameters -- not on the other images of the batch, and not on how the batch is cut into slabs (below): the
+ * same image gives the same bits in any batch.  That holds for every gather-sum kernel, the two-limb f16 dense
+ * members (DAU_FLAG_DENSE_SPLIT_F16) included, which scale each image by a power of two of its own.  A
+ * non-finite input element affects only the outputs its taps reach within its own image.
+ *
  * Offset buckets.  The kernels stage a border of R pixels around every tile, R in
  * {4, 8, 16, 18, 20, 24, 32}.  The reference picks R per call from a blocking amax of mu1/mu2
  * (dau_conv_op.cpp:223-253).  Here a plan holds the kernel sets of every R up to the one
@@ -65,7 +71,8 @@
  * Workspace.  Every pass stages its input before it gathers.  Where the staged copy of the
  * whole batch would exceed 12 GB (DAU_WORKSPACE_BUDGET_GB in the environment at plan
  * creation; only 512 x 512 maps get there) the pass runs over the batch in slabs of an even
- * divisor of N images, and dau_conv_workspace_bytes reports the smaller requirement.
+ * divisor of N images, and dau_conv_workspace_bytes reports the smaller requirement.  y and dx
+ * of a slabbed pass are bit-identical to the whole-batch pass (images are independent).
  *
  * HIP graphs.  After one ordinary call (which sets the kernels' launch attributes) forward and
  * backward only enqueue kernels and one 16-byte memset on the caller's stream, so they can be
@@ -130,6 +137,13 @@ enum {
                                                gather, measured margins in profiles/ -- at 3 * taps / 16 of the fp32 rate per (pixel,
                                                channel pair) instead of 4 G.  float32, bfloat16 or float16 activations; the call's offsets decide
                                                on the device which member runs; every other call keeps the exact kernels.
+                                               The limbs are taken after an exact power-of-two scaling, ONE SCALE PER IMAGE (from the
+                                               image's largest finite |value|; the dense taps likewise from the finite units): y[n] and
+                                               dx[n] depend only on image n of the input and on the parameters, whatever the other
+                                               images hold and however the batch is cut into slabs; a non-finite element (Inf, NaN)
+                                               affects only the outputs its taps reach within its own image -- in the dense form the
+                                               whole (2R+1)^2 kernel around the prefiltered element.  Dynamic range within one image:
+                                               values below 2^-17 of that image's maximum carry an absolute error below 2^-39 of it.
                                                The parameter gradients of fp32, interpolating, 2-D calls within +-4 likewise run as a
                                                two-limb f16 GEMM with the four kinds x four bilinear corners as rows (k_split_dot.hip,
                                                fp32 accuracy).  DEFAULT (neither flag): the members that pay for the plan's unit count

@@ -1,0 +1,64 @@
+#!/usr/bin/env python3
+"""tools/ab_step_libs.py --parent-lib <library of the parent commit> --out FILE: A/B of the north-star step (bench.py) between
+another build of the library and this tree's, interleaved rounds of fresh processes on one box, then one rocprofv3 --kernel-trace
+--stats run of each build for the per-pass times of the two-limb gather-sum's kernels.  One JSON line per run, a verdict line (this
+build's median against the parent's median plus the parent's own min-max spread), one line of kernel times per build."""
+import argparse, csv, glob, json, os, statistics, subprocess, sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ap = argparse.ArgumentParser()
+ap.add_argument("--parent-lib", required=True)
+ap.add_argument("--out", required=True, help="JSON-lines file to write; the rocprofv3 scratch directories go next to it")
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--steps", type=int, default=40)
+ap.add_argument("--warmup", type=int, default=5)
+args = ap.parse_args()
+OUT = os.path.dirname(os.path.abspath(args.out))
+LIBS = [("parent", os.path.abspath(args.parent_lib)), ("this", os.path.join(ROOT, "dau-convnet_amd", "dau_conv", "libdau_conv_hip.so"))]
+ROUNDS, STEPS, WARMUP = args.rounds, args.steps, args.warmup
+BENCH = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(STEPS), "--warmup", str(WARMUP)]
+os.makedirs(OUT, exist_ok=True)
+lines = open(args.out, "w")
+
+
+def emit(d):
+    lines.write(json.dumps(d) + "\n"); lines.flush()
+    print(json.dumps(d)[:600], flush=True)
+
+
+def run(cmd, env, limit):
+    p = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, cwd=ROOT, env=env, capture_output=True, text=True)
+    if p.returncode != 0:
+        print("rc", p.returncode, "of", cmd, "\n", p.stdout[-1500:], p.stderr[-3000:], flush=True)
+        sys.exit(p.returncode)           # nothing more on the GPU after a failure
+    return p.stdout
+
+
+ms = {t: [] for t, _ in LIBS}
+for rnd in range(ROUNDS):
+    for tag, lib in LIBS:
+        env = dict(os.environ, DAU_CONV_LIB=lib)
+        d = json.loads([l for l in run(BENCH, env, 280).splitlines() if l.startswith("{")][-1])
+        ms[tag].append(d["ms_per_step"])
+        emit(dict(call="bench", round=rnd, build=tag, ms_per_step=d["ms_per_step"], value=d["value"], unit=d["unit"], steps=STEPS, warmup=WARMUP,
+                  lib=d.get("lib"), parity_gate=d.get("parity_gate"),
+                  kernels_avg_ms={k: v.get("avg_ms") for k, v in (d.get("roofline") or {}).get("kernels", {}).items()},
+                  workload=d["config"]["workload"]))
+med = {t: statistics.median(v) for t, v in ms.items()}
+spread = max(ms["parent"]) - min(ms["parent"])
+emit(dict(call="verdict", rounds=ROUNDS, ms_per_step=ms, median_ms=med, parent_min_max_spread_ms=round(spread, 4),
+          this_minus_parent_median_ms=round(med["this"] - med["parent"], 4), within_parent_spread=bool(med["this"] <= med["parent"] + spread)))
+
+for tag, lib in LIBS:
+    d = os.path.join(OUT, "prof_" + tag)
+    env = dict(os.environ, DAU_CONV_LIB=lib)
+    run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "x", "--"] + BENCH, env, 400)
+    stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
+    rows = {}
+    for r in csv.DictReader(open(stats[0])):
+        name = r["Name"]
+        if any(k in name for k in ("split_absmax", "split_scales", "split_stage", "split_densify", "split_gather_kernel")):
+            key = name.split("(")[0][:90]
+            rows[key] = dict(calls=int(r["Calls"]), avg_us=round(float(r["AverageNs"]) / 1e3, 2), total_ms=round(float(r["TotalDurationNs"]) / 1e6, 3))
+    emit(dict(call="rocprofv3 --kernel-trace --stats", build=tag, steps=STEPS, warmup=WARMUP, kernels=rows))
+    subprocess.run(["rm", "-rf", d])
