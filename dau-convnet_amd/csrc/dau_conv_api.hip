@@ -619,12 +619,12 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             }
         }
         {
-            // two-limb f16 gather-dot: fp32 and f16 layers, bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default
-            // where the blocks of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with
-            // DAU_FLAG_DENSE_SPLIT_F16 whatever the unit count
+            // two-limb f16 gather-dot: bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default where the blocks
+            // of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with DAU_FLAG_DENSE_SPLIT_F16 whatever the
+            // unit count.  fp32, f16 and bf16 layers alike; a bf16 layer's error is staged in one limb (split_dot_configure)
             const bool interp2d = (flags & DAU_FLAG_USE_INTERPOLATION) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL);
             const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
-            bs.has[kSplitDot] = split_allowed && !bf16 && whole_dot && interp2d && (split_forced || fill) &&
+            bs.has[kSplitDot] = split_allowed && whole_dot && interp2d && (split_forced || fill) &&
                                 split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
         }
     }

@@ -150,12 +150,15 @@ void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, lon
 
 // Parameter gradients at fp32 accuracy on the f16 matrix cores (k_split_dot.hip): per input channel a GEMM with the four kinds x
 // four bilinear corners as rows, the units as columns and (position, image) as K, both operands split into two binary16 limbs.
-// Offsets within +-4, fp32 or f16 activations, interpolation on; the whole batch in one pass.
+// Offsets within +-4, interpolation on; the whole batch in one pass.  fp32 and f16 activations: both operands in two limbs, three
+// products.  bf16 activations: a bf16 dy times its channel's power-of-two scale is its own hi limb, so the error is staged in
+// ONE limb (ES1, half the bytes) and a tile takes two products per K step (sd_e1_dot_kernel); Xk keeps two limbs.
 struct SplitDotConfig {
     Shape sh;
     int blur_k;
     int RW;               // region columns = K steps per item (10 or 12: the ring of error-window rows fills the LDS at 12)
-    int act;              // storage format of x and dy: kActF32 or kActF16
+    int act;              // storage format of x and dy (ActFormat)
+    int e_limbs;          // binary16 limbs of the staged error: 2, or 1 for bf16 activations
 };
 bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);

@@ -13,6 +13,7 @@
 //  * Staging (8 images innermost, so that a 16-byte fragment is aligned at any displacement):
 //      XS[oct][s][k][Ty][Tx][limb][8 img]   Ty, Tx = image position + 1 (a zero row / column in front for the corner d = 0 of q = -1)
 //      ES[oct][fb][Vy][Vx][limb][16 f][8 img]   Vy, Vx = image position + R + 1, zero halo, the unit_testing edge rule applied
+//      ES1[oct][fb][Vy][Vx][16 f][8 img]        the same with the hi limb only: bf16 activations (below)
 //    Exact power-of-two scales per (s, k) and per f bring each maximum to [2^13, 2^14); the maxima are taken over finite values only
 //    (an Inf / NaN does not remove the scaling of the other channels).  The epilogue undoes them exactly.
 //  * Main kernel.  Workgroup = (chunk of (image octet, region) items, 16 output channels, 16 input channels, 4 units); region =
@@ -30,6 +31,12 @@
 //  * Accuracy.  Per item a tile's accumulator chains 3 x RW MFMAs (hierarchical accumulation, as in the gather-sum); the bilinear
 //    combination joins a running fp32 sum per unit, flushed every few items into the float partial sums [chunk][4][S][G][F] with a
 //    no-return atomic add (the slot belongs to one lane: the program's order), summed over the chunks in double (dot_reduce).
+//  * bf16 activations (SplitDotConfig::e_limbs = 1).  A bf16 dy has 8 significant bits: times its channel's power-of-two scale it
+//    IS its binary16 hi limb (down to the f16 subnormal grid, 2^-27 of the channel's maximum; smaller values round to that grid)
+//    and its lo limb is zero.  The product hi_x * lo_e therefore adds nothing: the error is staged in one limb (ES1, 256 B per
+//    window position instead of 512: half the window copy, half the ring) and a tile takes two MFMAs per K step instead of
+//    three (sd_e1_dot_kernel).  Xk is blurred in fp32 and keeps its two limbs.  Every accumulator chain is that of the
+//    three-product kernel on the widened values with its zero products left out: the same bits.
 #include <algorithm>
 #include <cfloat>
 
@@ -92,7 +99,7 @@ SdLayout sd_layout(const SplitDotConfig& c, const SdGeom& g) {
     l.xk_off = off; off += rup((size_t)g.NP * s.S * s.H * s.W * 32);                              // blur4_pack output, fp32
     // + one position: the pair load of column Wq (sd_next_col) reads, unused, the position after the last plane's last column
     l.xs_off = off; off += rup((size_t)g.octs * s.S * kNumK * g.XTr * g.XTc * 32 + 32);
-    l.es_off = off; off += rup((size_t)g.octs * g.nfb * g.EYs * g.EXs * 512);
+    l.es_off = off; off += rup((size_t)g.octs * g.nfb * g.EYs * g.EXs * 256 * c.e_limbs);
     l.partial_off = off; off += rup((size_t)g.chunks * kNumK * s.S * s.G * s.F * 4);
     l.total = off;
     return l;
@@ -147,7 +154,7 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
 }
 #endif
 
-// max |dy| per output channel: grid (F, split); dy is fp32 or f16 (act)
+// max |dy| per output channel: grid (F, split); dy is fp32, f16 or bf16 (act)
 __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
                                                           unsigned* __restrict__ emax, const Guard guard) {
     if (!guard_pass(guard)) return;
@@ -304,6 +311,55 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
 }
 #endif
 
+// ES1[oct][fb][Vy][Vx][16 f][8]: the one-limb form of the workgroup-per-window-row sd_stage_e_kernel above (bf16 activations:
+// hi = f16(v * scale) is the whole value).  The same structure -- the row's image in LDS, whole-run stores, zero halo, the edge
+// rule -- with 16 pieces of 16 bytes per position.  Bank permutation: a position is 256 B = twice the 128 B that the 32 banks of
+// a ds_write_b128 span, so a piece's bank group is (piece & 7) whatever the position; the eight lanes of a write group (eight
+// consecutive x, one channel fl) write pieces fl ^ (lx & 7), whose low three bits take all eight values: all 32 banks.
+// (-DDAU_SD_STAGE_REF keeps the earlier form of the two-limb kernel only; one-limb plans stage through this kernel there too.)
+constexpr int kSe1TX = 80;              // window columns per workgroup: 20 KiB of LDS
+__global__ void __launch_bounds__(256) sd_stage_e1_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
+                                                          int F, int H, int W, int nfb, int EYs, int EXs, int nct, int TX,
+                                                          int drop_col, int drop_row, int act, h8* __restrict__ es,
+                                                          const Guard guard) {
+    __shared__ h8 tile[kSe1TX * kSdFB];
+    if (!guard_pass(guard)) return;
+    int t = blockIdx.x;
+    const int ct = t % nct; t /= nct;
+    const int vy = t % EYs; t /= EYs;
+    const int fb = t % nfb;
+    const int oct = t / nfb;
+    const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
+    const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
+    const int y = vy - (kSdR + 1);
+    // its columns inside the image: [c0, c1)
+    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    const int nd = max(c1 - c0, 0);
+    for (int i = threadIdx.x; i < kSdFB * nd; i += 256) {
+        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdR + 1), lx = vx - vx0;
+        const int f = fb * kSdFB + fl;
+        const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
+        float v[8];
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int img = oct * 8 + n;
+            v[n] = (f < F && img < N) ? load_act(dy, (((long)img * F + f) * H + y) * W + x, act) : 0.0f;
+        }
+        h8 hi;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) hi[n] = (_Float16)(v[n] * sc);   // (a non-finite value keeps its hi limb, as in split_limbs)
+        tile[lx * kSdFB + (fl ^ (lx & 7))] = hi;
+    }
+    if (nd > 0) __syncthreads();                         // (nd is the same for the whole workgroup)
+    h8* dst = es + ((((size_t)oct * nfb + fb) * EYs + vy) * EXs + vx0) * kSdFB;
+    for (int q = threadIdx.x; q < nvx * kSdFB; q += 256) {
+        const int lx = q >> 4, vx = vx0 + lx;
+        h8 piece = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (vx >= c0 && vx < c1) piece = tile[lx * kSdFB + ((q & 15) ^ (lx & 7))];
+        dst[q] = piece;
+    }
+}
+
 struct SdArgs {
     const h8* xs;
     const char* es;
@@ -348,14 +404,19 @@ __device__ __forceinline__ h8 sd_next_col(h8 cur, h8 nxt, int dx) {
 // Timing experiments of a tuning build (tools/build_variant.sh; results are garbage): DAU_SD_DIAG_NOFILL copies no window
 // (waits and barriers stay), DAU_SD_DIAG_NOA reloads no A fragment, DAU_SD_DIAG_AFIXED reads the A fragments of the chunk's
 // first item for every item (the same loads, hitting in the caches).
-template <int RW>
-__global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) split_gather_dot_kernel(const SdArgs a) {
+// EL: limbs of the staged error = 256-byte halves of a window position.  EL = 2 is split_gather_dot_kernel; EL = 1
+// (sd_e1_dot_kernel, bf16 activations) reads ES1, holds half the ring and leaves out the product with the lo limb of the error.
+template <int RW, int EL>
+__device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     if (!guard_pass(a.guard)) return;
     constexpr int WL = RW + 2 * kSdR, WR = kSdRH + 2 * kSdR;
     constexpr int kRing = WR + kSdRH;                    // ring slots (rows)
-    constexpr unsigned RB = WL * 512;                    // bytes per window row
-    constexpr int kRowPieces = (RB + 1023) / 1024;       // 1 KiB pieces per row (a whole number: WL is even)
+    constexpr int PB = EL * 256;                         // bytes per window position: 16 channels x 8 images x EL limbs
+    constexpr unsigned RB = WL * PB;                     // bytes per window row
+    // 1 KiB pieces per row: a whole number for EL = 2 (WL is even); for EL = 1 and RW = 10 the last piece of a row is half
+    // a piece (its upper 32 lanes are masked off: `within < RB` below)
+    constexpr int kRowPieces = (RB + 1023) / 1024;
     static_assert((kRing & (kRing - 1)) == 0, "ring slot = (origin + row) & (kRing - 1)");
     static_assert(RW % 2 == 0, "A fragment sets by the parity of the K step / of the pair of K steps");
 #ifdef DAU_SD_STEP_LOADS
@@ -396,7 +457,7 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
             const int g = gb * kSdGT + gg;
             UnitRef u{0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
             if (s_ok[i] && g < a.G && f_ok) u = a.table[((size_t)sidx[i] * a.G + g) * a.F + f];
-            uw[i][gg] = (unsigned)(j - u.oy + kSdR) | (unsigned)((kSdR - u.ox) * 512 + fl * 16) << 4;
+            uw[i][gg] = (unsigned)(j - u.oy + kSdR) | (unsigned)((kSdR - u.ox) * PB + fl * 16) << 4;
             wb[i][gg] = f4s{u.w00, u.w01, u.w10, u.w11};
             run[i][gg] = 0.0f;
         }
@@ -433,12 +494,12 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
     // eight waves row by row (a piece must be contiguous in LDS)
     auto fill = [&](int oct, int ry, int rx, int w0, int nrows, int origin) {
 #ifndef DAU_SD_DIAG_NOFILL
-        const char* src = a.es + ((((size_t)oct * a.nfb + fb) * a.EYs + (size_t)(ry * kSdRH + w0)) * a.EXs + (size_t)rx * RW) * 512;
+        const char* src = a.es + ((((size_t)oct * a.nfb + fb) * a.EYs + (size_t)(ry * kSdRH + w0)) * a.EXs + (size_t)rx * RW) * PB;
         for (int u = wave_u; u < nrows * kRowPieces; u += kSdWaves) {
             const int rr = u / kRowPieces, pc = u - rr * kRowPieces;
             const unsigned within = pc * 1024 + lane * 16;
             const unsigned slot = (unsigned)(origin + w0 + rr) & (kRing - 1);
-            if (within < RB) sd_glds16(src + (size_t)rr * a.EXs * 512 + within, lds0 + slot * RB + pc * 1024);
+            if (within < RB) sd_glds16(src + (size_t)rr * a.EXs * PB + within, lds0 + slot * RB + pc * 1024);
         }
 #endif
     };
@@ -500,7 +561,7 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
         for (int i = 0; i < kSdAS; ++i)
 #pragma unroll
             for (int gg = 0; gg < kSdGT; ++gg) part[i][gg] = f4s{0.0f, 0.0f, 0.0f, 0.0f};
-        // Inside a K step the two input channels are two groups of 12 MFMAs; the B fragments of group i + 1 are read from LDS
+        // Inside a K step the two input channels are two groups of 12 MFMAs (8 for EL = 1); the B fragments of group i + 1 are read from LDS
         // while group i runs, and what follows the MFMAs of group i (the odd step's fragment, the loads of channel i) is issued
         // while they run (sched barriers pin it).  The item is not unrolled whole: hipcc hoists loads of later steps until it
         // spills.
@@ -511,9 +572,9 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
 #endif
 #define SD_READ_B(i, bh, bl)                                                                                    \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
-        const char* bp = lds + base[i][gg] + k * 512;                                                           \
+        const char* bp = lds + base[i][gg] + k * PB;                                                            \
         bh[gg] = *reinterpret_cast<const h8*>(bp);                                                              \
-        bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                                        \
+        if constexpr (EL == 2) bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                 \
     }
         // group i of a K step: the MFMAs on the fragment (AH, AL), then AFTER, between two sched barriers
 #define SD_GROUP(i, AH, AL, bh, bl, AFTER)                                                                      \
@@ -521,7 +582,7 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
         part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, bh[gg], part[i][gg], 0, 0, 0);                 \
         part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AL, bh[gg], part[i][gg], 0, 0, 0);                 \
-        part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, bl[gg], part[i][gg], 0, 0, 0);                 \
+        if constexpr (EL == 2) part[i][gg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(AH, bl[gg], part[i][gg], 0, 0, 0); \
     }                                                                                                           \
     AFTER                                                                                                       \
     __builtin_amdgcn_sched_barrier(0);
@@ -611,21 +672,36 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
 }
 
 template <int RW>
+__global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) split_gather_dot_kernel(const SdArgs a) {
+    sd_dot_body<RW, 2>(a);
+}
+
+// the one-limb-error member (bf16 activations): ES1, two products per tile and K step
+template <int RW>
+__global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) sd_e1_dot_kernel(const SdArgs a) {
+    sd_dot_body<RW, 1>(a);
+}
+
+template <int RW, int EL>
 void launch_sd(hipStream_t st, const SdArgs* a, int grid) {
-    auto kern = split_gather_dot_kernel<RW>;
-    const size_t lds = (size_t)(2 * kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 512;
+    auto kern = [] { if constexpr (EL == 2) return split_gather_dot_kernel<RW>; else return sd_e1_dot_kernel<RW>; }();
+    const size_t lds = (size_t)(2 * kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 256 * EL;
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kSdWaves * 64), lds, st, *a);
 }
-void dispatch_sd(int RW, hipStream_t st, const SdArgs* a, int grid) {
-    if (RW == 10) launch_sd<10>(st, a, grid);
-    else launch_sd<12>(st, a, grid);
+void dispatch_sd(int RW, int e_limbs, hipStream_t st, const SdArgs* a, int grid) {
+    if (e_limbs == 1) {
+        if (RW == 10) launch_sd<10, 1>(st, a, grid);
+        else launch_sd<12, 1>(st, a, grid);
+    } else {
+        if (RW == 10) launch_sd<10, 2>(st, a, grid);
+        else launch_sd<12, 2>(st, a, grid);
+    }
 }
 
 }  // namespace
 
 bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg) {
-    if (act == kActBF16) return false;
     // the region width whose ring of error-window rows fits the LDS (RW <= 12) with the least work: the q columns (W + 1) padded
     // to a multiple of RW, plus about two K steps' worth of per-item cost (barrier, bilinear epilogue) per region
     int best = 0;
@@ -639,9 +715,17 @@ bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* c
     if (!blur4_pack_fits(blur_k, sh.H, sh.W)) return false;
     SplitDotConfig c{};
     c.sh = sh; c.blur_k = blur_k; c.RW = best; c.act = act;
+    // bf16 activations: the error in one limb.  -DDAU_SD_BF16_E2 (libdau_conv_hip_bf16_e2.so of `make tuning`) gives bf16 plans the
+    // three-product kernel and the two-limb ES through widening loads instead: the bit-exact reference of
+    // tests/test_gpu_bf16_split_dot.py and the A/B partner that tells what the one-limb form itself is worth.
+#ifdef DAU_SD_BF16_E2
+    c.e_limbs = 2;
+#else
+    c.e_limbs = act == kActBF16 ? 1 : 2;
+#endif
     const SdGeom g = sd_geom(c);
     // 32-bit LDS / lane offsets; h8 offsets of the staged planes stay in size_t
-    if ((long)g.EXs * 512 * 32 > (1L << 31)) return false;
+    if ((long)g.EXs * 512 * 32 > (1L << 31)) return false;   // (the two-limb row; a one-limb row is half of it)
     *cfg = c;
     return true;
 }
@@ -649,7 +733,7 @@ bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* c
 size_t split_dot_workspace_bytes(const SplitDotConfig& c) { return sd_layout(c, sd_geom(c)).total; }
 
 void split_dot_init(const SplitDotConfig& c) {
-    dispatch_sd(c.RW, nullptr, nullptr, 0);
+    dispatch_sd(c.RW, c.e_limbs, nullptr, nullptr, 0);
 #ifndef DAU_SD_STAGE_REF
     blur4_pack_init(c.blur_k, true);
 #else
@@ -680,6 +764,12 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
     hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
                        reinterpret_cast<h8*>(ws + l.xs_off), guard);
+    if (c.e_limbs == 1) {
+        const int nct = (g.EXs + kSe1TX - 1) / kSe1TX, tx = (g.EXs + nct - 1) / nct;  // column tiles of a window row, evenly wide
+        hipLaunchKernelGGL(sd_stage_e1_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F,
+                           s.H, s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+        return;
+    }
 #ifndef DAU_SD_STAGE_REF
     const int nct = (g.EXs + kSeTX - 1) / kSeTX, tx = (g.EXs + nct - 1) / nct;    // column tiles of a window row, evenly wide
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F, s.H,
@@ -706,7 +796,7 @@ void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table
     a.nfb = g.nfb; a.nsb = g.nsb; a.ngb = g.ngb; a.per = g.per; a.items = g.items; a.rq = g.rq; a.cq = g.cq;
     a.XTr = g.XTr; a.XTc = g.XTc; a.EYs = g.EYs; a.EXs = g.EXs;
     a.guard = guard;
-    dispatch_sd(c.RW, st, &a, g.chunks * g.nfb * g.nsb * g.ngb);
+    dispatch_sd(c.RW, c.e_limbs, st, &a, g.chunks * g.nfb * g.nsb * g.ngb);
     launch_dot_reduce(st, a.partial, 1, (long)kNumK * s.S * s.G * s.F, s.G, s.F, s.G, g.chunks, g.chunks, s.G, false, r4, guard);
 }
 

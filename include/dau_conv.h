@@ -144,9 +144,16 @@ enum {
                                                affects only the outputs its taps reach within its own image -- in the dense form the
                                                whole (2R+1)^2 kernel around the prefiltered element.  Dynamic range within one image:
                                                values below 2^-17 of that image's maximum carry an absolute error below 2^-39 of it.
-                                               The parameter gradients of fp32, interpolating, 2-D calls within +-4 likewise run as a
+                                               The parameter gradients of interpolating, 2-D calls within +-4 likewise run as a
                                                two-limb f16 GEMM with the four kinds x four bilinear corners as rows (k_split_dot.hip,
-                                               fp32 accuracy).  DEFAULT (neither flag): the members that pay for the plan's unit count
+                                               fp32 accuracy), for float32, float16 and bfloat16 activations alike.  A bfloat16 layer's
+                                               error enters in ONE limb (a bf16 dy times its channel's power-of-two scale is exactly
+                                               representable in binary16: two products per tile instead of three): its parameter
+                                               gradients meet the fp32 bar; an error value of at least 2^-27 of its output channel's
+                                               largest finite |dy| enters exactly, smaller ones are rounded to the f16 subnormal grid
+                                               (an absolute error below 2^-38 of that maximum); a non-finite dy element affects only
+                                               its own output channel's gradients, a non-finite x element only its own input
+                                               channel's.  DEFAULT (neither flag): the members that pay for the plan's unit count
                                                (on whole tiles: radius 2 from two units per channel pair, radius 3 from three, radius 4 from four;
                                                the parameter-gradient member where blocks of four units are at least 3/4 full: G = 3, 4, 7, 8, ...).
                                                This flag: all members whatever the unit count.                             */
