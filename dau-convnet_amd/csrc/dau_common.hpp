@@ -57,6 +57,28 @@ __device__ __forceinline__ void with_act(int act, F&& f) {
     else if (act == kActF16) f(std::integral_constant<int, kActF16>{});
     else f(std::integral_constant<int, kActF32>{});
 }
+// DAU_FLAG_IO_NHWC: the user's activations are [N][H][W][C] arrays.  Every kernel that loads x / dy or stores y / dx has NHWC
+// instantiations of its own; only the addresses differ, the arithmetic and the order of every sum are the NCHW instantiation's.
+// The NCHW instantiations must stay the code -- and the symbols -- they were, so a kernel template takes no new argument for it: an
+// NHWC instantiation is the template with kNhwcArg or'ed into its FIRST int argument (blur_pack_kernel<7 | kNhwcArg>), the gather-sum
+// with its traits wrapped in NhwcOut<>.  (A common body inlined into two kernels was tried first: it changed the code of the NCHW ones.)
+// blur4_pack_kernel, whose instantiations the tests count by name, is one text compiled under two names (k_blur4_pack_body.hpp); the
+// small kernels that are no templates (pack_error, sd_stage_e / _e1, sd_absmax_e) have NHWC kernels written for that layout.
+// blur4_pack_kernel, whose instantiations the tests count by name, is one text compiled under two names (k_blur4_pack_body.hpp); the
+// small kernels that are no templates (pack_error, sd_stage_e / _e1, sd_absmax_e) have NHWC kernels written for that layout.
+constexpr int kNhwcArg = 0x100;
+template <class T> struct NhwcOut : T {};
+template <class T> struct IsNhwcOut : std::false_type {};
+template <class T> struct IsNhwcOut<NhwcOut<T>> : std::true_type {};
+// element index of (n, c, y, x) in an [N][H][W][C] array
+__device__ __forceinline__ long nhwc_index(long n, int c, int y, int x, int C, int H, int W) { return ((n * H + y) * W + x) * C + c; }
+// Workgroups b and b + 8 run on the same XCD and share its L2: the logical id under which every XCD takes a contiguous range of
+// ids.  The NHWC staging kernels whose workgroups own ONE channel give consecutive ids to the channels of a window, so that the
+// 128-byte lines their strided loads share are fetched into one L2.
+__device__ __forceinline__ int xcd_contiguous_id(int b, int nblk) {
+    const int xcd = b % 8, idx = b / 8, per = nblk / 8, rem = nblk % 8;
+    return (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + idx;
+}
 // v where keep, +0 elsewhere, as a bit mask: with a select hipcc moves the load that produced v under a branch on `keep`
 __device__ __forceinline__ float mask_act(float v, bool keep) { return __uint_as_float(__float_as_uint(v) & (keep ? 0xffffffffu : 0u)); }
 // Load phase of the staging kernels: rows_ x cols_ items of one plane split over the nw waves of its wave group, the loads of
@@ -107,6 +129,11 @@ __device__ __forceinline__ void store_act(float* base, long idx, float v, bool b
     // exponent: 0xFFFFFFFF -> +0, 0x7F800001 -> +inf), so it is stored as the quiet NaN pattern instead
     u = (v != v) ? 0x7fc00000u : u + 0x7fffu + ((u >> 16) & 1u);
     *p = (unsigned short)(u >> 16);
+}
+// the bfloat16 bits store_act writes for v (round to nearest even, a NaN as the quiet NaN pattern): for stores of several values at once
+__device__ __forceinline__ unsigned bf16_bits(float v) {
+    const unsigned u = __float_as_uint(v);
+    return ((v != v) ? 0x7fc00000u : u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
 }
 // binary16: v_cvt_f16_f32 -- round to nearest even, f16 subnormals kept, beyond the largest finite value +-inf, a NaN stays a
 // NaN (the IEEE conversion, as torch.Tensor.half()); a window pass re-reads the stored value, adds and rounds once more

@@ -536,6 +536,9 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
         (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
+    const bool nhwc = (flags & DAU_FLAG_IO_NHWC) != 0;
+    if (nhwc && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
 
     std::unique_ptr<dau_conv_plan> p(new (std::nothrow) dau_conv_plan());
     if (!p) return fail(DAU_INTERNAL, "out of host memory");
@@ -550,6 +553,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     const Shape& s = p->sh;
     // storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does
     // (the staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ
+    // likewise the layout: an NHWC plan is the NCHW plan of the same desc, its configs marked after they are made (addresses only)
     const int act = f16 ? kActF16 : bf16 ? kActBF16 : kActF32;
     const char* budget_env = getenv("DAU_WORKSPACE_BUDGET_GB");
     const double budget_bytes = (budget_env ? atof(budget_env) : 12.0) * 1e9;
@@ -579,6 +583,10 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             }
             // radius 3 + ring: where the radius-3 member is; its list holds the entries of ring_limit live units and of the ignored ones
             // (the input-gradient table ignores no unit, and the count leaves them out)
+            for (int dir : {kFwd, kDx}) {
+                bs.tiled[dir].nhwc = nhwc;
+                for (int m = kSplit2; m <= kSplit4; ++m) bs.dense[m - kSplit2][dir].nhwc = nhwc;
+            }
             bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
             if (bs.ring) {
                 bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
@@ -589,6 +597,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         auto configure_dot = [&](int n) {
             Shape sn = s; sn.N = n;
             bs.has[kTiledDot] = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
+            bs.tiled_dot.nhwc = nhwc;
             return dot_bytes(bs);
         };
         // slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
@@ -626,12 +635,15 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
             bs.has[kSplitDot] = split_allowed && whole_dot && interp2d && (split_forced || fill) &&
                                 split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
+            bs.sdot.nhwc = nhwc;
         }
     }
     const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
     if ((bf16 || f16) && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
         return fail(DAU_INVALID_ARGUMENT, "%s needs the tiled kernels, which do not support this shape / algo",
                     f16 ? "DAU_FLAG_IO_F16" : "DAU_FLAG_IO_BF16");
+    if (nhwc && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC needs the tiled kernels, which do not support this shape / algo");
     if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
     p->algo_fwd = (desc->algo != DAU_ALGO_DIRECT && fwd_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
     p->algo_bwd = (desc->algo != DAU_ALGO_DIRECT && dot_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;

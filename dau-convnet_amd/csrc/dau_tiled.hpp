@@ -24,6 +24,7 @@ struct TiledConfig {
     int variant;      // kernel instantiation id
     int debug;        // DAU_GATHER_DEBUG at plan creation (timing experiments)
     int act;          // storage format of the activations in and out (ActFormat, dau_common.hpp)
+    int nhwc;         // DAU_FLAG_IO_NHWC: in and out are [N][H][W][C] arrays (set by the plan after configure; addresses only)
 };
 
 bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, TiledConfig* cfg);
@@ -48,6 +49,7 @@ struct DenseConfig {
     int act;          // storage format of the activations in and out (ActFormat; the dense bf16 form requires kActBF16)
     int nsub;         // 8-pixel subtiles per column block = kernel instantiation
     int ftiles;       // 32-channel accumulator tiles per wave (2: four waves per workgroup, 1: eight)
+    int nhwc;         // DAU_FLAG_IO_NHWC (the split forms only): in and out are [N][H][W][C] arrays (set by the plan after configure)
 };
 // The functions exist once per offset radius of the dense form, in the namespaces r4 (|mu| <= 4: 9 x 9 taps) and r3 (|mu| <= 3:
 // 7 x 7): the same source compiled twice (Makefile); `R` of configure must be the namespace's radius.
@@ -124,6 +126,7 @@ struct TiledDotConfig {
     int act;              // storage format of x and dy (ActFormat)
     int ignore;           // number_units_ignore: binned window passes give those units no slot
     int debug;
+    int nhwc;             // DAU_FLAG_IO_NHWC: x and dy are [N][H][W][C] arrays (set by the plan after configure)
 };
 
 bool tiled_dot_configure(const Shape& sh, int R, int blur_k, int act, int ignore, TiledDotConfig* cfg);
@@ -140,8 +143,8 @@ void tiled_dot_init(const TiledDotConfig& cfg);
 // kmax (optional, [cstride][4 kinds] float bits, zeroed by the caller): max |value| per (channel, kind) over the finite values,
 // taken while they are written (a kernel instantiation of its own: callers that pass none run the plain one)
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax = nullptr);
-void blur4_pack_init(int blur_k, bool kmax = false);
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax = nullptr, bool nhwc = false);
+void blur4_pack_init(int blur_k, bool kmax = false, bool nhwc = false);
 bool blur4_pack_fits(int blur_k, int Hp, int Wp);
 
 // r4[k][u] = sum over the slabs of partial[slab][k][u] in double (the gather-dot's deterministic reduction, k_gather_dot.hip)
@@ -159,6 +162,7 @@ struct SplitDotConfig {
     int RW;               // region columns = K steps per item (10 or 12: the ring of error-window rows fills the LDS at 12)
     int act;              // storage format of x and dy (ActFormat)
     int e_limbs;          // binary16 limbs of the staged error: 2, or 1 for bf16 activations
+    int nhwc;             // DAU_FLAG_IO_NHWC: x and dy are [N][H][W][C] arrays (set by the plan after configure)
 };
 bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);

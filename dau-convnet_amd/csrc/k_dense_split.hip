@@ -415,8 +415,15 @@ __device__ __forceinline__ void split_stage_walk(const float* rawl, const float*
 #define DAU_SPLIT_STAGE_THREADS 512        // eight waves share a band (same box: 375 us per pass at the north-star shape with 256 threads, 362 with 512)
 #endif
 constexpr int kStageThreads = DAU_SPLIT_STAGE_THREADS;
-template <int K, int A>
+// KN = K | kNhwcArg: `in` is [N][H][W][C].  The group's eight channels of a pixel are 32 (fp32) or 16 (16-bit) contiguous bytes: a piece
+// is 16 of them -- four fp32 channels or all eight 16-bit ones -- of one pixel, adjacent lanes take the pieces of adjacent pixels of a
+// row, and a lane scatters its piece into the same [row][8 channels][kSP] image (consecutive lanes, consecutive columns: no bank
+// conflict), so that the filter passes are the NCHW kernel's.  a.vec: C is a multiple of the piece's channels and the base is 16-byte
+// aligned; otherwise the piece is loaded element by element.
+template <int KN, int A>
 __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitStageArgs a) {
+    constexpr int K = KN & (kNhwcArg - 1);
+    constexpr bool NHWC = (KN & kNhwcArg) != 0;
     extern __shared__ __attribute__((aligned(16))) float rawl[];   // [row][8 channels][kSP]
     if (!guard_pass(a.guard)) return;
     constexpr int kr = (K - 1) / 2;
@@ -431,6 +438,58 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
     const int x0 = seg * 64, x1 = x0 + 64 < a.W ? x0 + 64 : a.W;
     const int lh = y1 - y0 + 2 * kr;
     const long plane = (long)a.H * a.W;
+    if constexpr (NHWC) {
+        // ---- raw window -> LDS: piece (r, j, part) covers image row y0 - kr + r, column x0 - 8 + j, channels grp*8 + part*CPP .. + CPP - 1
+        constexpr int CPP = A == kActF32 ? 4 : 8, PARTS = 8 / CPP;
+        const int pieces = lh * kSP * PARTS;
+        constexpr int UB = (13 * 256 + kStageThreads - 1) / kStageThreads;   // (as below)
+        for (int i0 = threadIdx.x; i0 < pieces; i0 += kStageThreads * UB) {
+            float v[UB][CPP];
+            // branch-free loads (clamped address, masked value), as below
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int i = i0 + u * kStageThreads, part = i % PARTS, rj = i / PARTS, r = rj / kSP, j = rj - r * kSP;
+                const int c = grp * 8 + part * CPP, y = y0 - kr + r, x = x0 - 8 + j;
+                const bool pix = y >= 0 && y < a.H && x >= 0 && x < a.W && i < pieces;
+                if (a.vec) {
+                    const bool ok = pix && c < a.C;                  // (C is a multiple of CPP: the whole piece lies inside)
+                    const long idx = ok ? nhwc_index(n, c, y, x, a.C, a.H, a.W) : 0;
+                    if constexpr (A == kActF32) {
+                        const float4 w = *reinterpret_cast<const float4*>(a.in + idx);
+                        v[u][0] = mask_act(w.x, ok); v[u][1] = mask_act(w.y, ok); v[u][2] = mask_act(w.z, ok); v[u][3] = mask_act(w.w, ok);
+                    } else {
+                        const uint4 w = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(a.in) + idx);
+                        const unsigned q[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if constexpr (A == kActF16) {
+                                v[u][2 * k] = mask_act(f16_bits_to_float(q[k] & 0xffffu), ok);
+                                v[u][2 * k + 1] = mask_act(f16_bits_to_float(q[k] >> 16), ok);
+                            } else {
+                                const unsigned m = ok ? 0xffffffffu : 0u;
+                                v[u][2 * k] = __uint_as_float((q[k] << 16) & m);
+                                v[u][2 * k + 1] = __uint_as_float(q[k] & 0xffff0000u & m);
+                            }
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < CPP; ++k) {
+                        const bool ok = pix && c + k < a.C;
+                        v[u][k] = mask_act(load_act_t<A>(a.in, ok ? nhwc_index(n, c + k, y, x, a.C, a.H, a.W) : 0), ok);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UB; ++u) {
+                const int i = i0 + u * kStageThreads, part = i % PARTS, rj = i / PARTS, r = rj / kSP, j = rj - r * kSP;
+                if (i < pieces) {
+#pragma unroll
+                    for (int k = 0; k < CPP; ++k) rawl[(r * 8 + part * CPP + k) * kSP + j] = v[u][k];
+                }
+            }
+        }
+    } else
     // ---- raw window -> LDS: piece (r, ch, q) covers image row y0 - kr + r, columns x0 - 8 + 4q .. + 3 of channel grp*8 + ch
     {
         const int pieces = lh * 8 * PPR;
@@ -520,9 +579,9 @@ struct SplitArgs {
     const _Float16* xs;
     const _Float16* wsd;
     const SplitScales* sc;
-    float* out;               // [N][Cout][H][W], f32, bf16 or f16
-    const float* partial;     // ADD instantiations: [N][Cout][H][W] fp32, added to the sums before the store's rounding
-    int N, Cout, CoutP, H, W, Hs, Ws, nchunk, ncb, nrb, out_act;   // out_act: ActFormat of out
+    float* out;               // [N][Cout][H][W] (NHWC instantiations: [N][H][W][Cout]), f32, bf16 or f16
+    const float* partial;     // ADD instantiations: [N][Cout][H][W] fp32 (always planar), added to the sums before the store's rounding
+    int N, Cout, CoutP, H, W, Hs, Ws, nchunk, ncb, nrb, out_act;   // out_act: ActFormat of out (NHWC instantiations: | kNhwcVecOut)
     int col0;                 // first column of this launch's blocks (a row is covered by blocks of NSUB and of NSUB - 1 tiles)
     int row0;                 // first row of this launch's row blocks (a map whose height leaves 1 .. 4 rows after its 8-row blocks
                               // ends with one block of FOUR rows: RG = 1)
@@ -538,8 +597,14 @@ struct SplitArgs {
 // columns where 4 x 8 tiles pad to 32).
 // H16: out is binary16 (an instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
 // ADD (radius 3 only): the epilogue adds the fp32 partial sums of the ring pass (k_dense_ring.hip) before the one rounding of the store
-template <int NSUB, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
+// NSUBN = NSUB | kNhwcArg: out is [N][H][W][Cout].  A lane's sixteen results of a tile are four groups of four CONSECUTIVE channels of
+// its pixel: one 16-byte (fp32) or 8-byte (16-bit) store per group where Cout is a multiple of four and the base is aligned (kNhwcVecOut
+// in out_act), element stores otherwise.  The values and their one rounding are the NCHW epilogue's.
+constexpr int kNhwcVecOut = 0x100;
+template <int NSUBN, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
 __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
+    constexpr int NSUB = NSUBN & (kNhwcArg - 1);
+    constexpr bool NHWC = (NSUBN & kNhwcArg) != 0;
     static_assert(!TT || RG == 2, "tall tiles: blocks of eight rows");
     constexpr int TW = TT ? 4 : 8;                           // columns of a tile
     constexpr int P = TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB);   // LDS pitch (positions)
@@ -607,7 +672,8 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     // (kernel arguments the epilogue uses, read once: inside the lambda hipcc reloads them from the argument segment at every store)
     float* const out_ptr = a.out;
     const float* const part_ptr = a.partial;
-    const bool out_bf16 = a.out_act != 0;                   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
+    const bool out_bf16 = NHWC ? (a.out_act & 0xff) != 0 : a.out_act != 0;   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
+    const bool vec_out = NHWC && (a.out_act & kNhwcVecOut) != 0;
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
     auto body = [&](auto ntc) __attribute__((always_inline)) {
     constexpr int NT = decltype(ntc)::value;                 // tiles of this wave
@@ -716,6 +782,48 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int x = colb + TW * (ptile + j) + pcc;
+        if constexpr (NHWC) {
+            if (y < out_h && x < out_w && ptile + j < NSUB) {
+                const long pix = ((long)n * out_h + y) * out_w + x;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const int f0 = fb * kDFB + fw * 32 + 8 * g4 + 4 * h;
+                    float v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if constexpr (ADD) {
+                            const int fc = f0 + k < out_c ? f0 + k : out_c - 1;      // (clamped address; the value is not stored)
+                            v[k] = sum[j][4 * g4 + k] * inv_w * inv_x + part_ptr[((long)n * out_c + fc) * plane + (long)y * out_w + x];
+                        } else {
+                            v[k] = sum[j][4 * g4 + k] * inv_w * inv_x;
+                        }
+                    }
+                    const long o = pix * out_c + f0;
+                    if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
+                        if (f0 < out_c) {
+                            if constexpr (H16) {
+                                typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                                *reinterpret_cast<f16x4*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
+                                    f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+                            } else if (out_bf16) {
+                                *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
+                                    make_uint2(bf16_bits(v[0]) | (bf16_bits(v[1]) << 16), bf16_bits(v[2]) | (bf16_bits(v[3]) << 16));
+                            } else {
+                                *reinterpret_cast<float4*>(out_ptr + o) = make_float4(v[0], v[1], v[2], v[3]);
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            if (f0 + k < out_c) {
+                                if constexpr (H16) store_act_t<kActF16>(out_ptr, o + k, v[k], false);
+                                else store_act(out_ptr, o + k, v[k], out_bf16, false);
+                            }
+                        }
+                    }
+                }
+            }
+        } else
         if (y < out_h && x < out_w && ptile + j < NSUB) {      // (RG = 1, odd NSUB: the second column half's last tile does not exist)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -751,41 +859,47 @@ template <int NSUB, int RG, bool TT>
 constexpr size_t split_lds_bytes() { return 2 * (size_t)((4 * (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB)) + 63) / 64) * 1024; }
 
 template <int NSUB, int RG, bool TT = false>
-void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool add) {
+void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool add, bool nhwc) {
+    constexpr int NH = NSUB | kNhwcArg;                      // the instantiations that store [N][H][W][Cout]
     auto kern = h16 ? split_gather_kernel<NSUB, RG, TT, true> : split_gather_kernel<NSUB, RG, TT, false>;
+    if (nhwc) kern = h16 ? split_gather_kernel<NH, RG, TT, true> : split_gather_kernel<NH, RG, TT, false>;
 #if DAU_SPLIT_R == 3
     if (add) kern = h16 ? split_gather_kernel<NSUB, RG, TT, true, true> : split_gather_kernel<NSUB, RG, TT, false, true>;
+    if (add && nhwc) kern = h16 ? split_gather_kernel<NH, RG, TT, true, true> : split_gather_kernel<NH, RG, TT, false, true>;
 #endif
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     constexpr size_t lds = split_lds_bytes<NSUB, RG, TT>();      // (a comma inside the launch macro's arguments would split them)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, *a);
 }
 
-void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall = false, bool add = false) {
+void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall, bool add, bool nhwc) {
     if (tall) {                                              // nsub = tiles of four columns: 5 or 7 (split_geometry)
-        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16, add);
-        else launch_split<7, 2, true>(st, a, grid, h16, add);
+        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16, add, nhwc);
+        else launch_split<7, 2, true>(st, a, grid, h16, add, nhwc);
         return;
     }
     if (rg == 1) {
         switch (nsub) {
-            case 1: launch_split<1, 1>(st, a, grid, h16, add); break;
-            case 2: launch_split<2, 1>(st, a, grid, h16, add); break;
-            case 3: launch_split<3, 1>(st, a, grid, h16, add); break;
-            default: launch_split<4, 1>(st, a, grid, h16, add); break;
+            case 1: launch_split<1, 1>(st, a, grid, h16, add, nhwc); break;
+            case 2: launch_split<2, 1>(st, a, grid, h16, add, nhwc); break;
+            case 3: launch_split<3, 1>(st, a, grid, h16, add, nhwc); break;
+            default: launch_split<4, 1>(st, a, grid, h16, add, nhwc); break;
         }
         return;
     }
     switch (nsub) {
-        case 1: launch_split<1, 2>(st, a, grid, h16, add); break;
-        case 2: launch_split<2, 2>(st, a, grid, h16, add); break;
-        case 3: launch_split<3, 2>(st, a, grid, h16, add); break;
-        default: launch_split<4, 2>(st, a, grid, h16, add); break;
+        case 1: launch_split<1, 2>(st, a, grid, h16, add, nhwc); break;
+        case 2: launch_split<2, 2>(st, a, grid, h16, add, nhwc); break;
+        case 3: launch_split<3, 2>(st, a, grid, h16, add, nhwc); break;
+        default: launch_split<4, 2>(st, a, grid, h16, add, nhwc); break;
     }
 }
 
-const void* stage_for(int blur_k, int act) {
-#define DAU_SPLIT_STAGE(K) case K: return act == kActF16 ? reinterpret_cast<const void*>(split_stage_kernel<K, kActF16>) : \
+const void* stage_for(int blur_k, int act, bool nhwc = false) {
+#define DAU_SPLIT_STAGE(K) case K: if (nhwc) return act == kActF16 ? reinterpret_cast<const void*>(split_stage_kernel<K | kNhwcArg, kActF16>) : \
+                                          act == kActBF16 ? reinterpret_cast<const void*>(split_stage_kernel<K | kNhwcArg, kActBF16>) : \
+                                                            reinterpret_cast<const void*>(split_stage_kernel<K | kNhwcArg, kActF32>); \
+                                   return act == kActF16 ? reinterpret_cast<const void*>(split_stage_kernel<K, kActF16>) : \
                                           act == kActBF16 ? reinterpret_cast<const void*>(split_stage_kernel<K, kActBF16>) : \
                                                             reinterpret_cast<const void*>(split_stage_kernel<K, kActF32>)
     switch (blur_k) {
@@ -836,12 +950,12 @@ void split_gather_init(const DenseConfig& c) {
     for (int rg = 1; rg <= 2; ++rg) {
         if (!(rg == 2 ? g.nrb8 : g.nrb4)) continue;
         for (int add = 0; add <= (kDR == 3 ? 1 : 0); ++add) {    // (the radius-3 form also exists with the ring pass's partial sums added)
-            if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true, add != 0); continue; }
-            dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0, false, add != 0);
-            if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0, false, add != 0);
+            if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true, add != 0, c.nhwc != 0); continue; }
+            dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0, false, add != 0, c.nhwc != 0);
+            if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0, false, add != 0, c.nhwc != 0);
         }
     }
-    (void)hipFuncSetAttribute(stage_for(c.blur_k, c.act), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(stage_for(c.blur_k, c.act, c.nhwc != 0), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in, const float* filters, bool mirrored,
@@ -866,8 +980,9 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     stage_plan(c, &s.RB, &s.nbands, &lds);
     s.nsegs = (c.W + 63) / 64;
     s.vec = c.W % 4 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0;
+    if (c.nhwc) s.vec = c.Cin % (c.act == kActF32 ? 4 : 8) == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0;   // 16-byte pieces of a pixel's channels
     void* args[] = {&s};
-    (void)hipLaunchKernel(stage_for(c.blur_k, c.act), dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(kStageThreads), args, lds, st);
+    (void)hipLaunchKernel(stage_for(c.blur_k, c.act, c.nhwc != 0), dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(kStageThreads), args, lds, st);
 }
 
 namespace {
@@ -884,20 +999,22 @@ void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* pa
     a.out = out; a.partial = partial;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
     a.out_act = c.act; a.guard = guard;
+    const bool nhwc = c.nhwc != 0;
+    if (nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(out) % (c.act == kActF32 ? 16 : 8) == 0) a.out_act |= kNhwcVecOut;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
         a.nrb = rg == 2 ? g.nrb8 : g.nrb4;
         if (!a.nrb) continue;
         a.row0 = rg == 2 ? 0 : g.nrb8 * kDRows;
         if (rg == 2 && g.tall) {                             // one column block of tall tiles
             a.ncb = 1; a.col0 = 0;
-            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true, add);
+            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true, add, nhwc);
             continue;
         }
         a.ncb = g.nb_a; a.col0 = 0;
-        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB), false, add);
+        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB), false, add, nhwc);
         if (g.nb_b) {
             a.ncb = g.nb_b; a.col0 = g.nb_a * g.nsub_a * 8;
-            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB), false, add);
+            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB), false, add, nhwc);
         }
     }
 }

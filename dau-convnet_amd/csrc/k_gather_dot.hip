@@ -279,6 +279,32 @@ __global__ void __launch_bounds__(256) pack_error_kernel(const float* __restrict
     }
 }
 
+// The same EP from an [N][H][W][F] dy (DAU_FLAG_IO_NHWC).  There the 32 channels x 2 images of a position, which EP keeps together, are
+// already channel-major runs of the input: no transpose through LDS -- a thread loads the element it stores, a wave two 128-byte (fp32)
+// runs of the two images' channels, and writes one contiguous 256 bytes.
+__global__ void __launch_bounds__(256) pack_error_kernel_nhwc(const float* __restrict__ dy, int N, int F, int H, int W, int R,
+                                                              int EX, int EY, int nfb, int drop_col, int drop_row, int act,
+                                                              float* __restrict__ ep, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const int nxc = (EX + kPackErrorChunk - 1) / kPackErrorChunk;
+    int t0 = blockIdx.x;
+    const int xc = t0 % nxc; t0 /= nxc;
+    const int Y = t0 % EY; t0 /= EY;
+    const int fb = t0 % nfb;
+    const int np = t0 / nfb;
+    const int y = Y - (R + 1);
+    const int X0 = xc * kPackErrorChunk, X1 = X0 + kPackErrorChunk < EX ? X0 + kPackErrorChunk : EX;   // padded columns
+    const bool rowin = y >= 0 && y < H && !(drop_row && y == H - 1);
+    float* out = ep + ((((size_t)np * nfb + fb) * EY + Y) * EX + X0) * (kDF * 2);
+    const int wlim = drop_col ? W - 1 : W;
+    for (int t = threadIdx.x; t < (X1 - X0) * 64; t += blockDim.x) {
+        const int X = X0 + (t >> 6), r = t & 63, x = X - (R + 1);
+        const int f = fb * kDF + (r >> 1), n = 2 * np + (r & 1);
+        const bool ok = rowin && x >= 0 && x < wlim && f < F && n < N;
+        out[t] = mask_act(load_act(dy, ok ? nhwc_index(n, f, y, x, F, H, W) : 0, act), ok);   // (branch free: clamped address, masked value)
+    }
+}
+
 // x[N,S,H,W] -> XK[NP][S][Hp][Wp][4][2]: the four derivative-filtered copies (separable form, see dau_common.hpp),
 // zero padded to whole regions.  One workgroup per (pair, output window, channel): raw window (+ blur halo) -> LDS,
 // three horizontal passes (gx, ax, cx) -> LDS, five vertical 1-D passes -> 32 B per position.  HBM bound.
@@ -299,133 +325,16 @@ struct Blur4Args {
 // KMAX: also take max |value| per (channel, kind) of what is stored, over finite values only (the scales of the two-limb
 // gather-dot, k_split_dot.hip: the values are in registers here, a pass of its own would read all of XK back).  A wave works
 // on one window, so on one channel: it reduces its four maxima across its lanes and lane 0 issues one atomicMax per kind.
-template <int K, bool KMAX>
-__global__ void __launch_bounds__(512) blur4_pack_kernel(const Blur4Args a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (!guard_pass(a.guard)) return;
-    // C counts the channel slots of the staged copy (cstride = input channels padded to whole workgroups of the
-    // gather-dot); slots beyond the real channels are written as zero planes
-    const int C = a.cstride, H = a.H, W = a.W, k = K ? K : a.k;
-    const int Creal = a.C;
-    const int lane = threadIdx.x & 63;
-    const int nw = (blockDim.x >> 6) / a.ppb;     // waves per window
-    const int sub = (threadIdx.x >> 6) / nw, wave = (threadIdx.x >> 6) % nw;
-    int t = blockIdx.x * a.ppb + sub;
-    const bool active = t < a.items;              // idle wave groups of the last workgroup still reach the barriers
-    if (!active) t = a.items - 1;
-    const int c = t % C; t /= C;
-    const int wx = t % a.nwx; t /= a.nwx;
-    const int wy = t % a.nwy;
-    const int np = t / a.nwy;
-    const int oy0 = wy * a.WY, ox0 = wx * a.WX;
-    const int oh = oy0 + a.WY < a.Hp ? a.WY : a.Hp - oy0, ow = ox0 + a.WX < a.Wp ? a.WX : a.Wp - ox0;
-    const int kr = (k - 1) / 2;
-    const int lw = ow + 2 * kr, lh = oh + 2 * kr;
-    f2* A = reinterpret_cast<f2*>(lds + (size_t)sub * a.lds_item_floats);   // raw [lh][lw], image (oy0 - kr + r, ox0 - kr + xl)
-    f2* B = A + (size_t)lh * lw;                             // [3][lh][ow]
-    const float* tp[6] = {a.taps + kTapGX * kTapPitch, a.taps + kTapAX * kTapPitch, a.taps + kTapCX * kTapPitch,
-                          a.taps + kTapGY * kTapPitch, a.taps + kTapAY * kTapPitch, a.taps + kTapBY * kTapPitch};
-    float tr[6][K ? K : 1];
-    if (K) {
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-#pragma unroll
-            for (int i = 0; i < K; ++i) tr[q][i] = tp[q][i];
-    }
-    auto tap = [&](int q, int i) { return K ? tr[q][i] : tp[q][i]; };
-    const int n0 = 2 * np, n1 = 2 * np + 1;
-    const bool real = c < Creal;
-    const int cs = real ? c : 0;
-    const long p0 = ((long)n0 * Creal + cs) * H * W, p1 = ((long)(n1 < a.N ? n1 : n0) * Creal + cs) * H * W;   // element offsets
-    const float m0 = real ? 1.0f : 0.0f;
-    const float m1 = (real && n1 < a.N) ? 1.0f : 0.0f;
-    // rows x cols of work for this window's waves: a wave per row when the rows are wide, a flat index when they are narrow
-    auto for_each = [&](int rows_, int cols_, auto&& body) {
-        if (cols_ >= 56) {
-            for (int r = wave; r < rows_; r += nw)
-                for (int x = lane; x < cols_; x += 64) body(r, x);
-        } else {
-            for (int t = wave * 64 + lane; t < rows_ * cols_; t += nw * 64) { const int r = t / cols_; body(r, t - r * cols_); }
-        }
-    };
-    // raw window -> LDS, the loads of a batch in flight together (load_phase, dau_common.hpp)
-    auto fill = [&](auto actc) {
-        constexpr int AF = decltype(actc)::value;
-        struct Raw2 { typename RawAct<AF>::type v0, v1; };
-        load_phase<Raw2>(lh, lw, wave, nw, lane,
-            [&](int r, int xl) {
-                const int yy = oy0 - kr + r, xx = ox0 - kr + xl;
-                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                const long off = in ? (long)yy * W + xx : 0;            // outside the image: element 0 (valid), discarded
-                return Raw2{load_raw<AF>(a.in, p0 + off), load_raw<AF>(a.in, p1 + off)};
-            },
-            [&](int r, int xl, Raw2 v) {
-                const int yy = oy0 - kr + r, xx = ox0 - kr + xl;
-                const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                A[r * lw + xl] = f2{mask_act(m0 * act_of(v.v0), in), mask_act(m1 * act_of(v.v1), in)};
-            });
-    };
-    with_act(a.act, fill);
-    __syncthreads();
-    for_each(lh, ow, [&](int r, int x) {
-        const int yy = oy0 - kr + r;
-        f2 h1 = {0.0f, 0.0f}, h2 = {0.0f, 0.0f}, h3 = {0.0f, 0.0f};
-        if (yy >= 0 && yy < H) {
-#pragma unroll
-            for (int i = 0; i < k; ++i) {
-                const f2 v = A[r * lw + x + i];
-                h1 = __builtin_elementwise_fma(v, f2{tap(0, i), tap(0, i)}, h1);
-                h2 = __builtin_elementwise_fma(v, f2{tap(1, i), tap(1, i)}, h2);
-                h3 = __builtin_elementwise_fma(v, f2{tap(2, i), tap(2, i)}, h3);
-            }
-        }
-        B[(0 * lh + r) * ow + x] = h1; B[(1 * lh + r) * ow + x] = h2; B[(2 * lh + r) * ow + x] = h3;
-    });
-    __syncthreads();
-    f8* out = reinterpret_cast<f8*>(a.xk) + ((size_t)np * a.cstride + c) * a.Hp * a.Wp;
-    // KMAX: the maxima are kept as keys (bits << 1) + 2^24: the shift drops the sign, and the addition wraps an Inf / NaN
-    // (exponent 255) below the key of zero, so that an unsigned maximum passes over it: one v_lshl_add_u32 per value, one
-    // v_max3_u32 per pair.  What kmax holds so far is read here, long before it is needed (below).
-    constexpr unsigned kKeyZero = 1u << 24;
-    unsigned km[4] = {kKeyZero, kKeyZero, kKeyZero, kKeyZero}, seen[4] = {0u, 0u, 0u, 0u};
-    if constexpr (KMAX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) seen[q] = __hip_atomic_load(a.kmax + c * kNumK + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for_each(active ? oh : 0, ow, [&](int yr, int xc) {
-        const int yy = oy0 + yr, xx = ox0 + xc;
-        f2 dw = {0.0f, 0.0f}, d1 = {0.0f, 0.0f}, d2 = {0.0f, 0.0f}, ds = {0.0f, 0.0f};
-        if (yy < H && xx < W) {
-#pragma unroll
-            for (int j = 0; j < k; ++j) {
-                const f2 b1 = B[(0 * lh + yr + j) * ow + xc], b2 = B[(1 * lh + yr + j) * ow + xc], b3 = B[(2 * lh + yr + j) * ow + xc];
-                dw = __builtin_elementwise_fma(b1, f2{tap(3, j), tap(3, j)}, dw);
-                d1 = __builtin_elementwise_fma(b2, f2{tap(3, j), tap(3, j)}, d1);
-                d2 = __builtin_elementwise_fma(b1, f2{tap(4, j), tap(4, j)}, d2);
-                ds = __builtin_elementwise_fma(b3, f2{tap(3, j), tap(3, j)}, ds);
-                ds = __builtin_elementwise_fma(b1, f2{tap(5, j), tap(5, j)}, ds);
-            }
-        }
-        out[(size_t)yy * a.Wp + xx] = f8{dw.x, dw.y, d1.x, d1.y, d2.x, d2.y, ds.x, ds.y};
-        if constexpr (KMAX) {
-            const f2 kv[4] = {dw, d1, d2, ds};
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                km[q] = max(max(km[q], (__float_as_uint(kv[q].x) << 1) + kKeyZero), (__float_as_uint(kv[q].y) << 1) + kKeyZero);
-        }
-    });
-    if constexpr (KMAX) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned m = km[q];
-            for (int o = 32; o >= 1; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-            // a maximum only grows: a value that does not exceed what was there when the workgroup began changes nothing (a
-            // stale, smaller reading only costs the atomic) -- most waves issue none, and none waits for one
-            const unsigned bits = (m - kKeyZero) >> 1;
-            if (lane == 0 && bits > seen[q]) atomicMax(a.kmax + c * kNumK + q, bits);
-        }
-    }
-}
+#define DAU_BLUR4_KERNEL blur4_pack_kernel
+#define DAU_BLUR4_NHWC false
+#include "k_blur4_pack_body.hpp"
+#undef DAU_BLUR4_KERNEL
+#undef DAU_BLUR4_NHWC
+#define DAU_BLUR4_KERNEL blur4_pack_nhwc_kernel
+#define DAU_BLUR4_NHWC true
+#include "k_blur4_pack_body.hpp"
+#undef DAU_BLUR4_KERNEL
+#undef DAU_BLUR4_NHWC
 
 // per-lane parameters: params[sub][s][gb][gp][fb][lane][8] = {b00, b01, b10, b11, base, 0, 0, 0}
 // lane = half*32 + fl ; unit = (s, g = g_begin + gb*2*GP + 2*gp + half, f = fb*32 + fl); invalid units get zero factors.
@@ -1373,17 +1282,26 @@ const void* blur4_pack_pick(int blur_k) {
               : blur_k == 9 ? blur4_pack_kernel<9, KMAX> : blur4_pack_kernel<0, KMAX>;
     return reinterpret_cast<const void*>(kern);
 }
-const void* blur4_pack_for(int blur_k, bool kmax = false) { return kmax ? blur4_pack_pick<true>(blur_k) : blur4_pack_pick<false>(blur_k); }
+template <bool KMAX>
+const void* blur4_pack_nhwc_pick(int blur_k) {
+    auto kern = blur_k == 7 ? blur4_pack_nhwc_kernel<7, KMAX> : blur_k == 5 ? blur4_pack_nhwc_kernel<5, KMAX>
+              : blur_k == 9 ? blur4_pack_nhwc_kernel<9, KMAX> : blur4_pack_nhwc_kernel<0, KMAX>;
+    return reinterpret_cast<const void*>(kern);
+}
+const void* blur4_pack_for(int blur_k, bool kmax = false, bool nhwc = false) {
+    if (nhwc) return kmax ? blur4_pack_nhwc_pick<true>(blur_k) : blur4_pack_nhwc_pick<false>(blur_k);
+    return kmax ? blur4_pack_pick<true>(blur_k) : blur4_pack_pick<false>(blur_k);
+}
 
 }  // namespace
 
-// x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1;
+// x[N,C,H,W] (nhwc: [N,H,W,C]) -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1;
 // kmax != nullptr: kmax[cstride][4 kinds] (float bits, zeroed by the caller) receives max |value| over the finite values
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax) {
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax, bool nhwc) {
     int wy, wx; size_t blur_lds;
     blur4_plan(blur_k, Hp, Wp, &wy, &wx, &blur_lds);
-    const void* kern = blur4_pack_for(blur_k, kmax != nullptr);
+    const void* kern = blur4_pack_for(blur_k, kmax != nullptr, nhwc);
     Blur4Args b{};
     b.guard = guard;
     b.in = x; b.taps = filters + kTaps1dOffset; b.xk = xk; b.kmax = kmax;
@@ -1404,8 +1322,8 @@ void launch_dot_reduce(hipStream_t st, const void* partial, int partial_f32, lon
     hipLaunchKernelGGL(dot_reduce_kernel, dim3(rgrid), dim3(256), 0, st, partial, partial_f32, n, G, F, g_split, slabs0, slabs1,
                        zero_from, accumulate ? 1 : 0, r4, guard);
 }
-void blur4_pack_init(int blur_k, bool kmax) {
-    (void)hipFuncSetAttribute(blur4_pack_for(blur_k, kmax), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+void blur4_pack_init(int blur_k, bool kmax, bool nhwc) {
+    (void)hipFuncSetAttribute(blur4_pack_for(blur_k, kmax, nhwc), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 bool blur4_pack_fits(int blur_k, int Hp, int Wp) {
     int wy, wx; size_t blur_lds;
@@ -1447,7 +1365,7 @@ void tiled_dot_init(const TiledDotConfig& c) {
     const DotGeometry g = make_dot_geometry(c.sh, c.R, c.as1, c.one_tile, c.rounds, c.rw8);
     for (int i = 0; i < g.npass; ++i) dispatch_dot(g.nsub1 > 1, c.ring, g.RW, g.RH, g.pass[i].GP, g.pass[i].AS, nullptr, nullptr, 0, 0);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pack_error_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(blur4_pack_for(c.blur_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(blur4_pack_for(c.blur_k, false, c.nhwc != 0), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& c, const float* x, const float* dy, const float* filters,
@@ -1461,11 +1379,17 @@ void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& c, const float* x, 
         const int cwmax = s.W < kPackErrorChunk ? s.W : kPackErrorChunk;
         const size_t lds = (size_t)64 * (cwmax | 1) * 4;
         const int nxc = (g.EX + kPackErrorChunk - 1) / kPackErrorChunk;
-        hipLaunchKernelGGL(pack_error_kernel, dim3(c.NP * g.nfb * g.EY * nxc), dim3(256), lds, st, dy, s.N, s.F, s.H, s.W, g.Rp, g.EX,
-                           g.EY, g.nfb, drop_col, drop_row, c.act, reinterpret_cast<float*>(ws + l.ep_off), guard);
+        if (c.nhwc) {
+            hipLaunchKernelGGL(pack_error_kernel_nhwc, dim3(c.NP * g.nfb * g.EY * nxc), dim3(256), 0, st, dy, s.N, s.F, s.H, s.W, g.Rp, g.EX,
+                               g.EY, g.nfb, drop_col, drop_row, c.act, reinterpret_cast<float*>(ws + l.ep_off), guard);
+        } else {
+            hipLaunchKernelGGL(pack_error_kernel, dim3(c.NP * g.nfb * g.EY * nxc), dim3(256), lds, st, dy, s.N, s.F, s.H, s.W, g.Rp, g.EX,
+                               g.EY, g.nfb, drop_col, drop_row, c.act, reinterpret_cast<float*>(ws + l.ep_off), guard);
+        }
     }
     // channel slots beyond S (padding of the last input-channel block) are written as zero planes by the kernel
-    launch_blur4_pack(st, x, filters, s.N, s.S, s_pad, s.H, s.W, g.Hp, g.Wp, c.blur_k, c.act, reinterpret_cast<float*>(ws + l.xk_off), guard);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s_pad, s.H, s.W, g.Hp, g.Wp, c.blur_k, c.act, reinterpret_cast<float*>(ws + l.xk_off), guard,
+                      nullptr, c.nhwc != 0);
     if (g.nsub1 > 1) {
         const DotGeometry::Pass& ps = g.pass[0];
         hipLaunchKernelGGL(dot_worklist_kernel, dim3(g.nsub1 * g.nsub1 * g.nfb * ps.nsb), dim3(1024), 0, st, table_bare, s.S, s.G, s.F,

@@ -225,18 +225,22 @@ struct BlurPackArgs {
 };
 
 // K: compile-time prefilter support (taps live in SGPRs, tap loops unrolled); K = 0: any support, taps re-read per use
-template <int K>
+// KN = K | kNhwcArg: `in` is [N][H][W][C] (a lane's loads are C elements apart, so the workgroups of a window's channels are made
+// neighbours on one XCD, whose L2 then serves the lines they share)
+template <int KN>
 #ifndef DAU_BLUR_WAVES_PER_EU
 #define DAU_BLUR_WAVES_PER_EU 6
 #endif
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BLUR_WAVES_PER_EU))) blur_pack_kernel(const BlurPackArgs a) {
+    constexpr int K = KN & (kNhwcArg - 1);
+    constexpr bool NHWC = (KN & kNhwcArg) != 0;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (!guard_pass(a.guard)) return;
     const int C = a.C, H = a.H, W = a.W, R = a.R, k = K ? K : a.k;
     const int lane = threadIdx.x & 63;
     const int nw = (blockDim.x >> 6) / a.ppb;     // waves per plane
     const int sub = (threadIdx.x >> 6) / nw, wave = (threadIdx.x >> 6) % nw;
-    int pid = blockIdx.x * a.ppb + sub;
+    int pid = (NHWC ? xcd_contiguous_id(blockIdx.x, gridDim.x) : blockIdx.x) * a.ppb + sub;
     const bool active = pid < a.planes;           // the last workgroup may have idle wave groups (they still reach the barriers)
     if (!active) pid = a.planes - 1;
     const int band = pid % a.bands; pid /= a.bands;
@@ -267,7 +271,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
     auto gx = [&](int i) { return K ? gxr[i] : gxp[i]; };
     auto gy = [&](int i) { return K ? gyr[i] : gyp[i]; };
     const int n0 = 2 * np, n1 = 2 * np + 1;
-    const long p0 = ((long)n0 * C + c) * H * W, p1 = ((long)(n1 < a.N ? n1 : n0) * C + c) * H * W;   // element offsets
+    const long p0 = NHWC ? (long)n0 * H * W * C + c : ((long)n0 * C + c) * H * W;                    // element offsets
+    const long p1 = NHWC ? (long)(n1 < a.N ? n1 : n0) * H * W * C + c : ((long)(n1 < a.N ? n1 : n0) * C + c) * H * W;
     const float m1 = n1 < a.N ? 1.0f : 0.0f;      // odd batch: the second image of the last pair is zero
     // rows x cols of work for this plane's waves: a wave per row when the rows are wide, a flat index when they are narrow
     // (a 7-pixel row would leave most of a wave idle)
@@ -288,7 +293,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
             [&](int r, int xl) {
                 const int yy = ya0 - kr + r, xx = xa0 - kr + xl;
                 const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                const long off = in ? (long)yy * W + xx : 0;            // outside the image: element 0 (valid), discarded
+                const long off = in ? (NHWC ? ((long)yy * W + xx) * C : (long)yy * W + xx) : 0;   // outside the image: element 0 (valid), discarded
                 return Raw2{load_raw<AF>(a.in, p0 + off), load_raw<AF>(a.in, p1 + off)};
             },
             [&](int r, int xl, Raw2 v) {
@@ -417,7 +422,7 @@ __global__ void pack_units_binned_kernel(const UnitRef* __restrict__ table, int 
 struct GatherArgs {
     const char* staged;        // [NP][Cin][plane_bytes]
     const char* packed;        // [NFB][Cin][ut_stride]
-    float* out;                // [N][Cout][H][W]
+    float* out;                // [N][Cout][H][W] (traits NhwcOut<>: [N][H][W][Cout])
     int N, Cin, Cout, G, H, W, R;
     int npx, npy;              // patches per image (EDGE variants: 8*TY x 8*TX pixels each)
     int ph, pw;                // patch size in pixels (non-EDGE variants: at most 8*TY - 1 by 8*TX - 1)
@@ -586,7 +591,8 @@ __device__ __forceinline__ void unit_group(f4 (&acc)[KP][2], unsigned ut_addr0, 
 // Whole per-wave program for one PART (the part only selects which tiles the wave owns, so that all
 // LDS immediates are compile-time constants; every wave runs the same number of barriers).
 // H16: out is binary16 (a compile-time instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
-template <class T, int PART, bool H16>
+// NHWC: out is [N][H][W][Cout] (gather_mfma_kernel<NhwcOut<T>, H16>)
+template <class T, int PART, bool H16, bool NHWC = false>
 __device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int lane, int wave, int fi) {
     // lagged kernels: the waves of the second half (SIMD partners of the first) run one unit behind (GatherTraits::NB)
     const bool lag = T::LAGGED && wave >= T::kWaves / 2;
@@ -761,7 +767,7 @@ __device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int
                 const float v = zf[0] + zf[zplane + 1] + zf[2 * zplane + zpitch] + zf[3 * zplane + zpitch + 1];
                 if (npp < npp_total && n < a.N && f < a.Cout && gy < a.H && gx < a.W)
                 {
-                    const long o = ((long)n * a.Cout + f) * plane_out + (long)gy * a.W + gx;
+                    const long o = NHWC ? nhwc_index(n, f, gy, gx, a.Cout, a.H, a.W) : ((long)n * a.Cout + f) * plane_out + (long)gy * a.W + gx;
                     if constexpr (H16) store_act_t<kActF16>(a.out, o, v, a.accumulate != 0);
                     else store_act(a.out, o, v, a.act != 0, a.accumulate != 0);          // act: kActF32 or kActBF16
                 }
@@ -778,6 +784,12 @@ __global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const GatherAr
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int part = wave % SPLIT, fi = wave / SPLIT;
+    if constexpr (IsNhwcOut<T>::value) {
+        if (SPLIT == 1 || part == 0) gather_body<T, 0, H16, true>(a, smem, lane, wave, fi);
+        else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1, H16, true>(a, smem, lane, wave, fi); }
+        else if (SPLIT == 3 || part == 2) { if constexpr (SPLIT > 2) gather_body<T, 2, H16, true>(a, smem, lane, wave, fi); }
+        else { if constexpr (SPLIT > 3) gather_body<T, 3, H16, true>(a, smem, lane, wave, fi); }
+    } else
     if (SPLIT == 1 || part == 0) gather_body<T, 0, H16>(a, smem, lane, wave, fi);
     else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1, H16>(a, smem, lane, wave, fi); }
     else if (SPLIT == 3 || part == 2) { if constexpr (SPLIT > 2) gather_body<T, 2, H16>(a, smem, lane, wave, fi); }
@@ -791,57 +803,61 @@ namespace {
 
 // a == nullptr: raise the kernel's dynamic-LDS limit (once per plan and device, tiled_gather_init); else launch
 // h16: the instantiation with binary16 output (DAU_FLAG_IO_F16)
+// nhwc: the instantiations that store [N][H][W][Cout] (DAU_FLAG_IO_NHWC)
 template <class T>
-void launch_variant(hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16) {
-    auto kern = h16 ? gather_mfma_kernel<T, true> : gather_mfma_kernel<T, false>;
+void launch_variant(hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16, bool nhwc) {
+    auto kern = nhwc ? (h16 ? gather_mfma_kernel<NhwcOut<T>, true> : gather_mfma_kernel<NhwcOut<T>, false>)
+                     : (h16 ? gather_mfma_kernel<T, true> : gather_mfma_kernel<T, false>);
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, *a);
 }
 
-void dispatch_variant(int variant, hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16) {
+void dispatch_variant(int variant, hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16, bool nhwc) {
     switch (variant) {
-        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16); break;
-        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16); break;
-        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds, h16); break;
-        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds, h16); break;
-        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds, h16); break;
-        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds, h16); break;
-        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds, h16); break;
+        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16, nhwc); break;
+        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16, nhwc); break;
+        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds, h16, nhwc); break;
+        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
+        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
+        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
+        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds, h16, nhwc); break;
 #ifdef DAU_TUNING
-        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds, h16); break;
+        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds, h16, nhwc); break;
 #endif
-        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds, h16); break;
-        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds, h16); break;
-        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds, h16); break;
-        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds, h16); break;
-        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds, h16); break;
-        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds, h16); break;
-        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds, h16); break;
-        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds, h16); break;
-        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds, h16); break;
-        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds, h16); break;
-        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds, h16); break;
+        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds, h16, nhwc); break;
+        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds, h16, nhwc); break;
+        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds, h16, nhwc); break;
+        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds, h16, nhwc); break;
+        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds, h16, nhwc); break;
+        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds, h16, nhwc); break;
+        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds, h16, nhwc); break;
+        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds, h16, nhwc); break;
+        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds, h16, nhwc); break;
+        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc); break;
+        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc); break;
 #ifdef DAU_TUNING
-        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds, h16); break;
+        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds, h16, nhwc); break;
 #endif
 #ifdef DAU_TUNING
-        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds, h16); break;
+        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds, h16, nhwc); break;
 #endif
-        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
-        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
-        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds, h16); break;
+        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
+        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
+        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
 #ifdef DAU_TUNING                // explicit-request rows (Variant::tuning != 0) exist in the tuning build only
-        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16); break;
-        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16); break;
-        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16); break;
-        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16); break;
+        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc); break;
+        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc); break;
+        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc); break;
+        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc); break;
 #endif
         default: break;
     }
 }
 
-auto blur_pack_for(int blur_k) {
+auto blur_pack_for(int blur_k, bool nhwc) {
     // sigma = 0.5 (the reference's default) gives a 7-tap prefilter; other supports take the generic instantiation
+    constexpr int NH = kNhwcArg;
+    if (nhwc) return blur_k == 7 ? blur_pack_kernel<7 | NH> : blur_k == 5 ? blur_pack_kernel<5 | NH> : blur_k == 9 ? blur_pack_kernel<9 | NH> : blur_pack_kernel<0 | NH>;
     return blur_k == 7 ? blur_pack_kernel<7> : blur_k == 5 ? blur_pack_kernel<5> : blur_k == 9 ? blur_pack_kernel<9> : blur_pack_kernel<0>;
 }
 
@@ -896,8 +912,8 @@ size_t tiled_gather_workspace_bytes(const TiledConfig& c) {
 }
 
 void tiled_gather_init(const TiledConfig& c) {
-    dispatch_variant(c.variant, nullptr, nullptr, 0, 0, c.act == kActF16);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur_pack_for(c.blur_k)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    dispatch_variant(c.variant, nullptr, nullptr, 0, 0, c.act == kActF16, c.nhwc != 0);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur_pack_for(c.blur_k, c.nhwc != 0)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 int tiled_gather_windows(const TiledConfig& c) { return c.windows; }
@@ -910,7 +926,7 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
     const int bands = blur_pack_bands(g, c.blur_k);
     const int band_rows = (g.rows + bands - 1) / bands;
     const size_t blur_lds = blur_pack_lds_bytes(g, c.blur_k, band_rows);
-    auto kern = blur_pack_for(c.blur_k);
+    auto kern = blur_pack_for(c.blur_k, c.nhwc != 0);
     BlurPackArgs b{};
     b.guard = guard;
     b.in = in; b.taps = filters + kTaps1dOffset; b.staged = reinterpret_cast<float*>(staged);
@@ -972,7 +988,7 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.debug = c.debug;
     const int grid = ((c.NP * c.patches + g.sk - 1) / g.sk) * a.nfb;
     const size_t lds = lds_bytes(c, g);
-    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16);
+    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16, c.nhwc != 0);
 }
 
 }  // namespace dau

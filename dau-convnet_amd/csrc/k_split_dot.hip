@@ -170,6 +170,23 @@ __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restric
     if ((threadIdx.x & 63) == 0) atomicMax(&emax[f], __float_as_uint(m));
 }
 
+// the same maxima from an [N][H][W][F] dy (DAU_FLAG_IO_NHWC): a workgroup takes 64 consecutive channels, a lane one of them, and its
+// four waves every fourth pixel of the workgroup's share; grid (ceil(F / 64), split).  A maximum does not depend on the order.
+__global__ void __launch_bounds__(256) sd_absmax_nhwc_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
+                                                               unsigned* __restrict__ emax, const Guard guard) {
+    if (!guard_pass(guard)) return;
+    const int nfb = (F + 63) / 64;
+    const int f = (blockIdx.x % nfb) * 64 + (threadIdx.x & 63), part = blockIdx.x / nfb;
+    if (f >= F) return;
+    float m = 0.0f;
+    const long total = (long)N * HW;
+    for (long i = part * 4L + (threadIdx.x >> 6); i < total; i += 4L * split) {
+        float a;
+        if (finite_abs(load_act(dy, i * F + f, act), &a)) m = fmaxf(m, a);
+    }
+    atomicMax(&emax[f], __float_as_uint(m));
+}
+
 __device__ __forceinline__ void split_limbs(float v, _Float16* hi, _Float16* lo) {
     const _Float16 h = (_Float16)v;
     const float hf = (float)h;
@@ -280,7 +297,7 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
 // (the earlier form) one thread per (oct, fb, Vy, Vx), the 16 channels of the block
 __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
                                                          int F, int H, int W, int octs, int nfb, int EYs, int EXs, int drop_col,
-                                                         int drop_row, int act, h8* __restrict__ es, const Guard guard) {
+                                                         int drop_row, int act, int nhwc, h8* __restrict__ es, const Guard guard) {
     if (!guard_pass(guard)) return;
     const long total = (long)octs * nfb * EYs * EXs;
     const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
@@ -300,7 +317,7 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int n = oct * 8 + i;
-                const float v = (in && f < F && n < N) ? load_act(dy, (((long)n * F + f) * H + y) * W + x, act) : 0.0f;
+                const float v = (in && f < F && n < N) ? load_act(dy, nhwc ? nhwc_index(n, f, y, x, F, H, W) : (((long)n * F + f) * H + y) * W + x, act) : 0.0f;
                 _Float16 h, l;
                 split_limbs(v * sc, &h, &l);
                 hi[i] = h; lo[i] = l;
@@ -357,6 +374,56 @@ __global__ void __launch_bounds__(256) sd_stage_e1_kernel(const float* __restric
         h8 piece = {0, 0, 0, 0, 0, 0, 0, 0};
         if (vx >= c0 && vx < c1) piece = tile[lx * kSdFB + ((q & 15) ^ (lx & 7))];
         dst[q] = piece;
+    }
+}
+
+// ES (LIMBS = 2) or ES1 (LIMBS = 1) from an [N][H][W][F] dy (DAU_FLAG_IO_NHWC): the workgroups, window rows and column tiles of the two
+// kernels above.  The sixteen channels of a position, which ES keeps together, are one contiguous run of the input, so nothing goes
+// through LDS: a thread takes one (position, channel) -- sixteen lanes read the sixteen channels of a pixel, once per image of the
+// octet -- scales and splits as above and stores its one or two 16-byte pieces, consecutive lanes to consecutive addresses.  Halo
+// positions (the edge rule's dropped row / column included), channels beyond F and images beyond N are masked to +0 and give zero pieces.
+template <int LIMBS>
+__global__ void __launch_bounds__(256) sd_stage_nhwc_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
+                                                              int F, int H, int W, int nfb, int EYs, int EXs, int nct, int TX,
+                                                              int drop_col, int drop_row, int act, h8* __restrict__ es,
+                                                              const Guard guard) {
+    if (!guard_pass(guard)) return;
+    int t = blockIdx.x;
+    const int ct = t % nct; t /= nct;
+    const int vy = t % EYs; t /= EYs;
+    const int fb = t % nfb;
+    const int oct = t / nfb;
+    const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
+    const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
+    const int y = vy - (kSdR + 1);
+    // its columns inside the image: [c0, c1)
+    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    h8* dst = es + ((((size_t)oct * nfb + fb) * EYs + vy) * EXs + vx0) * (kSdFB * LIMBS);
+    for (int i = threadIdx.x; i < nvx * kSdFB; i += 256) {
+        const int lx = i / kSdFB, fl = i - lx * kSdFB, vx = vx0 + lx, x = vx - (kSdR + 1);
+        const int f = fb * kSdFB + fl;
+        const bool in = vx >= c0 && vx < c1 && f < F;
+        const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
+        float v[8];
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int img = oct * 8 + n;
+            const bool ok = in && img < N;
+            v[n] = mask_act(load_act(dy, ok ? nhwc_index(img, f, y, x, F, H, W) : 0, act), ok);
+        }
+        h8 hi, lo;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            if constexpr (LIMBS == 2) {
+                _Float16 h, l;
+                split_limbs(v[n] * sc, &h, &l);
+                hi[n] = h; lo[n] = l;
+            } else {
+                hi[n] = (_Float16)(v[n] * sc);
+            }
+        }
+        dst[lx * (kSdFB * LIMBS) + fl] = hi;
+        if constexpr (LIMBS == 2) dst[lx * (kSdFB * LIMBS) + kSdFB + fl] = lo;
     }
 }
 
@@ -735,9 +802,9 @@ size_t split_dot_workspace_bytes(const SplitDotConfig& c) { return sd_layout(c, 
 void split_dot_init(const SplitDotConfig& c) {
     dispatch_sd(c.RW, c.e_limbs, nullptr, nullptr, 0);
 #ifndef DAU_SD_STAGE_REF
-    blur4_pack_init(c.blur_k, true);
+    blur4_pack_init(c.blur_k, true, c.nhwc != 0);
 #else
-    blur4_pack_init(c.blur_k);
+    blur4_pack_init(c.blur_k, false, c.nhwc != 0);
 #endif
 }
 
@@ -754,29 +821,45 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
     const int HW = s.H * s.W;
 #ifndef DAU_SD_STAGE_REF
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax, c.nhwc != 0);
 #else
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, nullptr, c.nhwc != 0);
     const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
     hipLaunchKernelGGL(sd_absmax_x_kernel, dim3(s.S * xsplit), dim3(256), 0, st, xk, g.NP, s.S, HW, xsplit, xmax, guard);
 #endif
-    const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
-    hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
+    if (c.nhwc) {
+        const int nfb64 = (s.F + 63) / 64;
+        const int esplit = (int)std::max(1L, std::min((long)(2048 / nfb64), ((long)s.N * HW + 3) / 4));
+        hipLaunchKernelGGL(sd_absmax_nhwc_e_kernel, dim3(nfb64 * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
+    } else {
+        const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
+        hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
+    }
     hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
                        reinterpret_cast<h8*>(ws + l.xs_off), guard);
     if (c.e_limbs == 1) {
         const int nct = (g.EXs + kSe1TX - 1) / kSe1TX, tx = (g.EXs + nct - 1) / nct;  // column tiles of a window row, evenly wide
+        if (c.nhwc) {
+            hipLaunchKernelGGL(sd_stage_nhwc_e_kernel<1>, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F,
+                               s.H, s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+            return;
+        }
         hipLaunchKernelGGL(sd_stage_e1_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F,
                            s.H, s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
         return;
     }
 #ifndef DAU_SD_STAGE_REF
     const int nct = (g.EXs + kSeTX - 1) / kSeTX, tx = (g.EXs + nct - 1) / nct;    // column tiles of a window row, evenly wide
+    if (c.nhwc) {
+        hipLaunchKernelGGL(sd_stage_nhwc_e_kernel<2>, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F,
+                           s.H, s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+        return;
+    }
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F, s.H,
                        s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
 #else
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3(4096), dim3(256), 0, st, dy, emax, s.N, s.F, s.H, s.W, g.octs, g.nfb, g.EYs, g.EXs,
-                       drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+                       drop_col, drop_row, c.act, c.nhwc, reinterpret_cast<h8*>(ws + l.es_off), guard);
 #endif
 }
 

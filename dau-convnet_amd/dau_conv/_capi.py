@@ -28,6 +28,7 @@ FLAG_DENSE_SPLIT_F16 = 1 << 9      # gather-sum passes of calls with |mu| <= 2 /
 FLAG_NO_DENSE_SPLIT = 1 << 10      # never (default: the radii that pay for the plan's unit count)
 FLAG_DENSE_SPLIT_OUTLIERS = 1 << 12   # opt-in: calls within +-4 with few units beyond +-3 run the radius-3 two-limb GEMM plus a sparse ring pass
 FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernels and arithmetic, parameters and their gradients float32
+FLAG_IO_NHWC = 1 << 13  # x, y, dy, dx are channels_last: [N][H][W][C] in memory; the NCHW plan of the same desc in everything but addresses
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED = 0, 1, 2
 PASS_FORWARD, PASS_BACKWARD = 1, 2
@@ -139,9 +140,10 @@ def _same_device(*tensors):
     return dev
 
 
-def _req(t, name, shape=None, dtype=torch.float32):
-    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous()):
-        raise InvalidArgumentError("%s must be a contiguous %s tensor on the GPU" % (name, str(dtype).replace("torch.", "")))
+def _req(t, name, shape=None, dtype=torch.float32, memory_format=torch.contiguous_format):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous(memory_format=memory_format)):
+        raise InvalidArgumentError("%s must be a %s %s tensor on the GPU" % (
+            name, "channels_last" if memory_format == torch.channels_last else "contiguous", str(dtype).replace("torch.", "")))
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise InvalidArgumentError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
     return t
@@ -170,6 +172,8 @@ class Plan(object):
             _check(lib.dau_conv_plan_create(ctypes.byref(d), ctypes.byref(self._h)))
         self.N, self.S, self.F, self.G, self.H, self.W = N, S, F, G, H, W
         self.io_dtype = torch.bfloat16 if int(flags) & FLAG_IO_BF16 else torch.float16 if int(flags) & FLAG_IO_F16 else torch.float32
+        # FLAG_IO_NHWC: activations of logical shape [N, C, H, W] with channels_last strides, in and out
+        self._io_format = torch.channels_last if int(flags) & FLAG_IO_NHWC else torch.contiguous_format
         info = _Info()
         _check(lib.dau_conv_plan_get_info(self._h, ctypes.byref(info)))
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}
@@ -180,6 +184,11 @@ class Plan(object):
         if h and lib is not None:        # at interpreter shutdown the module globals may already be gone
             lib.dau_conv_plan_destroy(h)
             self._h = None
+
+    @property
+    def io_layout(self):
+        """"NHWC" for a FLAG_IO_NHWC plan (x, y, dy, dx are channels_last tensors), else "NCHW"."""
+        return "NHWC" if self._io_format == torch.channels_last else "NCHW"
 
     def workspace_bytes(self, which):
         n = ctypes.c_size_t()
@@ -198,13 +207,13 @@ class Plan(object):
 
     def forward(self, x, w, mu1, mu2, sigma):
         pshape = (1, self.S, self.G, self.F)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype)
+        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
         for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
             _req(t, n, pshape)
         dev = _same_device(x, w, mu1, mu2, sigma)
         # the library launches on the CURRENT device: make that the tensors' device for the duration of the call
         with torch.cuda.device(dev):
-            y = torch.empty((self.N, self.F, self.H, self.W), dtype=self.io_dtype, device=dev)
+            y = torch.empty((self.N, self.F, self.H, self.W), dtype=self.io_dtype, device=dev, memory_format=self._io_format)
             ws = self._workspace(PASS_FORWARD, dev)
             _check(lib.dau_conv_forward(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma), _ptr(y),
                                         _ptr(ws), ws.numel()))
@@ -213,14 +222,14 @@ class Plan(object):
 
     def backward(self, x, dy, w, mu1, mu2, sigma, need_mask=NEED_ALL):
         pshape = (1, self.S, self.G, self.F)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype)
-        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype)
+        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
+        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype, self._io_format)
         for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
             _req(t, n, pshape)
         dev = _same_device(x, dy, w, mu1, mu2, sigma)
         new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            dx = torch.empty(x.shape, dtype=self.io_dtype, device=dev) if need_mask & NEED_DX else None
+            dx = torch.empty(x.shape, dtype=self.io_dtype, device=dev, memory_format=self._io_format) if need_mask & NEED_DX else None
             dw = new(pshape) if need_mask & NEED_DW else None
             dmu1 = new(pshape) if need_mask & NEED_DMU1 else None
             dmu2 = new(pshape) if need_mask & NEED_DMU2 else None
@@ -236,8 +245,8 @@ class Plan(object):
         """Raw parameter-gradient sums [4, S, G, F] (kinds w, mu1, mu2, sigma) of this batch: linear in the batch, so a
         data-parallel caller all-reduces THIS buffer and only then calls finalize_param_grads()."""
         pshape = (1, self.S, self.G, self.F)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype)
-        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype)
+        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
+        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype, self._io_format)
         for t, n in ((mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
             _req(t, n, pshape)
         dev = _same_device(x, dy, mu1, mu2, sigma, out)

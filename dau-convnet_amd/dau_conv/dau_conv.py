@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import _capi
 
 __all__ = ["DAUGridMean", "ZeroNLast", "DAUConv2d", "DAUConv1d", "dau_conv2d", "dau_conv1d", "dau_conv",
-           "dau_conv_grad", "check_pending_offsets"]
+           "dau_conv_grad", "check_pending_offsets", "is_channels_last"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -44,7 +44,34 @@ _PLANS = collections.OrderedDict()
 _PLAN_CACHE_MAX = 64
 
 
-def _get_plan(x, w, settings):
+def is_channels_last(t):
+    """True for a rank-4 tensor laid out [N][H][W][C] in memory (torch.channels_last) and not also NCHW-contiguous: tensors
+    whose strides fit both (C = 1, or H = W = 1) count as contiguous."""
+    return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+# channels_last=None: does a channels_last input of this dtype run the NHWC plan?  Decided by measurement (DESIGN.md 5.5b): the
+# NHWC plan against what a channels_last model pays around the NCHW plan -- x.contiguous(), y -> channels_last, dy.contiguous(),
+# dx -> channels_last -- at the north-star layer: 23.66 against 25.66 ms (float32), 23.03 against 24.46 (float16), 21.18 against
+# 22.53 (bfloat16), the rounds of one box within 0.1 ms of each other.  channels_last=True runs the NHWC plan whatever this table says.
+_NHWC_BY_DEFAULT = {torch.float32: True, torch.float16: True, torch.bfloat16: True}
+# plan keys whose NHWC form the library refused (shapes that fall back to the direct kernels): asked once, then today's path
+_NHWC_REFUSED = set()
+
+
+def _wants_nhwc(x, settings):
+    """Should this call run an NHWC plan, as far as the input and the settings go (the library may still refuse the shape)."""
+    cl = settings["channels_last"]
+    if cl is False or not is_channels_last(x):
+        return False
+    if x.dtype == torch.bfloat16 and settings["dense_bf16"]:
+        return False                     # DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16: that layer converts, as before
+    return True if cl is True else _NHWC_BY_DEFAULT.get(x.dtype, False)
+
+
+def _get_plan(x, w, settings, nhwc=False):
+    """The cached plan of this call.  nhwc: the FLAG_IO_NHWC plan if the library builds one for the shape, else the NCHW plan
+    (Plan.io_layout tells which came back)."""
     N, S, H, W = x.shape
     _, S2, G, F = w.shape
     if S2 != S:
@@ -81,16 +108,32 @@ def _get_plan(x, w, settings):
     # opt-in: calls within +-4 with few units beyond +-3 keep the radius-3 dense GEMM, plus a ring pass over those units' outer taps
     if settings["dense_outliers"] and not (flags & (_capi.FLAG_DENSE_BF16 | _capi.FLAG_NO_DENSE_SPLIT)):
         flags |= _capi.FLAG_DENSE_SPLIT_OUTLIERS
-    key = (N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], flags, settings["algo"],
-           _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"]), x.device.index)
-    plan = _PLANS.get(key)
-    if plan is not None:
-        _PLANS.move_to_end(key)
-        return plan
-    plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=settings["kernel_size"],
-                      number_units_ignore=settings["number_units_ignore"], flags=flags, algo=settings["algo"],
-                      sigma_hint=settings["sigma_hint"], mu_learning_rate_factor=settings["mu_learning_rate_factor"],
-                      device=x.device)
+    make_key = lambda fl: (N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], fl, settings["algo"],
+                           _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"]), x.device.index)
+    make_plan = lambda fl: _capi.Plan(N, S, F, G, H, W, max_kernel_size=settings["kernel_size"],
+                                      number_units_ignore=settings["number_units_ignore"], flags=fl, algo=settings["algo"],
+                                      sigma_hint=settings["sigma_hint"], mu_learning_rate_factor=settings["mu_learning_rate_factor"],
+                                      device=x.device)
+    plan = None
+    if nhwc and make_key(flags | _capi.FLAG_IO_NHWC) not in _NHWC_REFUSED:
+        key = make_key(flags | _capi.FLAG_IO_NHWC)
+        plan = _PLANS.get(key)
+        if plan is not None:
+            _PLANS.move_to_end(key)
+            return plan
+        try:
+            plan = make_plan(flags | _capi.FLAG_IO_NHWC)
+        except _capi.InvalidArgumentError as e:
+            if "DAU_FLAG_IO_NHWC" not in str(e):
+                raise
+            _NHWC_REFUSED.add(key)       # no tiled kernels for this shape / algo: the NCHW plan below, as without the feature
+    if plan is None:
+        key = make_key(flags)
+        plan = _PLANS.get(key)
+        if plan is not None:
+            _PLANS.move_to_end(key)
+            return plan
+        plan = make_plan(flags)
     if settings["algo"] == _capi.ALGO_AUTO and _capi.ALGO_DIRECT in (plan.info["algo_forward"], plan.info["algo_backward"]):
         # the LDS-tiled kernels refused this shape (e.g. more than 16 units per channel pair under a kernel larger than 17, a
         # prefilter window or error row larger than the LDS): correct, but orders of magnitude slower -- say so once per plan
@@ -135,7 +178,7 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
               merge_threshold=1, unit_testing=False, mu_learning_rate_factor=1.0, single_dim_kernel=False,
               forbid_positive_dim1=False, use_interpolation=True, sigma_hint=None, check_offsets="async",
               algo=_capi.ALGO_AUTO, dense_bf16=False, dense_split=None, process_group=None, grad_reduce="mean", name=None,
-              dense_outliers=False):
+              dense_outliers=False, channels_last=None):
     if not unit_normalization or square_unit_normalization:
         raise _capi.InvalidArgumentError("only unit_normalization=True, square_unit_normalization=False is implemented")
     if sigma_hint is None:
@@ -151,11 +194,19 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
                 use_interpolation=bool(use_interpolation), sigma_hint=float(sigma_hint),
                 check_offsets=mode, algo=int(algo), dense_bf16=bool(dense_bf16),
                 dense_split=(None if dense_split is None else bool(dense_split)), dense_outliers=bool(dense_outliers),
-                process_group=process_group, grad_reduce=grad_reduce)
+                process_group=process_group, grad_reduce=grad_reduce,
+                channels_last=(None if channels_last is None else bool(channels_last)))
 
 
 def _c(t):
     return t.contiguous() if not t.is_contiguous() else t
+
+
+def _act(t, plan):
+    """An activation in the layout the plan takes: channels_last for an NHWC plan, contiguous otherwise; copied only if it is not."""
+    if plan.io_layout == "NHWC":
+        return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
+    return _c(t)
 
 
 def _f32(t):
@@ -169,9 +220,9 @@ def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_AL
     attrs.setdefault("component_border_bound", 0.0)  # the only default that differs (dau_conv_grad_op.cpp:37)
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
-    plan = _get_plan(input, weights, st)
+    plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
     _check_before(plan, st["check_offsets"])
-    out = plan.backward(_c(input), _c(grad), _c(weights), _c(mu1), _c(mu2), _c(sigma), need_mask)
+    out = plan.backward(_act(input, plan), _act(grad, plan), _c(weights), _c(mu1), _c(mu2), _c(sigma), need_mask)
     _check_after(plan, st["check_offsets"])
     return out
 
@@ -179,8 +230,10 @@ def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_AL
 class _DAUConvFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, weights, mu1, mu2, sigma, st):
-        input, weights, mu1, mu2, sigma = _c(input), _c(weights), _c(mu1), _c(mu2), _c(sigma)
-        plan = _get_plan(input, weights, st)
+        weights, mu1, mu2, sigma = _c(weights), _c(mu1), _c(mu2), _c(sigma)
+        # a channels_last input runs the NHWC plan where there is one: no copy of x (it is saved as it is), y channels_last
+        plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
+        input = _act(input, plan)
         _check_before(plan, st["check_offsets"])
         y = plan.forward(input, weights, mu1, mu2, sigma)
         _check_after(plan, st["check_offsets"])
@@ -201,10 +254,10 @@ class _DAUConvFunction(torch.autograd.Function):
         group = ctx.st["process_group"]
         param_need = need & ~_capi.NEED_DX
         if group is not None and param_need and _group_size(group) > 1:
-            out = _data_parallel_backward(ctx.plan, input, _c(grad), weights, mu1, mu2, sigma, need, group,
+            out = _data_parallel_backward(ctx.plan, input, _act(grad, ctx.plan), weights, mu1, mu2, sigma, need, group,
                                           ctx.st["grad_reduce"])
         else:
-            out = ctx.plan.backward(input, _c(grad), weights, mu1, mu2, sigma, need)
+            out = ctx.plan.backward(input, _act(grad, ctx.plan), weights, mu1, mu2, sigma, need)
         _check_after(ctx.plan, ctx.st["check_offsets"])
         return out + (None,)
 
@@ -347,7 +400,8 @@ class _DAUConvolution2d(object):
                  num_dau_units_ignore=0, mu_learning_rate_factor=500, dau_unit_border_bound=0.01,
                  dau_unit_sigma_bound=0.01, dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, check_offsets="async", algo=_capi.ALGO_AUTO,
-                 dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None, dense_outliers=False):
+                 dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None, dense_outliers=False,
+                 channels_last=None):
         if len(input_shape) != 4:
             raise ValueError("Only two dimensional DAUConv supported (rank-4 NCHW input).")
         if data_format is None or data_format == "NHWC":
@@ -376,6 +430,7 @@ class _DAUConvolution2d(object):
         self.dense_bf16 = dense_bf16
         self.dense_split = dense_split
         self.dense_outliers = dense_outliers
+        self.channels_last = channels_last
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
@@ -395,7 +450,8 @@ class _DAUConvolution2d(object):
                         use_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing,
                         sigma_hint=sigma_hint, check_offsets=self.check_offsets, algo=self.algo,
                         dense_bf16=self.dense_bf16, dense_split=self.dense_split, dense_outliers=self.dense_outliers,
-                        process_group=self.process_group, grad_reduce=self.grad_reduce, name=self.name)
+                        process_group=self.process_group, grad_reduce=self.grad_reduce, name=self.name,
+                        channels_last=self.channels_last)
 
 
 class DAUConv2d(nn.Module):
@@ -422,6 +478,13 @@ class DAUConv2d(nn.Module):
     (DAU_FLAG_IO_F16); the layer casts nothing under autocast.  Parameters of any floating dtype are used as float32 and get
     their gradients in their own dtype.  The bias is added after the op with ordinary type promotion: a float16 (or bfloat16)
     output plus a float32 bias gives a float32 result; after `.half()` the bias is float16 and so is the result.
+    `channels_last` (None, True, False): what a channels_last input (`x.to(memory_format=torch.channels_last)`; a tensor whose
+    strides also fit NCHW -- one channel, or H = W = 1 -- counts as contiguous) runs on.  True: the NHWC plan (DAU_FLAG_IO_NHWC) --
+    the same kernels reading and writing [N][H][W][C], no copy of x, which is saved as it is, a channels_last output, and in backward
+    a channels_last input gradient from a gradient that is converted only if it is not channels_last already; bit for bit the results
+    of the contiguous call.  False: today's path: the input is made contiguous, the output is contiguous.  None (default): the
+    NHWC plan for the dtypes where it measured faster than converting (`dau_conv._NHWC_BY_DEFAULT`).  Layers with
+    `dense_bf16=True` and shapes that run on the direct kernels have no NHWC plan and convert, whatever the argument.
     `process_group` (a torch.distributed group, or True for the default one): batch-sharded data parallelism INSIDE the
     layer's backward -- the raw parameter-gradient sums of the local shard are all-reduced (one flat [4,S,G,F] buffer, RCCL
     over xGMI with backend "nccl") while the input gradient is computed, and the elementwise tail runs on the reduced sums;
@@ -442,7 +505,7 @@ class DAUConv2d(nn.Module):
                  dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False, dau_sigma_trainable=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, in_channels=None, check_offsets="async",
                  algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None,
-                 dense_outliers=False, **kwargs):
+                 dense_outliers=False, channels_last=None, **kwargs):
         super(DAUConv2d, self).__init__()
         self.rank = 2
         self.filters = int(filters)
@@ -494,6 +557,7 @@ class DAUConv2d(nn.Module):
         self.dense_bf16 = dense_bf16
         self.dense_split = dense_split
         self.dense_outliers = dense_outliers
+        self.channels_last = channels_last
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         # odd number of units: add one dummy (zero weight, ignored) unit (dau_conv.py:317-329)
@@ -582,7 +646,7 @@ class DAUConv2d(nn.Module):
             dau_mu_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing, data_format="NCHW",
             name=self.name, check_offsets=self.check_offsets, algo=self.algo, dense_bf16=self.dense_bf16,
             process_group=self.process_group, grad_reduce=self.grad_reduce, dense_split=self.dense_split,
-            dense_outliers=self.dense_outliers)
+            dense_outliers=self.dense_outliers, channels_last=self.channels_last)
         self.built = True
 
     def _var(self, key):

@@ -36,7 +36,8 @@
  *   dau_conv_last_error               DAUException::what (include/dau_conv/util/common.hpp:40-66)
  *
  * Tensor layouts (identical to the reference): activations NCHW contiguous float32 (or,
- * with DAU_FLAG_IO_BF16 / DAU_FLAG_IO_F16, bfloat16 / binary16 storage of x, y, dy, dx -- arithmetic stays fp32);
+ * with DAU_FLAG_IO_BF16 / DAU_FLAG_IO_F16, bfloat16 / binary16 storage of x, y, dy, dx -- arithmetic stays fp32;
+ * with DAU_FLAG_IO_NHWC the same activations as [N][H][W][C] arrays);
  * parameters and their gradients [1,S,G,F] contiguous float32 (f fastest); sigma is a
  * full [1,S,G,F] tensor whose element 0 is used (base_dau_conv_layer.hpp:266-275).
  * Alignment: every pointer need only be aligned to its element type (4 bytes for float32, 2 bytes for the 16-bit activation
@@ -175,6 +176,18 @@ enum {
                                                the flag.  Holds where the plan holds the radius-3 member (DAU_FLAG_DENSE_SPLIT_F16
                                                forces that); inert elsewhere; excludes DAU_FLAG_NO_DENSE_SPLIT and DAU_FLAG_DENSE_BF16.
                                                The parameter gradients are not affected.                                     */
+    DAU_FLAG_IO_NHWC = 1 << 13,             /* x, y, dy, dx of dau_conv_forward, dau_conv_backward and dau_conv_backward_param_sums are
+                                               [N][H][W][C] arrays (C = S for x / dx, F for y / dy: torch.channels_last) instead of
+                                               [N][C][H][W].  Parameters, their gradients, the raw sums, the unit table and the filters
+                                               do not change, nor does anything inside the workspace: the plan is the NCHW plan of the
+                                               same desc (members, buckets, windows, tilings, batch slabs, dau_conv_plan_info,
+                                               dau_conv_workspace_bytes) in everything but the addresses of the activations, and a call
+                                               returns, bit for bit, what the NCHW call returns on the permuted arrays.  Combines with
+                                               DAU_FLAG_IO_BF16 / DAU_FLAG_IO_F16 and every other flag except DAU_FLAG_DENSE_BF16 and
+                                               its qualifiers; needs the tiled kernels (not DAU_ALGO_DIRECT, nor a shape that falls
+                                               back to the direct kernels).  Alignment: none beyond that of an element -- the 16-byte
+                                               load and store paths check the base address and the channel count at run time and
+                                               fall back to element-wise access.                                              */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
