@@ -45,6 +45,10 @@
 //   147 (one chunk): 5.1e-7 (4.9e-7), 294: 8.3e-7 (6.4e-7)                        -- profiles/r4_ab_split_chain_length.txt
 // at the same speed.  Two accumulators of 16 registers per tile is why a wave owns at most four tiles (a 56-pixel row is a block of
 // four and a block of three).
+//
+// Radius 3 runs the same GEMM on v_mfma_f32_16x16x32_f16, one instruction per tap of a PAIR of chunks (kK32 below; the fragment
+// mapping stands at the loop in split_gather_kernel): the staged layouts, the bytes, the LDS reads and the matrix-pipe cycles are
+// those of the 32x32x16 loop, a chain of kFlushRows rows of taps holds the products of two chunks.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -64,6 +68,7 @@ namespace DAU_SPLIT_NS {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(1))) const void* glb_ptr_t;
@@ -85,6 +90,18 @@ constexpr int kFlushTaps = DAU_SPLIT_FLUSH_TAPS > 0 ? DAU_SPLIT_FLUSH_TAPS : kDK
 #define DAU_SPLIT_FLUSH_ROWS 4          // rows of taps per chain (> 1: the chain runs across rows and chunks, `part` is zeroed by moves)
 #endif
 constexpr int kFlushRows = DAU_SPLIT_FLUSH_ROWS;
+// The MFMA shape of the gather-sum, chosen per radius at compile time (every form of a radius shares one tap loop):
+// v_mfma_f32_16x16x32_f16 over a PAIR of 16-channel chunks per tap ("K32", see split_gather_kernel) where it was measured to win,
+// v_mfma_f32_32x32x16_f16 over one chunk elsewhere.  -DDAU_SPLIT_MFMA32 keeps the 32x32x16 loop at every radius: the A/B partner
+// (libdau_conv_hip_mfma32.so).
+#if !defined(DAU_SPLIT_K32)
+#if !defined(DAU_SPLIT_MFMA32) && DAU_SPLIT_R == 3
+#define DAU_SPLIT_K32 1
+#else
+#define DAU_SPLIT_K32 0
+#endif
+#endif
+constexpr bool kK32 = DAU_SPLIT_K32 != 0;
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -612,10 +629,13 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     constexpr int NT0 = (RG == 2 && !TT) ? NSUB : (NSUB + 1) / 2;      // tiles per wave
     constexpr int NT1 = TT ? NSUB / 2 : NT0;                 // ... of the second column half (tall tiles)
     constexpr int WR = kRowsWG + kDSpan;                     // window rows
-    constexpr int HALF = WR * P * 16;                        // bytes of one (limb, half) plane window
-    constexpr int BUFU = 4 * WR * P;                         // 16-byte units of a window: [limb][half][row][P]
+    // K32: K groups 0 and 1 of a ds_read_b128 lane group read planes one `HALF` apart: a whole number of bank rows (16 positions)
+    constexpr int PLANE = kK32 ? (WR * P + 15) / 16 * 16 : WR * P;   // 16-byte units of one (limb, half) plane window
+    constexpr int HALF = PLANE * 16;                         // ... in bytes
+    constexpr int BUFU = 4 * PLANE;                          // 16-byte units of a chunk's window: [limb][half][row][P]
     constexpr int NPIECE = (BUFU + 63) / 64;                 // 1 KiB pieces (one global_load_lds wave instruction each)
-    constexpr int BUF = NPIECE * 1024;
+    constexpr int BUF1 = NPIECE * 1024;                      // one chunk's window
+    constexpr int BUF = kK32 ? 2 * BUF1 : BUF1;              // K32: the windows of a chunk pair, one after the other
     constexpr int PPW = (NPIECE + 7) / 8;                    // pieces per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (!guard_pass(a.guard)) return;
@@ -655,7 +675,10 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
         piece = piece < NPIECE ? piece : NPIECE - 1;         // surplus pieces repeat the last one
         int L = piece * 64 + lane;
         L = L < BUFU ? L : BUFU - 1;
-        const int ph = L / (WR * P), rem = L - ph * (WR * P), r = rem / P, c = rem - r * P;
+        const int ph = L / PLANE;
+        int rem = L - ph * PLANE;
+        rem = rem < WR * P ? rem : WR * P - 1;               // (K32: the units that pad a plane repeat its last one)
+        const int r = rem / P, c = rem - r * P;
         goff[i] = (int)(ph * xs_plane + (long)r * a.Ws + c);
     }
     auto issue = [&](int chunk, int buf) {
@@ -666,6 +689,16 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
             piece = piece < NPIECE ? piece : NPIECE - 1;
             __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + goff[i]), (lds_ptr_t)(smem + buf * BUF + piece * 1024), 16, 0, 0);
         }
+        if constexpr (kK32) {                                // `chunk` is the first of a pair; a last chunk without a partner is copied alone
+            if (chunk + 1 < a.nchunk) {
+#pragma unroll
+                for (int i = 0; i < PPW; ++i) {
+                    int piece = wave + 8 * i;
+                    piece = piece < NPIECE ? piece : NPIECE - 1;
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(src + 4 * xs_plane + goff[i]), (lds_ptr_t)(smem + buf * BUF + BUF1 + piece * 1024), 16, 0, 0);
+                }
+            }
+        }
     };
 
     const int prr = TT ? nn >> 2 : nn >> 3, pcc = TT ? nn & 3 : nn & 7;   // this lane's position inside a tile
@@ -675,6 +708,69 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     const bool out_bf16 = NHWC ? (a.out_act & 0xff) != 0 : a.out_act != 0;   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
     const bool vec_out = NHWC && (a.out_act & kNhwcVecOut) != 0;
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
+    // ADD: the GEMM's sum joins the ring pass's in fp32, and the store rounds THAT fp32 value once more.  Left to itself hipcc folds
+    // the multiply-add into the binary16 store's conversion (v_fma_mixlo_f16), which rounds the exact sum to binary16 at once: not
+    // always the binary16 rounding of what the fp32 plan stores.  The empty asm keeps the fp32 value a value.
+    auto joined = [&](float s, float inv_w, float inv_x, float part) __attribute__((always_inline)) {
+        float v = s * inv_w * inv_x + part;
+        if constexpr (H16) asm("" : "+v"(v));
+        return v;
+    };
+    // epilogue of four CONSECUTIVE output channels f0 .. f0 + 3 of pixel (y, x): the sums `s` as a lane holds them after either MFMA shape
+    auto store4 = [&](int y, int x, bool tile, int f0, const float (&s)[4], float inv_w, float inv_x) __attribute__((always_inline)) {
+        const long plane = (long)out_h * out_w;
+        if (!(y < out_h && x < out_w && tile)) return;       // (RG = 1, odd NSUB: the second column half's last tile does not exist)
+        if constexpr (NHWC) {
+            const long pix = ((long)n * out_h + y) * out_w + x;
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if constexpr (ADD) {
+                    const int fc = f0 + k < out_c ? f0 + k : out_c - 1;      // (clamped address; the value is not stored)
+                    v[k] = joined(s[k], inv_w, inv_x, part_ptr[((long)n * out_c + fc) * plane + (long)y * out_w + x]);
+                } else {
+                    v[k] = s[k] * inv_w * inv_x;
+                }
+            }
+            const long o = pix * out_c + f0;
+            if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
+                if (f0 < out_c) {
+                    if constexpr (H16) {
+                        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                        *reinterpret_cast<f16x4*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
+                            f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+                    } else if (out_bf16) {
+                        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
+                            make_uint2(bf16_bits(v[0]) | (bf16_bits(v[1]) << 16), bf16_bits(v[2]) | (bf16_bits(v[3]) << 16));
+                    } else {
+                        *reinterpret_cast<float4*>(out_ptr + o) = make_float4(v[0], v[1], v[2], v[3]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (f0 + k < out_c) {
+                        if constexpr (H16) store_act_t<kActF16>(out_ptr, o + k, v[k], false);
+                        else store_act(out_ptr, o + k, v[k], out_bf16, false);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int f = f0 + k;
+                if (f < out_c) {
+                    const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
+                    if constexpr (ADD) {
+                        const float v = joined(s[k], inv_w, inv_x, part_ptr[o]);
+                        if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
+                        else store_act(out_ptr, o, v, out_bf16, false);
+                    } else if constexpr (H16) store_act_t<kActF16>(out_ptr, o, s[k] * inv_w * inv_x, false);
+                    else store_act(out_ptr, o, s[k] * inv_w * inv_x, out_bf16, false);
+                }
+            }
+        }
+    };
     auto body = [&](auto ntc) __attribute__((always_inline)) {
     constexpr int NT = decltype(ntc)::value;                 // tiles of this wave
     f32x16 sum[NT], acc[NT];                                 // running sums; the rows of taps being chained
@@ -778,75 +874,175 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     // the fp32 range where the result does not
     const float inv_w = a.sc->inv_sw, inv_x = scales_inv_sx(a.sc, a.N)[n];
     const int y = rowb + prow + prr;
-    const long plane = (long)out_h * out_w;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int x = colb + TW * (ptile + j) + pcc;
-        if constexpr (NHWC) {
-            if (y < out_h && x < out_w && ptile + j < NSUB) {
-                const long pix = ((long)n * out_h + y) * out_w + x;
 #pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    const int f0 = fb * kDFB + fw * 32 + 8 * g4 + 4 * h;
-                    float v[4];
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const float s4[4] = {sum[j][4 * g4], sum[j][4 * g4 + 1], sum[j][4 * g4 + 2], sum[j][4 * g4 + 3]};
+            store4(y, x, ptile + j < NSUB, fb * kDFB + fw * 32 + 8 * g4 + 4 * h, s4, inv_w, inv_x);
+        }
+    }
+    };
+    // K32: one v_mfma_f32_16x16x32_f16 covers one tap of a PAIR of chunks.  Lane l = 16 g + q: K group g is half g & 1 of chunk
+    // 2 c + (g >> 1), row / column q.  The wave's output tile is the same 32 channels x NT tiles of 32 pixels, as 2 channel halves m
+    // (A row q = channel 16 m + q) x 2 NT pixel groups of 16 (B column q = pixel 16 (p & 1) + q of tile p >> 1: two rows of a 4 x 8
+    // tile, four of a tall one), four accumulator registers each (C/D: pixel q, channel 16 m + 4 g + reg).  Both operands are the
+    // planes and the WS rows of the 32x32x16 loop at one more per-lane offset: the second chunk's window lies BUF1 further in LDS, its
+    // dense kernel kDTaps taps further in WS.  Per tap a wave loads 4 A fragments (2 m x hi, lo), reads 4 NT B fragments and issues
+    // 12 NT MFMAs -- the bytes, LDS reads and matrix-pipe cycles of two steps of the other loop.
+    // The A stream runs through buffer loads: a descriptor per row of taps (scalar base = the row's first tap in WS, records = what
+    // is left of the real chunks from there), one 32-bit per-lane offset (channel, half, + one chunk for K groups 2 and 3) and scalar
+    // offsets per tap -- no per-lane address arithmetic, and a load whose per-lane offset lies beyond the records returns zeros.
+    // A last chunk WITHOUT a partner (an odd number of chunks) runs the same row of taps with K groups 2 and 3 idle: their A fragments
+    // are those zeros (the absent chunk's rows lie beyond the records: nothing of them is read) and their B fragments repeat those
+    // of groups 0 and 1 -- finite values add exact zeros, and a non-finite one meets there only the outputs it reaches anyway (every
+    // channel of the pixels whose taps touch it), with nothing read from the absent chunk's window.
+    auto body32 = [&](auto ntc) __attribute__((always_inline)) {
+    constexpr int NT = decltype(ntc)::value;                 // tiles of this wave
+    constexpr int NG = 2 * NT;                               // ... as groups of 16 pixels
+    constexpr int U = kDK * NG;                              // (tap, group) units of a row of taps: 6 MFMAs each
+    constexpr int GR = TT ? 4 : 2;                           // rows of a group
+    f32x4 sum[NG][2], acc[NG][2];                            // running sums; the rows of taps being chained
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        if constexpr (ADD) {
-                            const int fc = f0 + k < out_c ? f0 + k : out_c - 1;      // (clamped address; the value is not stored)
-                            v[k] = sum[j][4 * g4 + k] * inv_w * inv_x + part_ptr[((long)n * out_c + fc) * plane + (long)y * out_w + x];
-                        } else {
-                            v[k] = sum[j][4 * g4 + k] * inv_w * inv_x;
-                        }
+    for (int p = 0; p < NG; ++p) { sum[p][0] = zero; sum[p][1] = zero; acc[p][0] = zero; acc[p][1] = zero; }
+    int rows_chained = 0;
+    const int g = lane >> 4, q = lane & 15;
+    const int qr = TT ? q >> 2 : q >> 3, qc = TT ? q & 3 : q & 7;     // this lane's position inside a group
+    const bool upper = g >= 2;                               // the K groups of a pair's second chunk
+
+    // A fragments: lane (g, q) reads 16 bytes of channel fb*128 + fw*32 + 16 m + q; lo limb CoutP*2 units further
+    const int wlo = a.CoutP * 32, wtap = 2 * wlo;            // bytes
+    const long wchunk = (long)kDTaps * wtap, wend = a.nchunk * wchunk;
+    const unsigned wlane = (unsigned)(((fb * kDFB + fw * 32 + q) * 2 + (g & 1)) * 16) + (upper ? (unsigned)wchunk : 0u);
+    // descriptor of the WS rows from byte `off` on
+    auto rows_from = [&](long off) __attribute__((always_inline)) {
+        const long left = wend - off;
+        const unsigned records = left <= 0 ? 0u : left > 0xffffffffl ? 0xffffffffu : (unsigned)left;
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(a.wsd)) + off, 0, records, 0x00020000);
+    };
+    auto load_a = [&](__amdgpu_buffer_rsrc_t rows, int soff, int m) __attribute__((always_inline)) {
+        return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rows, wlane + 512 * m, soff, 0));
+    };
+    const unsigned lane_base = (unsigned)((g & 1) * HALF + ((prow + qr) * P + ptile * TW + qc) * 16);
+#ifdef DAU_SPLIT_NO_IDLE_WAVES           // (timing experiment: tools/build_variant.sh)
+    const bool live = true;
+#else
+    const bool live = rowb + prow < a.H && ptile < NSUB && colb + ptile * TW < a.W && fb * kDFB + fw * 32 < a.Cout;
+#endif
+    issue(0, 0);
+    f16x8 ah[kDK][2], al[kDK][2], an[2][2], bn[2][2];       // A fragments (hi, lo) x m of a row of taps; the next row's first two
+    static_assert(kAhead == 2 && kDK >= 5 && kDK <= 9, "the A ring below is written for two taps ahead");
+#pragma unroll
+    for (int i = 0; i < kAhead; ++i) {
+#pragma unroll
+        for (int m = 0; m < 2; ++m) { ah[i][m] = load_a(rows_from(0), i * wtap, m); al[i][m] = load_a(rows_from(0), i * wtap + wlo, m); }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const int npair = (a.nchunk + 1) >> 1;
+    for (int pair = 0; pair < npair; ++pair) {
+        const int buf = pair & 1;
+        const bool more = pair + 1 < npair;
+        if (more) issue(2 * pair + 2, buf ^ 1);              // lands under this pair's taps
+        const bool lone = 2 * pair + 1 >= a.nchunk;
+        const unsigned bbase = lane_base + buf * BUF + (lone || !upper ? 0u : (unsigned)BUF1);
+        // One row of taps per iteration, and NOTHING in flight across the back-edge (see the 32x32x16 loop below).  Within a row the
+        // B fragments run through a ring of three (tap, group) units: unit u reads the hi and lo fragments of unit u + 2 in front of
+        // its six MFMAs (hi.hi, lo.hi, hi.lo for both channel halves) and drops its own after them; a tap's first unit requests the
+        // A fragments of tap tx + 2 after its first two MFMAs; the next row's first two are requested at the row's last taps but one and
+        // have landed at its end.
+#pragma unroll 1
+        for (int ty = 0; ty < (live ? kDK : 0); ++ty) {
+            const unsigned brow = bbase + ty * P * 16;
+            const long wrow = 2 * pair * wchunk + (long)ty * kDK * wtap;
+            const __amdgpu_buffer_rsrc_t wcur = rows_from(wrow);
+            // the next row of taps (after a pair's last row: of the next pair)
+            const __amdgpu_buffer_rsrc_t wnxt = rows_from(wrow + kDK * wtap + (ty == kDK - 1 && more ? wchunk : 0));
+            f16x8 xb[3][2];
+            auto read = [&](int u, int limb) __attribute__((always_inline)) {
+                const int tx = u / NG, p = u % NG;
+                return *reinterpret_cast<const f16x8*>(smem + brow + limb * 2 * HALF + ((p & 1) * GR * P + tx + TW * (p >> 1)) * 16);
+            };
+            xb[0][0] = read(0, 0); xb[0][1] = read(0, 1); xb[1][0] = read(1, 0); xb[1][1] = read(1, 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int tx = u / NG, p = u % NG;
+                if (u + 2 < U) { xb[(u + 2) % 3][0] = read(u + 2, 0); xb[(u + 2) % 3][1] = read(u + 2, 1); }
+                const f16x8 xh = xb[u % 3][0], xl = xb[u % 3][1];
+                const f16x8 h0 = ah[tx][0], h1 = ah[tx][1], l0 = al[tx][0], l1 = al[tx][1];
+                const bool fresh = kFlushRows == 1 && tx % kFlushTaps == 0;
+                acc[p][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0, xh, fresh ? zero : acc[p][0], 0, 0, 0);
+                acc[p][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h1, xh, fresh ? zero : acc[p][1], 0, 0, 0);
+                if (p == 0) {
+                    if (tx + kAhead < kDK) {
+#pragma unroll
+                        for (int m = 0; m < 2; ++m) { ah[tx + kAhead][m] = load_a(wcur, (tx + kAhead) * wtap, m); al[tx + kAhead][m] = load_a(wcur, (tx + kAhead) * wtap + wlo, m); }
                     }
-                    const long o = pix * out_c + f0;
-                    if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
-                        if (f0 < out_c) {
-                            if constexpr (H16) {
-                                typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-                                *reinterpret_cast<f16x4*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
-                                    f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-                            } else if (out_bf16) {
-                                *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(out_ptr) + o) =
-                                    make_uint2(bf16_bits(v[0]) | (bf16_bits(v[1]) << 16), bf16_bits(v[2]) | (bf16_bits(v[3]) << 16));
-                            } else {
-                                *reinterpret_cast<float4*>(out_ptr + o) = make_float4(v[0], v[1], v[2], v[3]);
-                            }
-                        }
-                    } else {
+                    if (tx == kDK - 3 || tx == kDK - 2) {         // (where the row's own ring has a slot to spare)
+                        const int i = tx - (kDK - 3);
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if (f0 + k < out_c) {
-                                if constexpr (H16) store_act_t<kActF16>(out_ptr, o + k, v[k], false);
-                                else store_act(out_ptr, o + k, v[k], out_bf16, false);
-                            }
-                        }
+                        for (int m = 0; m < 2; ++m) { an[i][m] = load_a(wnxt, i * wtap, m); bn[i][m] = load_a(wnxt, i * wtap + wlo, m); }
                     }
                 }
+                acc[p][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(l0, xh, acc[p][0], 0, 0, 0);
+                acc[p][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(l1, xh, acc[p][1], 0, 0, 0);
+                acc[p][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h0, xl, acc[p][0], 0, 0, 0);
+                acc[p][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h1, xl, acc[p][1], 0, 0, 0);
+                // the order hipcc must keep (left alone it sinks every LDS read to just before its MFMA and waits for it there)
+                if (u + 2 < U) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+                if (p == 0 && tx + kAhead < kDK && tx == kDK - 3) __builtin_amdgcn_sched_group_barrier(0x020, 8, 0);
+                else if (p == 0 && (tx + kAhead < kDK || tx == kDK - 2)) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                if ((tx + 1) % kFlushTaps == 0 && tx + 1 < kDK) { sum[p][0] += acc[p][0]; sum[p][1] += acc[p][1]; }
             }
-        } else
-        if (y < out_h && x < out_w && ptile + j < NSUB) {      // (RG = 1, odd NSUB: the second column half's last tile does not exist)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int f = fb * kDFB + fw * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (f < out_c) {
-                    const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
-                    if constexpr (ADD) {
-                        const float v = sum[j][i] * inv_w * inv_x + part_ptr[o];
-                        if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
-                        else store_act(out_ptr, o, v, out_bf16, false);
-                    } else if constexpr (H16) store_act_t<kActF16>(out_ptr, o, sum[j][i] * inv_w * inv_x, false);
-                    else store_act(out_ptr, o, sum[j][i] * inv_w * inv_x, out_bf16, false);
+            for (int m = 0; m < 2; ++m) { ah[0][m] = an[0][m]; al[0][m] = bn[0][m]; ah[1][m] = an[1][m]; al[1][m] = bn[1][m]; }
+            if constexpr (kFlushRows == 1) {
+#pragma unroll
+                for (int p = 0; p < NG; ++p) { sum[p][0] += acc[p][0]; sum[p][1] += acc[p][1]; }   // round-to-nearest adds of the row's partial sums
+            } else {
+                if (++rows_chained == kFlushRows) {
+                    rows_chained = 0;
+#pragma unroll
+                    for (int p = 0; p < NG; ++p) { sum[p][0] += acc[p][0]; sum[p][1] += acc[p][1]; acc[p][0] = zero; acc[p][1] = zero; }
                 }
             }
+        }
+        if (more) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next windows have landed (this wave's pieces; the barrier joins the rest)
+            __syncthreads();
+        }
+    }
+    if constexpr (kFlushRows > 1) {
+#pragma unroll
+        for (int p = 0; p < NG; ++p) { sum[p][0] += acc[p][0]; sum[p][1] += acc[p][1]; }   // the chain in progress
+    }
+    // epilogue: C/D layout of a 16x16 tile: column (pixel) = lane & 15, row (channel) = 4 (lane >> 4) + i; the scales as below
+    const float inv_w = a.sc->inv_sw, inv_x = scales_inv_sx(a.sc, a.N)[n];
+#pragma unroll
+    for (int p = 0; p < NG; ++p) {
+        const int y = rowb + prow + (p & 1) * GR + qr, x = colb + TW * (ptile + (p >> 1)) + qc;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const float s4[4] = {sum[p][m][0], sum[p][m][1], sum[p][m][2], sum[p][m][3]};
+            store4(y, x, ptile + (p >> 1) < NSUB, fb * kDFB + fw * 32 + 16 * m + 4 * g, s4, inv_w, inv_x);
         }
     }
     };
     // (both branches meet the same barriers: one per chunk)
+    auto run = [&](auto ntc) __attribute__((always_inline)) {
+        if constexpr (kK32) body32(ntc);
+        else body(ntc);
+    };
     if constexpr (TT) {
-        if (pw == 0) body(std::integral_constant<int, NT0>{});
-        else body(std::integral_constant<int, NT1>{});
+        if (pw == 0) run(std::integral_constant<int, NT0>{});
+        else run(std::integral_constant<int, NT1>{});
     } else {
-        body(std::integral_constant<int, NT0>{});
+        run(std::integral_constant<int, NT0>{});
     }
 }
 
@@ -856,7 +1052,10 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
 namespace {
 
 template <int NSUB, int RG, bool TT>
-constexpr size_t split_lds_bytes() { return 2 * (size_t)((4 * (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB)) + 63) / 64) * 1024; }
+constexpr size_t split_lds_bytes() {
+    constexpr int plane = (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB));
+    return (kK32 ? 4 : 2) * (size_t)((4 * (kK32 ? (plane + 15) / 16 * 16 : plane) + 63) / 64) * 1024;
+}
 
 template <int NSUB, int RG, bool TT = false>
 void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool add, bool nhwc) {
