@@ -70,6 +70,29 @@ constexpr int kNhwcArg = 0x100;
 template <class T> struct NhwcOut : T {};
 template <class T> struct IsNhwcOut : std::false_type {};
 template <class T> struct IsNhwcOut<NhwcOut<T>> : std::true_type {};
+// The fused epilogue of a gather-sum's store (dau_conv_forward_epilogue): y = act(sum + bias[f]), act the identity or ReLU, in fp32
+// before the store's one rounding.  Like the NHWC instantiations these are kernels of their own, marked the same way -- kEpiArg or'ed
+// into the template's first int argument, the gather-sum's traits wrapped in EpiOut<> -- so that a call without an epilogue runs the
+// kernels it ran before.  One instantiation serves bias, ReLU and both: which of them apply is a kernel argument.
+constexpr int kEpiArg = 0x200;
+template <class T> struct EpiOut : T {};
+template <class T> struct IsEpiOut : std::false_type {};
+template <class T> struct IsEpiOut<EpiOut<T>> : std::true_type {};
+template <class T> struct IsNhwcOut<EpiOut<T>> : IsNhwcOut<T> {};
+struct Epilogue {
+    const float* bias = nullptr;     // [Cout] fp32, or none
+    bool relu = false;
+    bool on() const { return bias != nullptr || relu; }
+};
+// act(v + b) of the value v the kernel would have stored.  The add is an fp32 add of THAT value: the empty asm in front keeps a
+// multiply that produced v from being contracted into it, the one behind keeps the add out of a 16-bit store's conversion
+// (v_fma_mixlo_f16 rounds the exact sum once; the unfused form rounds the fp32 sum).  ReLU as torch.relu: a NaN stays a NaN.
+__device__ __forceinline__ float epilogue_value(float v, float b, bool has_bias, bool relu) {
+    asm("" : "+v"(v));
+    if (has_bias) v = v + b;
+    asm("" : "+v"(v));
+    return (relu && v <= 0.0f) ? 0.0f : v;
+}
 // element index of (n, c, y, x) in an [N][H][W][C] array
 __device__ __forceinline__ long nhwc_index(long n, int c, int y, int x, int C, int H, int W) { return ((n * H + y) * W + x) * C + c; }
 // Workgroups b and b + 8 run on the same XCD and share its L2: the logical id under which every XCD takes a contiguous range of

@@ -105,14 +105,17 @@ struct DenseFns {
     size_t (*workspace_bytes)(const DenseConfig&);
     void (*init)(const DenseConfig&);
     void (*prepare)(hipStream_t, const DenseConfig&, const float*, const float*, bool, const UnitRef*, void*, const Guard&);
-    void (*run)(hipStream_t, const DenseConfig&, float*, void*, const Guard&);
+    void (*run)(hipStream_t, const DenseConfig&, float*, void*, const Guard&, const Epilogue&);
 };
+// (the bf16-product forms take no epilogue: dau_conv_epilogue_supported refuses their plans)
+template <void (*Run)(hipStream_t, const DenseConfig&, float*, void*, const Guard&)>
+void run_plain(hipStream_t st, const DenseConfig& c, float* out, void* ws, const Guard& g, const Epilogue&) { Run(st, c, out, ws, g); }
 const DenseFns kDense[] = {
     {s2::split_gather_configure, s2::split_gather_workspace_bytes, s2::split_gather_init, s2::split_gather_prepare, s2::split_gather_run},
     {s3::split_gather_configure, s3::split_gather_workspace_bytes, s3::split_gather_init, s3::split_gather_prepare, s3::split_gather_run},
     {s4::split_gather_configure, s4::split_gather_workspace_bytes, s4::split_gather_init, s4::split_gather_prepare, s4::split_gather_run},
-    {r3::dense_gather_configure, r3::dense_gather_workspace_bytes, r3::dense_gather_init, r3::dense_gather_prepare, r3::dense_gather_run},
-    {r4::dense_gather_configure, r4::dense_gather_workspace_bytes, r4::dense_gather_init, r4::dense_gather_prepare, r4::dense_gather_run},
+    {r3::dense_gather_configure, r3::dense_gather_workspace_bytes, r3::dense_gather_init, r3::dense_gather_prepare, run_plain<r3::dense_gather_run>},
+    {r4::dense_gather_configure, r4::dense_gather_workspace_bytes, r4::dense_gather_init, r4::dense_gather_prepare, run_plain<r4::dense_gather_run>},
 };
 constexpr int kNumDense = kBf16R4 - kSplit2 + 1;
 // the bf16 dense parameter-gradient members kWgradR3, kWgradR4 (index m - kWgradR3)
@@ -210,6 +213,7 @@ struct dau_conv_plan {
     long units() const { return (long)sh.S * sh.G * sh.F; }
     // bytes per activation element: float32, or bfloat16 / binary16 behind the float* of the ABI
     size_t esize() const { return (d.flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_IO_F16)) ? 2 : 4; }
+    int act() const { return (d.flags & DAU_FLAG_IO_F16) ? kActF16 : (d.flags & DAU_FLAG_IO_BF16) ? kActBF16 : kActF32; }
     // optional benchmark timing (dau_conv_profile_begin/_end); mutable because the passes take a const plan
     mutable bool profiling = false;
     mutable std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events[DAU_PROFILE_SLOTS];
@@ -427,8 +431,9 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
 
 // One gather-sum pass: y from x (kFwd: S -> F, unit table [S][G][F]) or dx from the error (kDx: F -> S, mirrored Gaussian, table
 // [F][G][S] with negated offsets).  `ws`: the tiled workspace, or the direct path's blurred copy.
+// epi (tiled plans, kFwd): the fused epilogue of the stores; a pass of several offset windows gives it to the last window's store
 void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float* in, float* out, const float* filters,
-                    const UnitRef* table, Status* status, void* ws) {
+                    const UnitRef* table, Status* status, void* ws, const Epilogue& epi = Epilogue{}) {
     const Shape& s = p->sh;
     const int cin = dir == kFwd ? s.S : s.F, cout = dir == kFwd ? s.F : s.S;
     const bool mirrored = dir == kDx;
@@ -455,10 +460,11 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
             float* outs = slab_ptr(out, (size_t)n0 * cout * s.H * s.W, p->esize());
             if (m == kTiledGather) {
                 const TiledConfig& cfg = bs.tiled[dir];
-                for (int window = 0; window < tiled_gather_windows(cfg); ++window) {   // one pass unless the bucket is 32
+                const int nwin = tiled_gather_windows(cfg);
+                for (int window = 0; window < nwin; ++window) {   // one pass unless the bucket is 32
                     tiled_gather_prepare(st, cfg, ins, filters, mirrored, table, ws, window, g);
                     ProfScope prof(p, dir, st);
-                    tiled_gather_run(st, cfg, outs, ws, window > 0, g);
+                    tiled_gather_run(st, cfg, outs, ws, window > 0, g, window + 1 == nwin ? epi : Epilogue{});
                 }
             } else {                                                       // a dense member: one GEMM per slab
                 const DenseFns& fn = kDense[m - kSplit2];
@@ -467,9 +473,9 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
                 ProfScope prof(p, dir, st);
                 if (ring) {                                                // the ring pass, then the GEMM whose epilogue adds its sums
                     ring_run(st, bs.ringcfg[dir], s3::split_gather_staged(cfg, ws), ring_ws, status, g);
-                    s3::split_gather_run_add(st, cfg, outs, ring_partial(bs.ringcfg[dir], ring_ws), ws, g);
+                    s3::split_gather_run_add(st, cfg, outs, ring_partial(bs.ringcfg[dir], ring_ws), ws, g, epi);
                 } else {
-                    fn.run(st, cfg, outs, ws, g);
+                    fn.run(st, cfg, outs, ws, g, epi);
                 }
             }
         }
@@ -742,12 +748,15 @@ int dau_conv_workspace_bytes(const dau_conv_plan* plan, int pass, size_t* bytes_
     if (!plan || !bytes_out) return fail(DAU_INVALID_ARGUMENT, "null argument");
     if (pass == DAU_PASS_FORWARD) *bytes_out = carve_forward(plan, nullptr).bytes;
     else if (pass == DAU_PASS_BACKWARD) *bytes_out = carve_backward(plan, nullptr).bytes;
-    else return fail(DAU_INVALID_ARGUMENT, "pass must be DAU_PASS_FORWARD or DAU_PASS_BACKWARD");
+    else if (pass == DAU_PASS_EPILOGUE_BACKWARD)
+        *bytes_out = epilogue_grad_workspace_bytes(plan->sh.N, plan->sh.F, plan->sh.H, plan->sh.W, plan->act(), plan->d.flags & DAU_FLAG_IO_NHWC);
+    else return fail(DAU_INVALID_ARGUMENT, "pass must be DAU_PASS_FORWARD, DAU_PASS_BACKWARD or DAU_PASS_EPILOGUE_BACKWARD");
     return DAU_OK;
 }
 
-int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
-                     const float* mu2, const float* sigma, float* y, void* workspace, size_t workspace_bytes) {
+namespace {
+int forward_pass(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
+                 const float* mu2, const float* sigma, float* y, void* workspace, size_t workspace_bytes, const Epilogue& epi) {
     if (!p || !x || !w || !mu1 || !mu2 || !sigma || !y || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
     FwdWs ws = carve_forward(p, workspace);
     if (workspace_bytes < ws.bytes)
@@ -758,7 +767,57 @@ int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const
     launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters);
     launch_prepare_units(st, w, mu1, mu2, p->sh, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table, ws.status,
                          p->host_status);
-    run_gather_sum(p, st, kFwd, x, y, ws.filters, ws.table, ws.status, ws.gather);
+    run_gather_sum(p, st, kFwd, x, y, ws.filters, ws.table, ws.status, ws.gather, epi);
+    DAU_HIP(hipPeekAtLastError());
+    return DAU_OK;
+}
+}  // namespace
+
+int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
+                     const float* mu2, const float* sigma, float* y, void* workspace, size_t workspace_bytes) {
+    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, Epilogue{});
+}
+
+int dau_conv_epilogue_supported(const dau_conv_plan* p, int epilogue) {
+    if (!p) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    if (epilogue & ~(DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU))
+        return fail(DAU_INVALID_ARGUMENT, "unknown epilogue bits 0x%x (DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU)", epilogue);
+    if (p->algo_fwd != DAU_ALGO_TILED)
+        return fail(DAU_INVALID_ARGUMENT, "the direct kernels take no fused epilogue (this plan's forward pass runs on them)");
+    if (p->d.flags & DAU_FLAG_DENSE_BF16)
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 plans take no fused epilogue (the bf16-product forms have none)");
+    return DAU_OK;
+}
+
+int dau_conv_forward_epilogue(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
+                              const float* mu2, const float* sigma, const float* bias, int epilogue, float* y,
+                              void* workspace, size_t workspace_bytes) {
+    if (epilogue == 0) return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, Epilogue{});
+    if (int rc = dau_conv_epilogue_supported(p, epilogue)) return rc;
+    if ((epilogue & DAU_EPILOGUE_BIAS) && !bias) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_BIAS without a bias");
+    Epilogue epi;
+    epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
+    epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
+    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
+}
+
+int dau_conv_epilogue_backward(const dau_conv_plan* p, void* stream, const float* dy, const float* y, int epilogue, float* dz,
+                               float* dbias, void* workspace, size_t workspace_bytes) {
+    if (!p || !dy) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    if (epilogue & ~(DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU))
+        return fail(DAU_INVALID_ARGUMENT, "unknown epilogue bits 0x%x (DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU)", epilogue);
+    const bool relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
+    if (!(epilogue & DAU_EPILOGUE_BIAS)) dbias = nullptr;     // the bits select the work: no bias, no sum
+    if (relu && (!y || !dz)) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_RELU needs y and dz");
+    const bool nhwc = (p->d.flags & DAU_FLAG_IO_NHWC) != 0;
+    const Shape& s = p->sh;
+    if (dbias) {
+        const size_t need = epilogue_grad_workspace_bytes(s.N, s.F, s.H, s.W, p->act(), nhwc);
+        if (!workspace || workspace_bytes < need)
+            return fail(DAU_INVALID_ARGUMENT, "workspace too small: %zu < %zu", workspace ? workspace_bytes : (size_t)0, need);
+    }
+    if (!epilogue_grad_run(static_cast<hipStream_t>(stream), s.N, s.F, s.H, s.W, p->act(), nhwc, dy, y, relu, dz, dbias, workspace))
+        return fail(DAU_INVALID_ARGUMENT, "activation tensor too large for the epilogue's backward pass");
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;
 }

@@ -37,7 +37,9 @@ int tiled_gather_windows(const TiledConfig& cfg);
 // guard: see dau_common.hpp (every kernel of the pass returns at once unless max|mu| lies in the guard's range)
 void tiled_gather_prepare(hipStream_t st, const TiledConfig& cfg, const float* in, const float* filters, bool mirrored,
                           const UnitRef* table, void* workspace, int window, const Guard& guard);
-void tiled_gather_run(hipStream_t st, const TiledConfig& cfg, float* out, void* workspace, bool accumulate, const Guard& guard);
+// epi: the store is act(sum + bias[f]) (a call with an epilogue passes it to its LAST window pass only: act(old + sum + bias))
+void tiled_gather_run(hipStream_t st, const TiledConfig& cfg, float* out, void* workspace, bool accumulate, const Guard& guard,
+                      const Epilogue& epi = Epilogue{});
 // once per plan and device, before the first run: raises the kernels' dynamic-LDS limit
 void tiled_gather_init(const TiledConfig& cfg);
 
@@ -76,7 +78,9 @@ DAU_DECLARE_DENSE_GATHER(r3)
     void split_gather_init(const DenseConfig& cfg);                                                                           \
     void split_gather_prepare(hipStream_t st, const DenseConfig& cfg, const float* in, const float* filters, bool mirrored,   \
                               const UnitRef* table, void* workspace, const Guard& guard);                                     \
-    void split_gather_run(hipStream_t st, const DenseConfig& cfg, float* out, void* workspace, const Guard& guard);           \
+    /* epi: the store is act(sum + bias[f]) (dau_conv_forward_epilogue) */                                                  \
+    void split_gather_run(hipStream_t st, const DenseConfig& cfg, float* out, void* workspace, const Guard& guard,            \
+                          const Epilogue& epi = Epilogue{});                                                                  \
     }
 DAU_DECLARE_SPLIT_GATHER(s2)
 DAU_DECLARE_SPLIT_GATHER(s3)
@@ -92,8 +96,10 @@ struct SplitStaged {          // the radius-3 form's staged input, for the ring 
 };
 namespace s3 {
 SplitStaged split_gather_staged(const DenseConfig& cfg, const void* workspace);
-// split_gather_run with partial[N][Cout][H][W] (fp32) added to the sums before the store's one rounding
-void split_gather_run_add(hipStream_t st, const DenseConfig& cfg, float* out, const float* partial, void* workspace, const Guard& guard);
+// split_gather_run with partial[N][Cout][H][W] (fp32) added to the sums before the store's one rounding (the bias of an epilogue joins
+// after that partial sum)
+void split_gather_run_add(hipStream_t st, const DenseConfig& cfg, float* out, const float* partial, void* workspace, const Guard& guard,
+                          const Epilogue& epi = Epilogue{});
 }
 struct RingConfig {
     int N, Cin, Cout, G, H, W;
@@ -201,5 +207,12 @@ struct WgradConfig {
     }
 DAU_DECLARE_DENSE_WGRAD(r4)
 DAU_DECLARE_DENSE_WGRAD(r3)
+
+// Backward of the fused epilogue (k_epilogue_grad.hip): dz = (y <= 0) ? 0 : dy in the activations' format and layout (relu only;
+// dz may be dy), dbias[f] = sum of dz over n, h, w in fp32 (may be null) through partial sums in `workspace`, reduced in a fixed order.
+// x-like arguments: dy, y, dz are [N][F][H][W] (nhwc: [N][H][W][F]) arrays of format `act`.  false: a grid beyond 2^31 workgroups.
+size_t epilogue_grad_workspace_bytes(long N, int F, int H, int W, int act, bool nhwc);
+bool epilogue_grad_run(hipStream_t st, long N, int F, int H, int W, int act, bool nhwc, const float* dy, const float* y, bool relu,
+                       float* dz, float* dbias, void* workspace);
 
 }  // namespace dau

@@ -604,6 +604,12 @@ struct SplitArgs {
                               // ends with one block of FOUR rows: RG = 1)
     Guard guard;
 };
+// the arguments of the kEpiArg instantiations (kernels of their own: the others keep SplitArgs, and so the offsets of everything that
+// follows it in their argument segment)
+struct SplitArgsEpi : SplitArgs {
+    const float* bias;        // [Cout] fp32 added to the sums before the store's rounding, or null
+    int relu;                 // ... then ReLU
+};
 
 // RG: row groups (of four rows) per workgroup.  2: the eight waves are 4 (32 channels) x 2 (row groups), a wave owns the NSUB tiles of its
 // row group.  1: a block of four rows -- 4 (32 channels) x 2 (column halves), a wave owns (NSUB + 1) / 2 tiles; used for the last
@@ -617,11 +623,14 @@ struct SplitArgs {
 // NSUBN = NSUB | kNhwcArg: out is [N][H][W][Cout].  A lane's sixteen results of a tile are four groups of four CONSECUTIVE channels of
 // its pixel: one 16-byte (fp32) or 8-byte (16-bit) store per group where Cout is a multiple of four and the base is aligned (kNhwcVecOut
 // in out_act), element stores otherwise.  The values and their one rounding are the NCHW epilogue's.
+// NSUBN | kEpiArg: the store is act(v + bias[f]) of the value v the kernel would have stored (with ADD: after the ring's partial sum has
+// joined), in fp32 before the one rounding; the bias is read in the epilogue, after the tap loop, with the channel clamped to Cout - 1.
 constexpr int kNhwcVecOut = 0x100;
 template <int NSUBN, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
-__global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
+__global__ void __launch_bounds__(512) split_gather_kernel(const typename std::conditional<(NSUBN & kEpiArg) != 0, SplitArgsEpi, SplitArgs>::type a) {
     constexpr int NSUB = NSUBN & (kNhwcArg - 1);
     constexpr bool NHWC = (NSUBN & kNhwcArg) != 0;
+    constexpr bool EPI = (NSUBN & kEpiArg) != 0;
     static_assert(!TT || RG == 2, "tall tiles: blocks of eight rows");
     constexpr int TW = TT ? 4 : 8;                           // columns of a tile
     constexpr int P = TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB);   // LDS pitch (positions)
@@ -708,6 +717,14 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
     const bool out_bf16 = NHWC ? (a.out_act & 0xff) != 0 : a.out_act != 0;   // (the fp32 / bf16 instantiations: kActF32 or kActBF16)
     const bool vec_out = NHWC && (a.out_act & kNhwcVecOut) != 0;
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
+    const float* bias_ptr = nullptr;
+    bool relu = false;
+    if constexpr (EPI) { bias_ptr = a.bias; relu = a.relu != 0; }
+    // EPI: act(v + bias[f]) of the value the store would have rounded (the channel clamped: a padded channel's value is not stored)
+    auto finished = [&](float v, int f) __attribute__((always_inline)) {
+        const int fc = f < out_c ? f : out_c - 1;
+        return epilogue_value(v, bias_ptr ? bias_ptr[fc] : 0.0f, bias_ptr != nullptr, relu);
+    };
     // ADD: the GEMM's sum joins the ring pass's in fp32, and the store rounds THAT fp32 value once more.  Left to itself hipcc folds
     // the multiply-add into the binary16 store's conversion (v_fma_mixlo_f16), which rounds the exact sum to binary16 at once: not
     // always the binary16 rounding of what the fp32 plan stores.  The empty asm keeps the fp32 value a value.
@@ -731,6 +748,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
                 } else {
                     v[k] = s[k] * inv_w * inv_x;
                 }
+                if constexpr (EPI) v[k] = finished(v[k], f0 + k);
             }
             const long o = pix * out_c + f0;
             if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
@@ -761,6 +779,14 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const SplitArgs a) {
                 const int f = f0 + k;
                 if (f < out_c) {
                     const long o = ((long)n * out_c + f) * plane + (long)y * out_w + x;
+                    if constexpr (EPI) {
+                        float v;
+                        if constexpr (ADD) v = joined(s[k], inv_w, inv_x, part_ptr[o]);
+                        else v = s[k] * inv_w * inv_x;
+                        v = finished(v, f);
+                        if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
+                        else store_act(out_ptr, o, v, out_bf16, false);
+                    } else
                     if constexpr (ADD) {
                         const float v = joined(s[k], inv_w, inv_x, part_ptr[o]);
                         if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
@@ -1058,8 +1084,21 @@ constexpr size_t split_lds_bytes() {
 }
 
 template <int NSUB, int RG, bool TT = false>
-void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool add, bool nhwc) {
+void launch_split(hipStream_t st, const SplitArgsEpi* a, int grid, bool h16, bool add, bool nhwc, bool epi) {
     constexpr int NH = NSUB | kNhwcArg;                      // the instantiations that store [N][H][W][Cout]
+    constexpr int EP = NSUB | kEpiArg, EH = NH | kEpiArg;    // ... and those whose store is act(v + bias[f])
+    constexpr size_t lds = split_lds_bytes<NSUB, RG, TT>();      // (a comma inside the launch macro's arguments would split them)
+    if (epi) {
+        auto kern = h16 ? split_gather_kernel<EP, RG, TT, true> : split_gather_kernel<EP, RG, TT, false>;
+        if (nhwc) kern = h16 ? split_gather_kernel<EH, RG, TT, true> : split_gather_kernel<EH, RG, TT, false>;
+#if DAU_SPLIT_R == 3
+        if (add) kern = h16 ? split_gather_kernel<EP, RG, TT, true, true> : split_gather_kernel<EP, RG, TT, false, true>;
+        if (add && nhwc) kern = h16 ? split_gather_kernel<EH, RG, TT, true, true> : split_gather_kernel<EH, RG, TT, false, true>;
+#endif
+        if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, *a);
+        return;
+    }
     auto kern = h16 ? split_gather_kernel<NSUB, RG, TT, true> : split_gather_kernel<NSUB, RG, TT, false>;
     if (nhwc) kern = h16 ? split_gather_kernel<NH, RG, TT, true> : split_gather_kernel<NH, RG, TT, false>;
 #if DAU_SPLIT_R == 3
@@ -1067,30 +1106,29 @@ void launch_split(hipStream_t st, const SplitArgs* a, int grid, bool h16, bool a
     if (add && nhwc) kern = h16 ? split_gather_kernel<NH, RG, TT, true, true> : split_gather_kernel<NH, RG, TT, false, true>;
 #endif
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
-    constexpr size_t lds = split_lds_bytes<NSUB, RG, TT>();      // (a comma inside the launch macro's arguments would split them)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, *a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, static_cast<const SplitArgs&>(*a));
 }
 
-void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgs* a, int grid, bool tall, bool add, bool nhwc) {
+void dispatch_split(int nsub, int rg, bool h16, hipStream_t st, const SplitArgsEpi* a, int grid, bool tall, bool add, bool nhwc, bool epi) {
     if (tall) {                                              // nsub = tiles of four columns: 5 or 7 (split_geometry)
-        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16, add, nhwc);
-        else launch_split<7, 2, true>(st, a, grid, h16, add, nhwc);
+        if (nsub == 5) launch_split<5, 2, true>(st, a, grid, h16, add, nhwc, epi);
+        else launch_split<7, 2, true>(st, a, grid, h16, add, nhwc, epi);
         return;
     }
     if (rg == 1) {
         switch (nsub) {
-            case 1: launch_split<1, 1>(st, a, grid, h16, add, nhwc); break;
-            case 2: launch_split<2, 1>(st, a, grid, h16, add, nhwc); break;
-            case 3: launch_split<3, 1>(st, a, grid, h16, add, nhwc); break;
-            default: launch_split<4, 1>(st, a, grid, h16, add, nhwc); break;
+            case 1: launch_split<1, 1>(st, a, grid, h16, add, nhwc, epi); break;
+            case 2: launch_split<2, 1>(st, a, grid, h16, add, nhwc, epi); break;
+            case 3: launch_split<3, 1>(st, a, grid, h16, add, nhwc, epi); break;
+            default: launch_split<4, 1>(st, a, grid, h16, add, nhwc, epi); break;
         }
         return;
     }
     switch (nsub) {
-        case 1: launch_split<1, 2>(st, a, grid, h16, add, nhwc); break;
-        case 2: launch_split<2, 2>(st, a, grid, h16, add, nhwc); break;
-        case 3: launch_split<3, 2>(st, a, grid, h16, add, nhwc); break;
-        default: launch_split<4, 2>(st, a, grid, h16, add, nhwc); break;
+        case 1: launch_split<1, 2>(st, a, grid, h16, add, nhwc, epi); break;
+        case 2: launch_split<2, 2>(st, a, grid, h16, add, nhwc, epi); break;
+        case 3: launch_split<3, 2>(st, a, grid, h16, add, nhwc, epi); break;
+        default: launch_split<4, 2>(st, a, grid, h16, add, nhwc, epi); break;
     }
 }
 
@@ -1148,10 +1186,11 @@ void split_gather_init(const DenseConfig& c) {
     const bool h16 = c.act == kActF16;
     for (int rg = 1; rg <= 2; ++rg) {
         if (!(rg == 2 ? g.nrb8 : g.nrb4)) continue;
-        for (int add = 0; add <= (kDR == 3 ? 1 : 0); ++add) {    // (the radius-3 form also exists with the ring pass's partial sums added)
-            if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true, add != 0, c.nhwc != 0); continue; }
-            dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0, false, add != 0, c.nhwc != 0);
-            if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0, false, add != 0, c.nhwc != 0);
+        for (int v = 0; v < (kDR == 3 ? 4 : 2); ++v) {           // (the radius-3 form also exists with the ring pass's partial sums added; every form with the fused epilogue)
+            const bool add = (v & 2) != 0, epi = (v & 1) != 0;
+            if (rg == 2 && g.tall) { dispatch_split(g.tall, 2, h16, nullptr, nullptr, 0, true, add, c.nhwc != 0, epi); continue; }
+            dispatch_split(g.nsub_a, rg, h16, nullptr, nullptr, 0, false, add, c.nhwc != 0, epi);
+            if (g.nb_b) dispatch_split(g.nsub_b, rg, h16, nullptr, nullptr, 0, false, add, c.nhwc != 0, epi);
         }
     }
     (void)hipFuncSetAttribute(stage_for(c.blur_k, c.act, c.nhwc != 0), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1186,18 +1225,21 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
 
 namespace {
 // partial != nullptr (radius 3): the ADD instantiations
-void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard) {
+void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard,
+               const Epilogue& epilogue) {
     const SplitGeom g = split_geometry(c);
     const bool add = partial != nullptr;
     const bool h16 = c.act == kActF16;
     char* ws = static_cast<char*>(workspace);
-    SplitArgs a{};
+    SplitArgsEpi a{};
     a.sc = reinterpret_cast<const SplitScales*>(ws);
     a.xs = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes);
     a.wsd = reinterpret_cast<const _Float16*>(ws + g.hdr_bytes + g.xs_bytes);
     a.out = out; a.partial = partial;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
     a.out_act = c.act; a.guard = guard;
+    a.bias = epilogue.bias; a.relu = epilogue.relu ? 1 : 0;
+    const bool epi = epilogue.on();
     const bool nhwc = c.nhwc != 0;
     if (nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(out) % (c.act == kActF32 ? 16 : 8) == 0) a.out_act |= kNhwcVecOut;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
@@ -1206,26 +1248,27 @@ void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* pa
         a.row0 = rg == 2 ? 0 : g.nrb8 * kDRows;
         if (rg == 2 && g.tall) {                             // one column block of tall tiles
             a.ncb = 1; a.col0 = 0;
-            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true, add, nhwc);
+            dispatch_split(g.tall, 2, h16, st, &a, c.N * a.nrb * (g.CoutP / kDFB), true, add, nhwc, epi);
             continue;
         }
         a.ncb = g.nb_a; a.col0 = 0;
-        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB), false, add, nhwc);
+        dispatch_split(g.nsub_a, rg, h16, st, &a, c.N * a.nrb * g.nb_a * (g.CoutP / kDFB), false, add, nhwc, epi);
         if (g.nb_b) {
             a.ncb = g.nb_b; a.col0 = g.nb_a * g.nsub_a * 8;
-            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB), false, add, nhwc);
+            dispatch_split(g.nsub_b, rg, h16, st, &a, c.N * a.nrb * g.nb_b * (g.CoutP / kDFB), false, add, nhwc, epi);
         }
     }
 }
 }  // namespace
 
-void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* workspace, const Guard& guard) {
-    run_split(st, c, out, nullptr, workspace, guard);
+void split_gather_run(hipStream_t st, const DenseConfig& c, float* out, void* workspace, const Guard& guard, const Epilogue& epi) {
+    run_split(st, c, out, nullptr, workspace, guard, epi);
 }
 
 #if DAU_SPLIT_R == 3
-void split_gather_run_add(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard) {
-    run_split(st, c, out, partial, workspace, guard);
+void split_gather_run_add(hipStream_t st, const DenseConfig& c, float* out, const float* partial, void* workspace, const Guard& guard,
+                          const Epilogue& epi) {
+    run_split(st, c, out, partial, workspace, guard, epi);
 }
 
 SplitStaged split_gather_staged(const DenseConfig& c, const void* workspace) {

@@ -436,6 +436,12 @@ struct GatherArgs {
     int binned;                // window pass: every channel's slot count comes from its slice's count words
     Guard guard;
 };
+// the arguments of the EpiOut<> instantiations (kernels of their own: the others keep GatherArgs, and so the offsets of everything
+// that follows it in their argument segment)
+struct GatherArgsEpi : GatherArgs {
+    const float* bias;         // [Cout] fp32 added to the sums before the store's rounding, or null
+    int relu;                  // ... then ReLU
+};
 
 // TX, TY : regular 8x8 tiles of one plane;  PITCH: staged pitch (positions);  EDGE: two extra edge tiles per plane
 // SPLIT  : waves sharing one output channel (tiles are dealt out in contiguous ranges)
@@ -592,8 +598,10 @@ __device__ __forceinline__ void unit_group(f4 (&acc)[KP][2], unsigned ut_addr0, 
 // LDS immediates are compile-time constants; every wave runs the same number of barriers).
 // H16: out is binary16 (a compile-time instantiation of its own, so that the fp32 / bf16 kernels keep their epilogue as it was)
 // NHWC: out is [N][H][W][Cout] (gather_mfma_kernel<NhwcOut<T>, H16>)
-template <class T, int PART, bool H16, bool NHWC = false>
-__device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int lane, int wave, int fi) {
+// EPI: the store is act(sum + bias[f]) (gather_mfma_kernel<EpiOut<T>, H16>; the last offset-window pass of a call with an epilogue:
+// after a.accumulate's add, so that fp32 sums keep the unfused order)
+template <class T, int PART, bool H16, bool NHWC = false, bool EPI = false, class Args>
+__device__ __forceinline__ void gather_body(const Args& a, char* smem, int lane, int wave, int fi) {
     // lagged kernels: the waves of the second half (SIMD partners of the first) run one unit behind (GatherTraits::NB)
     const bool lag = T::LAGGED && wave >= T::kWaves / 2;
     constexpr int KP = T::kPerPart;
@@ -723,67 +731,47 @@ __device__ __forceinline__ void gather_body(const GatherArgs& a, char* smem, int
         unit_group<T, PART, KP, 1>(acc, a0, pbuf * buf_bytes, a0, unit_pitch, pbuf * buf_bytes, lane_base, ebase0, ebase1);
     }
 
-    // ---- epilogue: out[p] = Z0[p] + Z1[p+(0,1)] + Z2[p+(1,0)] + Z3[p+(1,1)] through LDS ---------------
-    // per round: one image of the pair, kEpiF output channels, all SK planes
-    const unsigned zpitch = a.zpitch;
-    const unsigned zplane = (unsigned)(H + 1) * zpitch;       // floats per tap plane
-    const unsigned zchan = 4 * zplane;                        // floats per (plane, output channel)
-    float* zs = reinterpret_cast<float*>(smem);
-    const int HW = H * W;
-    const long plane_out = (long)a.H * a.W;
-#pragma unroll
-    for (int img = 0; img < 2; ++img) {   // unrolled: acc[i][img] must be a static register index
-#pragma unroll 1
-        for (int fh = 0; fh < T::FB / T::kEpiF; ++fh) {
-            __syncthreads();
-            if (fi / T::kEpiF == fh) {
-#pragma unroll
-                for (int i = 0; i < KP; ++i) {
-                    constexpr int first = PART * KP;
-                    const int flat = first + i;
-                    const int k = flat / T::kPlaneTiles, tile = flat % T::kPlaneTiles;
-                    int y, x; bool ok;
-                    if (flat >= T::kTiles) { y = 0; x = 0; ok = false; }
-                    else if (tile < T::kRegular) { y = (tile / TX) * T::TH + ly; x = (tile % TX) * T::TW + lx; ok = (y <= H) && (x <= W); }
-                    else if (tile == T::kRegular) { y = ey[0]; x = ex[0]; ok = evalid[0]; }
-                    else { y = ey[1]; x = ex[1]; ok = evalid[1]; }
-                    if (ok) {
-                        const f4 v = acc[i][img];
-                        float* q = zs + (size_t)(k * T::kEpiF + fi % T::kEpiF) * zchan + (unsigned)y * zpitch + x;
-                        q[0] = v[0]; q[zplane] = v[1]; q[2 * zplane] = v[2]; q[3 * zplane] = v[3];
-                    }
-                }
-            }
-            __syncthreads();
-            for (int o = threadIdx.x; o < SK * T::kEpiF * HW; o += T::kThreads) {
-                const int kf = o / HW;                     // (plane, channel of the round)
-                const int k = kf / T::kEpiF, fl = kf % T::kEpiF;
-                const int p = o % HW, y = p / W, x = p % W;
-                const int f = fb * T::FB + fh * T::kEpiF + fl;
-                const int npp = npp0 + k;
-                const int n = 2 * (npp / npatch) + img, patch = npp % npatch;
-                const int gy = (patch / a.npx) * H + y, gx = (patch % a.npx) * W + x;
-                const float* zf = zs + (size_t)kf * zchan + (unsigned)y * zpitch + x;
-                const float v = zf[0] + zf[zplane + 1] + zf[2 * zplane + zpitch] + zf[3 * zplane + zpitch + 1];
-                if (npp < npp_total && n < a.N && f < a.Cout && gy < a.H && gx < a.W)
-                {
-                    const long o = NHWC ? nhwc_index(n, f, gy, gx, a.Cout, a.H, a.W) : ((long)n * a.Cout + f) * plane_out + (long)gy * a.W + gx;
-                    if constexpr (H16) store_act_t<kActF16>(a.out, o, v, a.accumulate != 0);
-                    else store_act(a.out, o, v, a.act != 0, a.accumulate != 0);          // act: kActF32 or kActBF16
-                }
-            }
-        }
+    // EPI: everything only the epilogue needs -- the bias pointer and the ReLU flag, but also out, the sizes, the format -- is read
+    // from the argument segment HERE, after the tap loop (the empty asm ties the address to an accumulator), instead of sitting in
+    // SGPRs across it: the stacked-plane kernels have none to spare, and what does not fit is moved through VGPR lanes between
+    // the MFMAs.  The other instantiations run the same text (k_gather_epilogue_body.hpp) on their arguments as they are.
+    if constexpr (EPI) {
+        // (Args is the kernel's ONE parameter -- gather_mfma_kernel(const Args a) -- so it lies at offset 0 of the argument segment;
+        // a second parameter in front of it would have to move this address along)
+        static_assert(std::is_trivially_copyable<Args>::value, "the argument struct is copied bytewise from the argument segment");
+        unsigned long kargs = (unsigned long)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kargs) : "v"(acc[0][0][0]));
+        Args late;                                            // (copied member-free: the argument segment is another address space)
+        __builtin_memcpy(&late, reinterpret_cast<const __attribute__((address_space(4))) char*>(kargs), sizeof(Args));
+        // (run as a lambda on the copy: hipcc then keeps the copy's SGPRs out of the tap loop's allocation)
+        auto epilogue = [&](const Args& e) __attribute__((always_inline)) {
+#define DAU_E e
+#include "k_gather_epilogue_body.hpp"
+#undef DAU_E
+        };
+        epilogue(late);
+    } else {
+#define DAU_E a
+#include "k_gather_epilogue_body.hpp"
+#undef DAU_E
     }
 }
 
 template <class T, bool H16>
-__global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const GatherArgs a) {
+__global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const typename std::conditional<IsEpiOut<T>::value, GatherArgsEpi, GatherArgs>::type a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (!guard_pass(a.guard)) return;
     constexpr int SPLIT = T::SPLIT;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int part = wave % SPLIT, fi = wave / SPLIT;
+    if constexpr (IsEpiOut<T>::value) {
+        constexpr bool NH = IsNhwcOut<T>::value;
+        if (SPLIT == 1 || part == 0) gather_body<T, 0, H16, NH, true>(a, smem, lane, wave, fi);
+        else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1, H16, NH, true>(a, smem, lane, wave, fi); }
+        else if (SPLIT == 3 || part == 2) { if constexpr (SPLIT > 2) gather_body<T, 2, H16, NH, true>(a, smem, lane, wave, fi); }
+        else { if constexpr (SPLIT > 3) gather_body<T, 3, H16, NH, true>(a, smem, lane, wave, fi); }
+    } else
     if constexpr (IsNhwcOut<T>::value) {
         if (SPLIT == 1 || part == 0) gather_body<T, 0, H16, true>(a, smem, lane, wave, fi);
         else if (SPLIT == 2 || part == 1) { if constexpr (SPLIT > 1) gather_body<T, 1, H16, true>(a, smem, lane, wave, fi); }
@@ -804,51 +792,59 @@ namespace {
 // a == nullptr: raise the kernel's dynamic-LDS limit (once per plan and device, tiled_gather_init); else launch
 // h16: the instantiation with binary16 output (DAU_FLAG_IO_F16)
 // nhwc: the instantiations that store [N][H][W][Cout] (DAU_FLAG_IO_NHWC)
+// epi: the instantiations whose store is act(sum + bias[f]) (dau_conv_forward_epilogue)
 template <class T>
-void launch_variant(hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16, bool nhwc) {
+void launch_variant(hipStream_t st, const GatherArgsEpi* a, int grid, size_t lds, bool h16, bool nhwc, bool epi) {
+    if (epi) {
+        auto kern = nhwc ? (h16 ? gather_mfma_kernel<EpiOut<NhwcOut<T>>, true> : gather_mfma_kernel<EpiOut<NhwcOut<T>>, false>)
+                         : (h16 ? gather_mfma_kernel<EpiOut<T>, true> : gather_mfma_kernel<EpiOut<T>, false>);
+        if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, *a);
+        return;
+    }
     auto kern = nhwc ? (h16 ? gather_mfma_kernel<NhwcOut<T>, true> : gather_mfma_kernel<NhwcOut<T>, false>)
                      : (h16 ? gather_mfma_kernel<T, true> : gather_mfma_kernel<T, false>);
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, *a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, static_cast<const GatherArgs&>(*a));
 }
 
-void dispatch_variant(int variant, hipStream_t st, const GatherArgs* a, int grid, size_t lds, bool h16, bool nhwc) {
+void dispatch_variant(int variant, hipStream_t st, const GatherArgsEpi* a, int grid, size_t lds, bool h16, bool nhwc, bool epi = false) {
     switch (variant) {
-        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16, nhwc); break;
-        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16, nhwc); break;
-        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds, h16, nhwc); break;
-        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
-        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
-        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds, h16, nhwc); break;
-        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds, h16, nhwc); break;
+        case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 2: launch_variant<GatherTraits<4, 4, 72, true, 1>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 3: launch_variant<GatherTraits<2, 2, 40, true, 1>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 4: launch_variant<GatherTraits<3, 3, 40, true, 1>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 5: launch_variant<GatherTraits<1, 1, 40, true, 1>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 6: launch_variant<GatherTraits<4, 4, 40, false, 1>>(st, a, grid, lds, h16, nhwc, epi); break;
 #ifdef DAU_TUNING
-        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds, h16, nhwc); break;
+        case 7: launch_variant<GatherTraits<7, 7, 72, true, 3>>(st, a, grid, lds, h16, nhwc, epi); break;
 #endif
-        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds, h16, nhwc); break;
-        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds, h16, nhwc); break;
-        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds, h16, nhwc); break;
-        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds, h16, nhwc); break;
-        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds, h16, nhwc); break;
-        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds, h16, nhwc); break;
-        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds, h16, nhwc); break;
-        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds, h16, nhwc); break;
-        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds, h16, nhwc); break;
-        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc); break;
-        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc); break;
+        case 8: launch_variant<GatherTraits<4, 4, 72, true, 2, 2, 26624>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 9: launch_variant<GatherTraits<3, 3, 40, true, 2, 4, 13312>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 10: launch_variant<GatherTraits<2, 2, 40, true, 1, 4, 10240, 8>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 11: launch_variant<GatherTraits<1, 1, 40, true, 1, 4, 7168, 16>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 12: launch_variant<GatherTraits<4, 4, 40, false, 2, 3, 13312>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 13: launch_variant<GatherTraits<3, 3, 40, false, 1, 2, 10240, 8>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 14: launch_variant<GatherTraits<2, 2, 40, false, 1, 4, 8192, 8>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 15: launch_variant<GatherTraits<1, 1, 40, false, 1, 8, 5120, 16>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 16: launch_variant<GatherTraits<4, 4, 72, false, 2>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 17: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 18: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 8>>(st, a, grid, lds, h16, nhwc, epi); break;
 #ifdef DAU_TUNING
-        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds, h16, nhwc); break;
+        case 19: launch_variant<GatherTraits<4, 4, 40, false, 2, 2, 13312, 4>>(st, a, grid, lds, h16, nhwc, epi); break;
 #endif
 #ifdef DAU_TUNING
-        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds, h16, nhwc); break;
+        case 20: launch_variant<GatherTraits<7, 7, 72, true, 2, 1, 0, 4, 3>>(st, a, grid, lds, h16, nhwc, epi); break;
 #endif
-        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
-        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
-        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc); break;
+        case 21: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 22: launch_variant<GatherTraits<4, 4, 104, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 23: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12>>(st, a, grid, lds, h16, nhwc, epi); break;
 #ifdef DAU_TUNING                // explicit-request rows (Variant::tuning != 0) exist in the tuning build only
-        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc); break;
-        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc); break;
-        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc); break;
-        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc); break;
+        case 24: launch_variant<GatherTraits<1, 15, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 25: launch_variant<GatherTraits<1, 14, 40, false, 1, 1, 0, 12, 2, 32>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 26: launch_variant<GatherTraits<4, 4, 40, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc, epi); break;
+        case 27: launch_variant<GatherTraits<4, 4, 72, false, 1, 1, 0, 12, 3>>(st, a, grid, lds, h16, nhwc, epi); break;
 #endif
         default: break;
     }
@@ -913,6 +909,7 @@ size_t tiled_gather_workspace_bytes(const TiledConfig& c) {
 
 void tiled_gather_init(const TiledConfig& c) {
     dispatch_variant(c.variant, nullptr, nullptr, 0, 0, c.act == kActF16, c.nhwc != 0);
+    dispatch_variant(c.variant, nullptr, nullptr, 0, 0, c.act == kActF16, c.nhwc != 0, true);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur_pack_for(c.blur_k, c.nhwc != 0)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -969,9 +966,10 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
                        reinterpret_cast<unsigned int*>(packed), guard);
 }
 
-void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* workspace, bool accumulate, const Guard& guard) {
+void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* workspace, bool accumulate, const Guard& guard,
+                      const Epilogue& epi) {
     const Geometry g = make_geometry(c.H, c.W, c.R, c.G, c.N, c.Cout, c.variant);
-    GatherArgs a{};
+    GatherArgsEpi a{};
     a.staged = static_cast<const char*>(workspace);
     a.packed = a.staged + round_up((size_t)c.NP * c.patches * c.Cin * g.plane_bytes, 256);
     a.out = out;
@@ -986,9 +984,10 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.ut_stride = (unsigned)ut_stride_bytes(c.G, g.fb, g.nwin1 > 1);
     a.zpitch = (unsigned)(g.pw + 2);
     a.debug = c.debug;
+    a.bias = epi.bias; a.relu = epi.relu ? 1 : 0;
     const int grid = ((c.NP * c.patches + g.sk - 1) / g.sk) * a.nfb;
     const size_t lds = lds_bytes(c, g);
-    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16, c.nhwc != 0);
+    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16, c.nhwc != 0, epi.on());
 }
 
 }  // namespace dau

@@ -31,7 +31,8 @@ FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernel
 FLAG_IO_NHWC = 1 << 13  # x, y, dy, dx are channels_last: [N][H][W][C] in memory; the NCHW plan of the same desc in everything but addresses
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED = 0, 1, 2
-PASS_FORWARD, PASS_BACKWARD = 1, 2
+PASS_FORWARD, PASS_BACKWARD, PASS_EPILOGUE_BACKWARD = 1, 2, 3
+EPILOGUE_BIAS, EPILOGUE_RELU = 1, 2   # fused into the forward store: y = act(sum + bias[f]) in fp32 before the one rounding
 NEED_DX, NEED_DW, NEED_DMU1, NEED_DMU2, NEED_DSIGMA, NEED_ALL = 1, 2, 4, 8, 16, 31
 
 
@@ -89,6 +90,10 @@ def _load():
     lib.dau_conv_check_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_float)]
     if hasattr(lib, "dau_conv_gather_outlier_status"):   # (an earlier build of the same ABI, loaded through DAU_CONV_LIB for an A/B run, lacks the query)
         lib.dau_conv_gather_outlier_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "dau_conv_forward_epilogue"):        # (likewise: the fused epilogue and its backward pass)
+        lib.dau_conv_epilogue_supported.argtypes = [vp, ctypes.c_int]
+        lib.dau_conv_forward_epilogue.argtypes = [vp, vp, fp, fp, fp, fp, fp, fp, ctypes.c_int, fp, vp, ctypes.c_size_t]
+        lib.dau_conv_epilogue_backward.argtypes = [vp, vp, fp, fp, ctypes.c_int, fp, fp, vp, ctypes.c_size_t]
     lib.dau_conv_last_status.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
     lib.dau_conv_filters.argtypes = [vp, vp, fp, fp]
     lib.dau_conv_unit_table.argtypes = [vp, vp, fp, fp, fp, ctypes.c_int, vp]
@@ -205,20 +210,69 @@ class Plan(object):
             ws = _SHARED_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
         return ws
 
-    def forward(self, x, w, mu1, mu2, sigma):
+    def epilogue_supported(self, epilogue=EPILOGUE_BIAS | EPILOGUE_RELU):
+        """True if forward() takes this epilogue (EPILOGUE_* bits); raises InvalidArgumentError naming the reason otherwise: a plan
+        whose forward pass runs on the direct kernels, a FLAG_DENSE_BF16 plan, unknown bits."""
+        if not hasattr(lib, "dau_conv_epilogue_supported"):
+            raise InvalidArgumentError("this build of the library has no fused epilogue")
+        _check(lib.dau_conv_epilogue_supported(self._h, int(epilogue)))
+        return True
+
+    def forward(self, x, w, mu1, mu2, sigma, bias=None, relu=False):
+        """y, or with bias ([F] float32) / relu the fused epilogue y = act(sum + bias[f]): one fp32 add and a clamp on the value the
+        plain call stores, before the store's one rounding; y keeps the plan's dtype and layout."""
         pshape = (1, self.S, self.G, self.F)
         _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
         for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
             _req(t, n, pshape)
-        dev = _same_device(x, w, mu1, mu2, sigma)
+        if bias is not None:
+            _req(bias, "bias", (self.F,))
+        dev = _same_device(x, w, mu1, mu2, sigma, bias)
+        epilogue = (EPILOGUE_BIAS if bias is not None else 0) | (EPILOGUE_RELU if relu else 0)
+        if epilogue:
+            self.epilogue_supported(epilogue)
         # the library launches on the CURRENT device: make that the tensors' device for the duration of the call
         with torch.cuda.device(dev):
             y = torch.empty((self.N, self.F, self.H, self.W), dtype=self.io_dtype, device=dev, memory_format=self._io_format)
             ws = self._workspace(PASS_FORWARD, dev)
-            _check(lib.dau_conv_forward(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma), _ptr(y),
-                                        _ptr(ws), ws.numel()))
+            if epilogue:
+                _check(lib.dau_conv_forward_epilogue(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma),
+                                                     _ptr(bias), epilogue, _ptr(y), _ptr(ws), ws.numel()))
+            else:
+                _check(lib.dau_conv_forward(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma), _ptr(y),
+                                            _ptr(ws), ws.numel()))
         self._last_ws = ws
         return y
+
+    def epilogue_backward(self, dy, y=None, relu=False, need_dbias=True, dz=None):
+        """Backward of forward()'s epilogue -> (dz, dbias).  relu: dz = (y <= 0) ? 0 : dy from the stored y, in dy's dtype and
+        layout, written into `dz` if given (it may be dy itself); without relu dz is None -- the gradient of the sum IS dy, nothing
+        is copied.  dbias = dz (or dy) summed over n, h, w: [F] float32, fixed summation order, None unless need_dbias.
+        The caller passes dz (or dy) on to backward() / backward_param_sums()."""
+        shape = (self.N, self.F, self.H, self.W)
+        _req(dy, "grad", shape, self.io_dtype, self._io_format)
+        if relu:
+            if y is None:
+                raise InvalidArgumentError("epilogue_backward(relu=True) needs the stored y")
+            _req(y, "output", shape, self.io_dtype, self._io_format)
+            if dz is not None:
+                _req(dz, "dz", shape, self.io_dtype, self._io_format)
+        dev = _same_device(dy, y if relu else None, dz if relu else None)
+        epilogue = (EPILOGUE_BIAS if need_dbias else 0) | (EPILOGUE_RELU if relu else 0)
+        if not epilogue:
+            return None, None
+        with torch.cuda.device(dev):
+            if relu and dz is None:
+                dz = torch.empty(shape, dtype=self.io_dtype, device=dev, memory_format=self._io_format)
+            dbias = torch.empty((self.F,), dtype=torch.float32, device=dev) if need_dbias else None
+            # a small workspace of its own: the shared one still holds the status block of the last forward / backward call
+            need = self._ws.get(PASS_EPILOGUE_BACKWARD)
+            if need is None:
+                need = self._ws[PASS_EPILOGUE_BACKWARD] = self.workspace_bytes(PASS_EPILOGUE_BACKWARD)
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev) if need_dbias else None
+            _check(lib.dau_conv_epilogue_backward(self._h, _stream(dev), _ptr(dy), _ptr(y) if relu else None, epilogue,
+                                                  _ptr(dz) if relu else None, _ptr(dbias), _ptr(ws), need if need_dbias else 0))
+        return (dz if relu else None), dbias
 
     def backward(self, x, dy, w, mu1, mu2, sigma, need_mask=NEED_ALL):
         pshape = (1, self.S, self.G, self.F)

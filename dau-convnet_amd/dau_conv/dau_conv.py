@@ -229,37 +229,51 @@ def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_AL
 
 class _DAUConvFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input, weights, mu1, mu2, sigma, st):
+    def forward(ctx, input, weights, mu1, mu2, sigma, st, bias=None, relu=False):
         weights, mu1, mu2, sigma = _c(weights), _c(mu1), _c(mu2), _c(sigma)
         # a channels_last input runs the NHWC plan where there is one: no copy of x (it is saved as it is), y channels_last
         plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
         input = _act(input, plan)
         _check_before(plan, st["check_offsets"])
-        y = plan.forward(input, weights, mu1, mu2, sigma)
+        # bias / relu: the epilogue fused into the store (dau_conv() asks the plan first); y is then saved for the ReLU mask
+        y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu) \
+            if (bias is not None or relu) else plan.forward(input, weights, mu1, mu2, sigma)
         _check_after(plan, st["check_offsets"])
-        ctx.save_for_backward(input, weights, mu1, mu2, sigma)
-        ctx.plan, ctx.st = plan, st
+        ctx.save_for_backward(*((input, weights, mu1, mu2, sigma) + ((y,) if relu else ())))
+        ctx.plan, ctx.st, ctx.relu = plan, st, bool(relu)
         return y
 
     @staticmethod
     def backward(ctx, grad):
-        input, weights, mu1, mu2, sigma = ctx.saved_tensors
+        input, weights, mu1, mu2, sigma = ctx.saved_tensors[:5]
+        y = ctx.saved_tensors[5] if ctx.relu else None
         need = 0
         for i, bit in enumerate((_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
             if ctx.needs_input_grad[i]:
                 need |= bit
-        if need == 0:
-            return (None,) * 6
+        n_in = len(ctx.needs_input_grad)             # 6, or 8 with (bias, relu)
+        need_dbias = n_in > 6 and ctx.needs_input_grad[6]
+        if need == 0 and not need_dbias:
+            return (None,) * n_in
         _check_before(ctx.plan, ctx.st["check_offsets"])
+        grad = _act(grad, ctx.plan)
+        dbias = None
+        if need_dbias or (ctx.relu and need):
+            # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient (local: it is not exchanged)
+            dz, dbias = ctx.plan.epilogue_backward(grad, y, relu=ctx.relu, need_dbias=need_dbias)
+            if dz is not None:
+                grad = dz
+        if need == 0:
+            return ((None,) * 6 + (dbias, None))[:n_in]
         group = ctx.st["process_group"]
         param_need = need & ~_capi.NEED_DX
         if group is not None and param_need and _group_size(group) > 1:
-            out = _data_parallel_backward(ctx.plan, input, _act(grad, ctx.plan), weights, mu1, mu2, sigma, need, group,
+            out = _data_parallel_backward(ctx.plan, input, grad, weights, mu1, mu2, sigma, need, group,
                                           ctx.st["grad_reduce"])
         else:
-            out = ctx.plan.backward(input, _act(grad, ctx.plan), weights, mu1, mu2, sigma, need)
+            out = ctx.plan.backward(input, grad, weights, mu1, mu2, sigma, need)
         _check_after(ctx.plan, ctx.st["check_offsets"])
-        return out + (None,)
+        return (out + (None, dbias, None))[:n_in]
 
 
 def _group_size(group):
@@ -290,12 +304,39 @@ def _data_parallel_backward(plan, input, grad, weights, mu1, mu2, sigma, need, g
     return (dx,) + tuple(ex.wait())
 
 
-def dau_conv(input, weights, mu1, mu2, sigma, **attrs):
+def _epilogue_ok(plan):
+    """Does the plan take the fused epilogue (asked once per plan)?"""
+    ok = getattr(plan, "_epilogue_ok", None)
+    if ok is None:
+        try:
+            ok = plan.epilogue_supported(_capi.EPILOGUE_BIAS | _capi.EPILOGUE_RELU)
+        except _capi.InvalidArgumentError:
+            ok = False                   # direct kernels, dense_bf16: the unfused form below
+        plan._epilogue_ok = ok
+    return ok
+
+
+def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, **attrs):
     """DAUConv op: output[n,f] = sum_{s,g} w * bilinear(blur_sigma(input[n,s]), . + (mu2, mu1)); differentiable.
-    input (and so output) float32, bfloat16 or float16; the parameters are used as float32 whatever their floating dtype."""
+    input (and so output) float32, bfloat16 or float16; the parameters are used as float32 whatever their floating dtype.
+    bias ([F]) and activation (None or "relu"): output = act(output + bias[f]) fused into the kernels' store -- one fp32 add and a
+    clamp before the one rounding, the output keeps the input's dtype, and backward takes the ReLU mask and the bias gradient (in
+    the bias's dtype) in one pass.  Plans that have no fused epilogue (shapes on the direct kernels, dense_bf16) run the op, then
+    `+ bias` and relu in torch, with torch's type promotion."""
+    if activation not in (None, "relu"):
+        raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
-    return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
+    if bias is None and activation is None:
+        return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
+    if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
+        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), weights.shape[-1]))
+    if _epilogue_ok(_get_plan(input, weights, st, _wants_nhwc(input, st))):
+        return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st, None if bias is None else _f32(bias), activation == "relu")
+    out = _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
+    if bias is not None:
+        out = out + bias.reshape(1, -1, 1, 1)
+    return torch.relu(out) if activation == "relu" else out
 
 
 # ----------------------------------------------------------------------------------------------
@@ -435,12 +476,12 @@ class _DAUConvolution2d(object):
         self.grad_reduce = grad_reduce
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
 
-    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None):
+    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None):
         # clip in the graph, so clipped units receive zero mu-gradient (dau_conv.py:190-191)
         m = self.mean_max_allowed_offset
         mu1 = torch.clamp(mu1, min=-m, max=m)
         mu2 = torch.clamp(mu2, min=-m, max=m)
-        return dau_conv(inp, w, mu1, mu2, sigma,
+        return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation,
                         num_output=self.num_output, number_units_x=self.dau_units[0], number_units_y=self.dau_units[1],
                         number_units_ignore=self.num_dau_units_ignore, kernel_size=self.max_kernel_size,
                         pad=int(self.padding), component_border_bound=self.dau_unit_border_bound,
@@ -478,6 +519,13 @@ class DAUConv2d(nn.Module):
     (DAU_FLAG_IO_F16); the layer casts nothing under autocast.  Parameters of any floating dtype are used as float32 and get
     their gradients in their own dtype.  The bias is added after the op with ordinary type promotion: a float16 (or bfloat16)
     output plus a float32 bias gives a float32 result; after `.half()` the bias is float16 and so is the result.
+    `fused_epilogue=True` (default False: the line above): the bias add (when `use_bias`) and the activation, when it is
+    `torch.relu`, `torch.nn.functional.relu` or an `nn.ReLU`, run inside the kernels' store -- y = act(sum + bias[f]) in fp32
+    before the one rounding -- so the output has the INPUT's dtype (float16 in, float16 out: the next layer keeps its 16-bit loads
+    and stores), two whole-tensor passes of the forward step go away, and backward takes the ReLU mask and the bias gradient in one
+    pass (the bias gradient stays local, as below).  For float32 the output is bit for bit the unfused one.  Any other activation
+    callable is applied after the op; strides > 1 slice the fused result (bias and ReLU commute with the slice); layers whose
+    plan has no fused epilogue (shapes on the direct kernels, `dense_bf16=True`) run unfused.
     `channels_last` (None, True, False): what a channels_last input (`x.to(memory_format=torch.channels_last)`; a tensor whose
     strides also fit NCHW -- one channel, or H = W = 1 -- counts as contiguous) runs on.  True: the NHWC plan (DAU_FLAG_IO_NHWC) --
     the same kernels reading and writing [N][H][W][C], no copy of x, which is saved as it is, a channels_last output, and in backward
@@ -505,7 +553,7 @@ class DAUConv2d(nn.Module):
                  dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False, dau_sigma_trainable=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, in_channels=None, check_offsets="async",
                  algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None,
-                 dense_outliers=False, channels_last=None, **kwargs):
+                 dense_outliers=False, channels_last=None, fused_epilogue=False, **kwargs):
         super(DAUConv2d, self).__init__()
         self.rank = 2
         self.filters = int(filters)
@@ -558,6 +606,7 @@ class DAUConv2d(nn.Module):
         self.dense_split = dense_split
         self.dense_outliers = dense_outliers
         self.channels_last = channels_last
+        self.fused_epilogue = bool(fused_epilogue)
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         # odd number of units: add one dummy (zero weight, ignored) unit (dau_conv.py:317-329)
@@ -682,6 +731,17 @@ class DAUConv2d(nn.Module):
         if inputs.dim() != self.rank + 2:
             raise ValueError('DAU convolution not supported for input with rank %d' % inputs.dim())
         sigma_t, hint = self._sigma_tensor_and_hint()
+        if self.fused_epilogue:
+            # bias and ReLU inside the op's store; both commute with the slicing that emulates strides > 1
+            relu = self.activation in (torch.relu, nn.functional.relu) or isinstance(self.activation, nn.ReLU)
+            outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
+                                               bias=self._parameters["bias"] if self.use_bias else None,
+                                               activation="relu" if relu else None)
+            if self.strides > 1:
+                outputs = outputs[:, :, ::self.strides, ::self.strides]
+            if self.activation is not None and not relu:
+                return self.activation(outputs)
+            return outputs
         outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint)
         # strides > 1 are emulated by sampling the stride-1 output (dau_conv.py:497-498)
         if self.strides > 1:
@@ -765,14 +825,18 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                sigma_initializer=None, sigma_regularizer=None, sigma_constraint=None, biases_initializer=zeros_initializer(),
                biases_regularizer=None, biases_constraint=None, dau_unit_border_bound=0.01, dau_sigma_trainable=False,
                dau_mu_interpolation=True, reuse=None, variables_collections=None, outputs_collections=None,
-               trainable=True, scope=None, dense_outliers=False):
+               trainable=True, scope=None, dense_outliers=False, fused_epilogue=False):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
         raise ValueError('DAU convolution not supported for input with rank', inputs.dim())
     df = 'channels_first' if data_format and data_format.startswith('NC') else 'channels_last'
+    # fused_epilogue: the layer itself adds the bias and applies activation_fn (fused where it is a ReLU) -- unless a normalizer
+    # stands between them
+    fuse_act = bool(fused_epilogue) and normalizer_fn is None and activation_fn is not None
     layer = _scoped_layer(scope, reuse, 'DAUConv', lambda name: DAUConv2d(
-        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=None,
+        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=activation_fn if fuse_act else None,
+        fused_epilogue=fused_epilogue,
         use_bias=bool(not normalizer_fn and biases_initializer), mu_learning_rate_factor=mu_learning_rate_factor,
         weight_initializer=weights_initializer, mu1_initializer=mu1_initializer, mu2_initializer=mu2_initializer,
         sigma_initializer=sigma_initializer, bias_initializer=biases_initializer, weight_regularizer=weights_regularizer,
@@ -785,7 +849,7 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))
-    if activation_fn is not None:
+    if activation_fn is not None and not fuse_act:
         outputs = activation_fn(outputs)
     if outputs_collections is not None:
         outputs_collections.append(outputs)
@@ -799,14 +863,16 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                biases_initializer=zeros_initializer(), biases_regularizer=None, dau_unit_border_bound=0.01,
                dau_sigma_trainable=False, dau_aggregation_forbid_positive_dim1=False, dau_mu_interpolation=True,
                reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
-               dense_outliers=False):
+               dense_outliers=False, fused_epilogue=False):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
         raise ValueError('DAU convolution not supported for input with rank', inputs.dim())
     df = 'channels_first' if data_format and data_format.startswith('NC') else 'channels_last'
+    fuse_act = bool(fused_epilogue) and normalizer_fn is None and activation_fn is not None      # (as dau_conv2d)
     layer = _scoped_layer(scope, reuse, 'DAUConv', lambda name: DAUConv1d(
-        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=None,
+        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=activation_fn if fuse_act else None,
+        fused_epilogue=fused_epilogue,
         use_bias=bool(not normalizer_fn and biases_initializer), mu_learning_rate_factor=mu_learning_rate_factor,
         weight_initializer=weights_initializer, mu1_initializer=mu1_initializer, sigma_initializer=sigma_initializer,
         bias_initializer=biases_initializer, weight_regularizer=weights_regularizer, mu1_regularizer=mu1_regularizer,
@@ -819,7 +885,7 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))
-    if activation_fn is not None:
+    if activation_fn is not None and not fuse_act:
         outputs = activation_fn(outputs)
     if outputs_collections is not None:
         outputs_collections.append(outputs)

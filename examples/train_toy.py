@@ -26,9 +26,9 @@ def run(steps=60, seed=0, verbose=True):
         p.requires_grad_(False)
     student = torch.nn.Sequential(
         dau_conv.DAUConv2d(filters=16, dau_units=(2, 2), max_kernel_size=9, in_channels=8, activation=torch.relu,
-                           mu_learning_rate_factor=10),
+                           mu_learning_rate_factor=10, fused_epilogue=True),      # bias and ReLU inside the kernels' store
         dau_conv.DAUConv2d(filters=16, dau_units=(2, 2), max_kernel_size=9, in_channels=16, use_bias=False,
-                           mu_learning_rate_factor=10),
+                           mu_learning_rate_factor=10, fused_epilogue=True),
     ).to(dev)
     opt = torch.optim.Adam(student.parameters(), lr=3e-3)
     losses = []

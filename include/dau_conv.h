@@ -22,6 +22,8 @@
  *   dau_conv_backward                 DAUConvGradOp::Compute (plugins/tensorflow/src/dau_conv_grad_op.cpp:115-318)
  *                                     -> BaseDAUConvLayer::Backward_gpu (base_dau_conv_layer.cu:130-363)
  *                                     -> DAUConvBackward::backward_pass (dau_conv_backward.cpp:173-232)
+ *   dau_conv_forward_epilogue /       the bias add and activation of the Python layer (plugins/tensorflow/dau_conv/dau_conv.py:500-525)
+ *   dau_conv_epilogue_backward        fused into the forward store, and their gradients in one pass (no reference kernel: TF's own ops)
  *   dau_conv_backward_param_sums /    the two halves of Backward_gpu's parameter-gradient path: the raw sums of K4
  *   dau_conv_finalize_param_grads     (base_dau_conv_layer.cu:232-241) and its elementwise tail (dmu *= w, ignored units,
  *                                     NaN -> 0, :335-355; lr factor, dau_conv_grad_op.cpp:297-303), split so that a
@@ -198,8 +200,15 @@ enum {
     DAU_ALGO_TILED = 2      /* LDS-tiled MFMA gather / wave-reduced gradient kernels             */
 };
 
-/* which pass a workspace is sized for */
-enum { DAU_PASS_FORWARD = 1, DAU_PASS_BACKWARD = 2 };
+/* which pass a workspace is sized for (DAU_PASS_EPILOGUE_BACKWARD: the partial sums of dau_conv_epilogue_backward's dbias -- small:
+ * one float per output channel and 16384 elements or so of the activations) */
+enum { DAU_PASS_FORWARD = 1, DAU_PASS_BACKWARD = 2, DAU_PASS_EPILOGUE_BACKWARD = 3 };
+
+/* the epilogue fused into the forward pass's store (dau_conv_forward_epilogue): y = act(sum + bias[f]) */
+enum {
+    DAU_EPILOGUE_BIAS = 1,   /* add bias[f] (F floats, always float32) to output channel f                       */
+    DAU_EPILOGUE_RELU = 2    /* then v <= 0 ? 0 : v (a NaN stays a NaN)                                          */
+};
 
 /* dau_conv_backward need-mask (params_propagate_down of Backward_gpu) */
 enum {
@@ -279,6 +288,37 @@ DAU_API int dau_conv_workspace_bytes(const dau_conv_plan *plan, int pass, size_t
 DAU_API int dau_conv_forward(const dau_conv_plan *plan, void *stream, const float *x, const float *w,
                      const float *mu1, const float *mu2, const float *sigma, float *y,
                      void *workspace, size_t workspace_bytes);
+
+/* The bias add and the activation of the reference's layer (plugins/tensorflow/dau_conv/dau_conv.py:500-525: tf.nn.bias_add, then
+ * self.activation), fused into the store of dau_conv_forward: y = act(sum + bias[f]) with act the identity or ReLU, computed in fp32
+ * from the very value dau_conv_forward would have stored, BEFORE the store's one rounding -- for float32 activations the bits of
+ * relu(dau_conv_forward(...) + bias), for 16-bit activations one rounding where the unfused form rounds twice, and y keeps the
+ * activations' format.  bias: F floats, always float32; may be NULL without DAU_EPILOGUE_BIAS.  With several offset windows
+ * (dau_conv_plan_info.gather_windows > 1) the epilogue belongs to the last window's store: act(old + v + bias).  epilogue == 0 is
+ * dau_conv_forward exactly.  The workspace is the DAU_PASS_FORWARD one.  y of a DAU_FLAG_IO_NHWC plan is, bit for bit, y of the NCHW
+ * plan on the permuted arrays.  _supported: DAU_OK, or DAU_INVALID_ARGUMENT (and dau_conv_last_error names the reason) for a plan
+ * whose forward pass runs on the direct kernels, for a DAU_FLAG_DENSE_BF16 plan and for unknown epilogue bits; _forward_epilogue
+ * refuses the same.  The input-gradient pass takes no epilogue. */
+DAU_API int dau_conv_epilogue_supported(const dau_conv_plan *plan, int epilogue);
+DAU_API int dau_conv_forward_epilogue(const dau_conv_plan *plan, void *stream, const float *x, const float *w,
+                     const float *mu1, const float *mu2, const float *sigma, const float *bias, int epilogue,
+                     float *y, void *workspace, size_t workspace_bytes);
+
+/* Backward of that epilogue -- what autodiff derives from the reference layer's bias_add and activation (same lines) -- in one pass
+ * over dy (and, with DAU_EPILOGUE_RELU, the stored y):
+ *   dz = (y <= 0) ? 0 : dy     in the activations' format and layout; the rule of a threshold at zero: a NaN y passes dy through.
+ *                              Written only with DAU_EPILOGUE_RELU; without it dz IS dy, nothing is copied, y and dz may be NULL.
+ *                              dz may alias dy.
+ *   dbias[f] = sum of dz over n, h, w, in float32 (F floats), with DAU_EPILOGUE_BIAS only (without the bit the pointer is ignored);
+ *                              may be NULL, then only dz is written.  epilogue == 0 does nothing.
+ * The caller passes dz (or dy) on to dau_conv_backward / dau_conv_backward_param_sums as their dy.  No atomics: partial sums in the
+ * workspace (DAU_PASS_EPILOGUE_BACKWARD; not needed without dbias), reduced in a fixed order -- two calls give the same bits -- and
+ * hierarchically: no value passes through more than 256 float32 additions (148 at most, for tensors up to 2^31 elements), so
+ * |dbias[f] - exact| <= 2^-16 * sum |dz[:, f]|.  dz of a DAU_FLAG_IO_NHWC plan is the bits of the NCHW plan's on the permuted arrays;
+ * dbias is the ONE exception to that contract: the order of a sum over positions follows memory, so the two layouts agree within
+ * that bound, not bit for bit. */
+DAU_API int dau_conv_epilogue_backward(const dau_conv_plan *plan, void *stream, const float *dy, const float *y, int epilogue,
+                     float *dz, float *dbias, void *workspace, size_t workspace_bytes);
 
 DAU_API int dau_conv_backward(const dau_conv_plan *plan, void *stream, const float *x, const float *dy,
                       const float *w, const float *mu1, const float *mu2, const float *sigma,
