@@ -13,6 +13,7 @@ something else before the hand-counted s_waitcnt.  Nothing in the sources shows 
   3. the hot kernels touch no scratch between their first and their last MFMA (spills in prologue / flush code are tolerated,
      they are listed), and the kernels that are not instantiated for production are not in the release library at all,
   4. every kernel of the release library is byte-identical in the tuning build (the variant tests run on that build)."""
+import collections
 import os
 import re
 import struct
@@ -20,6 +21,8 @@ import subprocess
 import tempfile
 
 import pytest
+
+import util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "dau-convnet_amd", "dau_conv")
@@ -248,3 +251,25 @@ def test_release_kernels_are_byte_identical_in_the_tuning_build():
     assert not missing, "kernels of the release build that the tuning build lacks: %s" % missing[:5]
     differ = [_kernel_name(k)[:90] for k in r if r[k] != t[k]]
     assert not differ, "%d kernels differ between the release and the tuning build, e.g. %s" % (len(differ), differ[:5])
+
+
+# csrc/Makefile's table of variant libraries, one "name source flags" line each
+VARIANTS = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "dau-convnet_amd", "csrc"), "print-variants"],
+                          capture_output=True, text=True, check=True).stdout.splitlines()
+FORMS = {"k_dense_bf16": 1, "k_dense_wgrad": 1, "k_dense_split": 2}      # compile forms of a source beside the plain one (r3_; s2_, s4_)
+
+
+@pytest.mark.parametrize("line", VARIANTS, ids=[v.split()[0] for v in VARIANTS])
+def test_a_variant_library_is_the_tuning_build_with_one_source_recompiled(line):
+    """One code object per translation unit: those of the variant's source (every compile form of it) differ from the tuning
+    library's, every other one is there byte for byte."""
+    name, source = line.split()[:2]
+    var, tun = util.variant_lib(name), util.variant_lib("tuning")
+    if not (os.path.exists(var) and os.path.exists(tun)):
+        pytest.skip("libraries not built")
+    with tempfile.TemporaryDirectory() as d:
+        v, t = ([open(co, "rb").read() for co in _code_objects(so, d)] for so in (var, tun))
+    v, t = collections.Counter(v), collections.Counter(t)
+    assert sum(v.values()) == sum(t.values()) > 0
+    units = 1 + FORMS.get(source, 0)
+    assert sum((v - t).values()) == units and sum((t - v).values()) == units, (sum((v - t).values()), sum((t - v).values()), units)

@@ -18,38 +18,9 @@ import pytest
 import torch
 
 from oracle import dau_oracle as orc
-from util import assert_parity
+from util import assert_parity, make_inputs, run_plan
 
 pytestmark = pytest.mark.gpu
-
-
-def _inputs(seed, N, S, F, G, H, W, k, m, ignore=0):
-    rs = np.random.RandomState(seed)
-    x = rs.rand(N, S, H, W).astype(np.float32)
-    dy = rs.randn(N, F, H, W).astype(np.float32)
-    w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
-    if ignore:
-        w[:, :, G - ignore:, :] = 0.0
-    lim = k // 2 - 0.01
-    mu1 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    mu2 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    return x, dy, w, mu1, mu2
-
-
-def _run(plan, x, dy, w, mu1, mu2, dtype=torch.float32, calls=1):
-    dev = lambda a: torch.from_numpy(a).cuda()
-    S, G, F = w.shape[1:]
-    sigma = torch.full((1, S, G, F), 0.5, device="cuda")
-    xd, dyd = dev(x).to(dtype), dev(dy).to(dtype)
-    wd, m1, m2 = dev(w), dev(mu1), dev(mu2)
-    for _ in range(calls):
-        y = plan.forward(xd, wd, m1, m2, sigma)
-        plan.check_status()
-        g = plan.backward(xd, dyd, wd, m1, m2, sigma)
-        plan.check_status()
-    torch.cuda.synchronize()
-    return dict(y=y.float().cpu().numpy(), dx=g[0].float().cpu().numpy(), dw=g[1].cpu().numpy(), dmu1=g[2].cpu().numpy(),
-                dmu2=g[3].cpu().numpy(), dsigma=g[4].cpu().numpy())
 
 
 def _check_all(got, x, dy, w, mu1, mu2, name, ignore=0, io_rel=1e-4, io_floor=1e-6, param_floor=1e-6):
@@ -64,22 +35,22 @@ def _check_all(got, x, dy, w, mu1, mu2, name, ignore=0, io_rel=1e-4, io_floor=1e
 def test_c1_alexnet_conv2_full_size():
     from dau_conv import _capi
     N, S, F, G, H, W, k = 64, 96, 256, 4, 27, 27, 9
-    x, dy, w, mu1, mu2 = _inputs(22, N, S, F, G, H, W, k, 3.0)
+    x, dy, w, mu1, mu2 = make_inputs(22, N, S, F, G, H, W, k, 3.0)
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5)
     assert plan.info["algo_forward"] == _capi.ALGO_TILED and plan.info["algo_backward"] == _capi.ALGO_TILED
-    _check_all(_run(plan, x, dy, w, mu1, mu2), x, dy, w, mu1, mu2, "C1")
+    _check_all(run_plan(plan, x, dy, w, mu1, mu2), x, dy, w, mu1, mu2, "C1")
 
 
 def test_c2_six_units_bf16_activations():
     """BASELINE config 2's combination: 56x56, G=6 (two gather-dot passes), bfloat16 x / y / dy / dx, S=F=256."""
     from dau_conv import _capi
     N, S, F, G, H, W, k = 3, 256, 256, 6, 56, 56, 9
-    x, dy, w, mu1, mu2 = _inputs(23, N, S, F, G, H, W, k, 3.0)
+    x, dy, w, mu1, mu2 = make_inputs(23, N, S, F, G, H, W, k, 3.0)
     xb = torch.from_numpy(x).to(torch.bfloat16).float().numpy()      # what the kernels read
     dyb = torch.from_numpy(dy).to(torch.bfloat16).float().numpy()
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5,
                       flags=_capi.FLAG_USE_INTERPOLATION | _capi.FLAG_IO_BF16)
-    got = _run(plan, xb, dyb, w, mu1, mu2, dtype=torch.bfloat16)
+    got = run_plan(plan, xb, dyb, w, mu1, mu2, dtype=torch.bfloat16)
     # bf16 outputs: one rounding to 8 bits (2^-9 relative); the fp32 parameter gradients keep the fp32 bar
     _check_all(got, xb, dyb, w, mu1, mu2, "C2", io_rel=2e-2, io_floor=4e-3)
 
@@ -92,12 +63,12 @@ def test_c4_seg_scale_large_offsets(static_bucket):
     gather-dot windows).  Both must match the oracle."""
     from dau_conv import _capi
     N, S, F, G, H, W, k = 2, 4, 32, 10, 512, 512, 65
-    x, dy, w, mu1, mu2 = _inputs(24, N, S, F, G, H, W, k, 17.0, ignore=1)
+    x, dy, w, mu1, mu2 = make_inputs(24, N, S, F, G, H, W, k, 17.0, ignore=1)
     flags = _capi.FLAG_USE_INTERPOLATION | (_capi.FLAG_STATIC_BUCKET if static_bucket else 0)
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, number_units_ignore=1, sigma_hint=0.5, flags=flags)
     assert plan.info["algo_forward"] == _capi.ALGO_TILED and plan.info["algo_backward"] == _capi.ALGO_TILED
     assert plan.info["offset_bucket"] == 32 and plan.info["bucket_sets"] == (1 if static_bucket else 7)
-    got = _run(plan, x, dy, w, mu1, mu2, calls=2)        # the second call has the first one's max|mu| as its hint
+    got = run_plan(plan, x, dy, w, mu1, mu2, calls=2)        # the second call has the first one's max|mu| as its hint
     _check_all(got, x, dy, w, mu1, mu2, "C4", ignore=1)
     assert float(np.abs(got["dw"][:, :, G - 1]).max()) == 0.0
 
@@ -123,10 +94,10 @@ def test_large_offsets_clustered_units(layout):
     mu1 = (c1.reshape(1, 1, G, 1) + rs.uniform(-j, j, (1, S, G, F))).astype(np.float32)
     mu2 = (c2.reshape(1, 1, G, 1) + rs.uniform(-j, j, (1, S, G, F))).astype(np.float32)
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5)
-    got = _run(plan, x, dy, w, mu1, mu2, calls=2)        # second call: bucket 18 (2 x 2 windows of radius 9)
+    got = run_plan(plan, x, dy, w, mu1, mu2, calls=2)        # second call: bucket 18 (2 x 2 windows of radius 9)
     _check_all(got, x, dy, w, mu1, mu2, "clustered/" + layout)
     static = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5, flags=_capi.FLAG_USE_INTERPOLATION | _capi.FLAG_STATIC_BUCKET)
-    got = _run(static, x, dy, w, mu1, mu2)               # bucket 32: 4 x 4 gather-dot windows, 2 x 2 gather-sum windows
+    got = run_plan(static, x, dy, w, mu1, mu2)               # bucket 32: 4 x 4 gather-dot windows, 2 x 2 gather-sum windows
     _check_all(got, x, dy, w, mu1, mu2, "clustered/" + layout + "/static")
 
 
@@ -151,22 +122,22 @@ def test_big_kernel_small_offsets_dynamic_bucket(shape):
     equals the oracle; the first two are bit-identical whenever the hinted bucket equals the static one."""
     from dau_conv import _capi
     N, S, F, G, H, W, k, m = (shape[q] for q in ("N", "S", "F", "G", "H", "W", "k", "m"))
-    x, dy, w, mu1, mu2 = _inputs(31, N, S, F, G, H, W, k, m)
+    x, dy, w, mu1, mu2 = make_inputs(31, N, S, F, G, H, W, k, m)
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5)
     assert plan.info["bucket_sets"] > 1
-    first = _run(plan, x, dy, w, mu1, mu2)               # no hint yet: static bucket
+    first = run_plan(plan, x, dy, w, mu1, mu2)               # no hint yet: static bucket
     assert plan.last_status() == pytest.approx(float(max(np.abs(mu1).max(), np.abs(mu2).max())))
-    second = _run(plan, x, dy, w, mu1, mu2)              # hinted: smallest bucket that covers max|mu|
+    second = run_plan(plan, x, dy, w, mu1, mu2)              # hinted: smallest bucket that covers max|mu|
     _check_all(first, x, dy, w, mu1, mu2, "static")
     _check_all(second, x, dy, w, mu1, mu2, "hinted")
     # offsets grow past the hinted bucket between two calls: the stale hint must not matter
     lim = k // 2 - 0.01
     mu1b, mu2b = mu1.copy(), mu2.copy()
     mu1b.flat[0] = lim; mu2b.flat[-1] = -lim
-    third = _run(plan, x, dy, w, mu1b, mu2b)
+    third = run_plan(plan, x, dy, w, mu1b, mu2b)
     _check_all(third, x, dy, w, mu1b, mu2b, "grown")
     # and shrink again
-    fourth = _run(plan, x, dy, w, mu1, mu2, calls=2)
+    fourth = run_plan(plan, x, dy, w, mu1, mu2, calls=2)
     for key in second:
         assert np.array_equal(fourth[key], second[key]), key
 
@@ -176,7 +147,7 @@ def test_dynamic_bucket_costs_what_the_offsets_need():
     its kernels from the actual offsets on every call, dau_conv_op.cpp:236-253)."""
     from dau_conv import _capi
     N, S, F, G, H, W = 16, 64, 64, 4, 56, 56
-    x, dy, w, mu1, mu2 = _inputs(32, N, S, F, G, H, W, 9, 3.0)
+    x, dy, w, mu1, mu2 = make_inputs(32, N, S, F, G, H, W, 9, 3.0)
     dev = lambda a: torch.from_numpy(a).cuda()
     xd, dyd, wd, m1, m2 = dev(x), dev(dy), dev(w), dev(mu1), dev(mu2)
     sigma = torch.full((1, S, G, F), 0.5, device="cuda")
@@ -213,7 +184,7 @@ def test_batch_slabs_under_a_workspace_budget(mode, monkeypatch):
     from dau_conv import _capi
     N, S, F, G, H, W, k = 12, 6, 10, 3, 40, 36, 17
     m = 3.5 if mode == "bf16-dense" else 7.5
-    x, dy, w, mu1, mu2 = _inputs(51, N, S, F, G, H, W, k, m)
+    x, dy, w, mu1, mu2 = make_inputs(51, N, S, F, G, H, W, k, m)
     flags = _capi.FLAG_USE_INTERPOLATION
     dtype, io_rel, io_floor = torch.float32, 1e-4, 1e-6
     if mode != "f32":
@@ -228,7 +199,7 @@ def test_batch_slabs_under_a_workspace_budget(mode, monkeypatch):
     assert whole.info["batch_slab_gather"] == N and whole.info["batch_slab_dot"] == N
     assert plan.info["batch_slab_gather"] < N and plan.info["batch_slab_dot"] < N, plan.info
     assert plan.workspace_bytes(_capi.PASS_BACKWARD) < whole.workspace_bytes(_capi.PASS_BACKWARD)
-    got = _run(plan, x, dy, w, mu1, mu2, dtype=dtype, calls=2)       # second call: hinted bucket, also in slabs
+    got = run_plan(plan, x, dy, w, mu1, mu2, dtype=dtype, calls=2)       # second call: hinted bucket, also in slabs
     _check_all(got, x, dy, w, mu1, mu2, "slabs/" + mode, io_rel=io_rel, io_floor=io_floor)
 
 
@@ -238,9 +209,9 @@ def test_more_units_than_the_work_list_places_fall_back_to_the_direct_kernels():
     results."""
     from dau_conv import _capi
     N, S, F, G, H, W, k = 2, 3, 8, 18, 24, 30, 33
-    x, dy, w, mu1, mu2 = _inputs(61, N, S, F, G, H, W, k, 15.0)
+    x, dy, w, mu1, mu2 = make_inputs(61, N, S, F, G, H, W, k, 15.0)
     plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5)
     assert plan.info["algo_forward"] == _capi.ALGO_TILED and plan.info["algo_backward"] == _capi.ALGO_DIRECT, plan.info
-    _check_all(_run(plan, x, dy, w, mu1, mu2, calls=2), x, dy, w, mu1, mu2, "G=18 under kernel 33")
+    _check_all(run_plan(plan, x, dy, w, mu1, mu2, calls=2), x, dy, w, mu1, mu2, "G=18 under kernel 33")
     small = _capi.Plan(N, S, F, G, H, W, max_kernel_size=17, sigma_hint=0.5)       # buckets 4 and 8 have no such limit
     assert small.info["algo_backward"] == _capi.ALGO_TILED

@@ -7,47 +7,22 @@ test_gpu_split_gather_dot_ring.py).  Beside that: the fp32 bar against the oracl
 counts, region widths and offset ranges; dynamic range across and inside channels (the f16 subnormal tail of a channel);
 non-finite values stay in their channel; the hand-over to the exact kernels beyond +-4; the three-product reference build
 (libdau_conv_hip_bf16_e2.so of `make tuning`); the layer under torch.autocast."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import dau_oracle as orc
-from util import assert_parity, make_inputs, record_margins
+from util import assert_parity, make_inputs, record_margins, variant_capi
 
 pytestmark = pytest.mark.gpu
 
 PARAMS = ("dw", "dmu1", "dmu2", "dsigma")
 BAR = "1e-4 rel + 1e-6 max-norm (fp32 bar; bf16 split gather-dot, one-limb error)"
-_E2 = []
 
 
 def _capi():
     from dau_conv import _capi
     return _capi
-
-
-def _e2_capi():
-    """the ctypes binding over the three-product reference build (as test_gpu_split_dot_staging.py loads its variant library)"""
-    if not _E2:
-        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
-        so = os.path.join(pkg, "libdau_conv_hip_bf16_e2.so")
-        assert os.path.exists(so), "%s missing: run `make -C dau-convnet_amd/csrc tuning` (or __graft_entry__.build())" % so
-        spec = importlib.util.spec_from_file_location("dau_conv_capi_bf16_e2", os.path.join(pkg, "_capi.py"))
-        mod = importlib.util.module_from_spec(spec)
-        old = os.environ.get("DAU_CONV_LIB")
-        os.environ["DAU_CONV_LIB"] = so
-        try:
-            spec.loader.exec_module(mod)
-        finally:
-            if old is None:
-                del os.environ["DAU_CONV_LIB"]
-            else:
-                os.environ["DAU_CONV_LIB"] = old
-        _E2.append(mod)
-    return _E2[0]
 
 
 def _bf16(a):
@@ -251,7 +226,7 @@ def test_bf16_split_dot_hands_over_beyond_the_window_and_the_hint_decides_nothin
 # ---- 6. the three-product reference build ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name, shape, m, seed", [RING_CASES[5], RING_CASES[6]], ids=["ragged", "small-ragged"])
 def test_one_limb_error_is_bit_identical_to_the_three_product_build(name, shape, m, seed):
-    capi, e2 = _capi(), _e2_capi()
+    capi, e2 = _capi(), variant_capi("bf16_e2")
     case = _inputs(seed, shape, m)
     one = _grads(capi, _plan(capi, shape, "bf16"), *case)
     three = _grads(e2, _plan(e2, shape, "bf16"), *case)

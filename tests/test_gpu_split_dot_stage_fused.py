@@ -8,46 +8,15 @@ widths 12 and 10), a 27x27 map (several windows per workgroup in blur4_pack), N 
 a map wider than one column tile of the new sd_stage_e_kernel, float16 activation I/O, the unit_testing edge rule, and an Inf in
 one input channel of x and one output channel of dy (the maxima are taken over finite values only: every other channel pair
 keeps its bits)."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
 from oracle import dau_oracle as orc
-from util import assert_parity, make_inputs
+from util import assert_parity, make_inputs, region_width, variant_capi
 
 pytestmark = pytest.mark.gpu
 
 PARAMS = ("dw", "dmu1", "dmu2", "dsigma")
-_REF = []
-
-
-def _stage_ref_capi():
-    """the ctypes binding over the build with the earlier staging (as util.tuning_capi does for the tuning build)"""
-    if not _REF:
-        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
-        so = os.path.join(pkg, "libdau_conv_hip_stage_ref.so")
-        assert os.path.exists(so), "%s missing: run `make -C dau-convnet_amd/csrc tuning` (or __graft_entry__.build())" % so
-        spec = importlib.util.spec_from_file_location("dau_conv_capi_stage_ref", os.path.join(pkg, "_capi.py"))
-        mod = importlib.util.module_from_spec(spec)
-        old = os.environ.get("DAU_CONV_LIB")
-        os.environ["DAU_CONV_LIB"] = so
-        try:
-            spec.loader.exec_module(mod)
-        finally:
-            if old is None:
-                del os.environ["DAU_CONV_LIB"]
-            else:
-                os.environ["DAU_CONV_LIB"] = old
-        _REF.append(mod)
-    return _REF[0]
-
-
-def _region_width(W):
-    """split_dot_configure's choice"""
-    cost = {rw: -(-(W + 1) // rw) * rw * (rw + 2) * (60 // rw) for rw in (12, 10)}
-    return 12 if cost[12] <= cost[10] else 10
 
 
 def _gradients(capi, x, dy, w, mu1, mu2, extra=0, half=False):
@@ -97,11 +66,11 @@ CASES = [
 @pytest.mark.parametrize("name,shape,rw,flag_names,half", CASES, ids=[c[0] for c in CASES])
 def test_fused_staging_is_bit_identical_to_the_earlier_staging(name, shape, rw, flag_names, half):
     from dau_conv import _capi
-    assert _region_width(shape[5]) == rw
+    assert region_width(shape[5]) == rw
     x, dy, w, mu1, mu2 = _inputs(801 + rw, shape)
     if half:                                       # the oracle sees the values the kernels see
         x, dy = x.astype(np.float16).astype(np.float32), dy.astype(np.float16).astype(np.float32)
-    ref_capi = _stage_ref_capi()
+    ref_capi = variant_capi("stage_ref")
     new = _gradients(_capi, x, dy, w, mu1, mu2, sum(getattr(_capi, f) for f in flag_names), half)
     ref = _gradients(ref_capi, x, dy, w, mu1, mu2, sum(getattr(ref_capi, f) for f in flag_names), half)
     want = orc.backward(x, dy, w, mu1, mu2, 0.5, need=PARAMS, unit_testing="FLAG_UNIT_TESTING" in flag_names)
@@ -117,7 +86,7 @@ def test_an_inf_leaves_the_other_channel_pairs_bit_identical():
     x[2, 3, 6, 9] = np.inf
     dy[1, 5, 3, 3] = np.inf
     new = _gradients(_capi, x, dy, w, mu1, mu2)
-    ref = _gradients(_stage_ref_capi(), x, dy, w, mu1, mu2)
+    ref = _gradients(variant_capi("stage_ref"), x, dy, w, mu1, mu2)
     with np.errstate(invalid="ignore", over="ignore"):
         want = orc.backward(x, dy, w, mu1, mu2, 0.5, need=PARAMS)
     ss = [s for s in range(shape[1]) if s != 3]

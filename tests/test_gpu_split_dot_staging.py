@@ -5,46 +5,15 @@ the per-step loads (libdau_conv_hip_step_loads.so of `make tuning`: -DDAU_SD_STE
 multiple of its block size; region width 12) and on one whose width takes the region width 10 (an odd number of pairs per
 item).  The shipped kernel is byte-identical in the tuning build (test_built_code.py), which is the one compared.
 (The x-side staging itself is unchanged: the one-pass form was measured and not kept)"""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 
 from oracle import dau_oracle as orc
-from util import assert_parity, make_inputs, tuning_capi
+from util import assert_parity, make_inputs, region_width, tuning_capi, variant_capi
 
 pytestmark = pytest.mark.gpu
 
 PARAMS = ("dw", "dmu1", "dmu2", "dsigma")
-_STEP = []
-
-
-def _step_loads_capi():
-    """the ctypes binding over the per-step-loads build (as util.tuning_capi does for the tuning build)"""
-    if not _STEP:
-        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
-        so = os.path.join(pkg, "libdau_conv_hip_step_loads.so")
-        assert os.path.exists(so), "%s missing: run `make -C dau-convnet_amd/csrc tuning` (or __graft_entry__.build())" % so
-        spec = importlib.util.spec_from_file_location("dau_conv_capi_step_loads", os.path.join(pkg, "_capi.py"))
-        mod = importlib.util.module_from_spec(spec)
-        old = os.environ.get("DAU_CONV_LIB")
-        os.environ["DAU_CONV_LIB"] = so
-        try:
-            spec.loader.exec_module(mod)
-        finally:
-            if old is None:
-                del os.environ["DAU_CONV_LIB"]
-            else:
-                os.environ["DAU_CONV_LIB"] = old
-        _STEP.append(mod)
-    return _STEP[0]
-
-
-def _region_width(W):
-    """split_dot_configure's choice"""
-    cost = {rw: -(-(W + 1) // rw) * rw * (rw + 2) * (60 // rw) for rw in (12, 10)}
-    return 12 if cost[12] <= cost[10] else 10
 
 
 def _gradients(capi, x, dy, w, mu1, mu2):
@@ -65,11 +34,11 @@ def _gradients(capi, x, dy, w, mu1, mu2):
 @pytest.mark.parametrize("name,shape,rw", [("ragged", (5, 20, 24, 3, 13, 22), 12), ("width-10", (9, 16, 32, 2, 11, 27), 10)])
 def test_pair_loads_are_bit_identical_to_per_step_loads(name, shape, rw):
     N, S, F, G, H, W = shape
-    assert _region_width(W) == rw
+    assert region_width(W) == rw
     x, dy, w, mu1, mu2 = make_inputs(701 + rw, N, S, F, G, H, W, 9, 3.0)
     mu1.flat[0] = 3.0; mu2.flat[0] = -3.0; mu1.flat[1] = -3.0; mu2.flat[1] = 3.0
     pair = _gradients(tuning_capi(), x, dy, w, mu1, mu2)
-    step = _gradients(_step_loads_capi(), x, dy, w, mu1, mu2)
+    step = _gradients(variant_capi("step_loads"), x, dy, w, mu1, mu2)
     want = orc.backward(x, dy, w, mu1, mu2, 0.5, need=PARAMS)
     for key in PARAMS:
         differ = int((pair[key].view(np.uint32) != step[key].view(np.uint32)).sum())

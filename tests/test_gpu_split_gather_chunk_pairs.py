@@ -5,21 +5,17 @@ input's part -- in the dx pass, a ragged single chunk, dead waves beyond Cout, r
 tiles, tall tiles and the block of four rows.  Bar: the fp32 one of tests/test_gpu_dense_split.py (1e-4 relative + 1e-6 of the
 max-norm against the oracle).  A last chunk without a partner must add exact zeros, read nothing of an absent chunk (poisoned
 workspace) and must not widen the reach of a non-finite input (compared with the 32x32x16 build of the same sources)."""
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import abi_arena as aa
 from oracle import dau_oracle as orc
-from util import assert_parity, make_inputs, run_plan, tuning_capi
+from util import assert_parity, make_inputs, run_plan, tuning_capi, variant_capi
 
 pytestmark = pytest.mark.gpu
 
 _ORACLE = {}
-_PARTNER = []
 
 
 def _flags(capi, extra=0):
@@ -41,27 +37,6 @@ def _oracle(key, x, dy, w, mu1, mu2):
         _ORACLE[key] = dict(y=orc.forward(x, w, mu1, mu2, 0.5), dx=want["dx"], dw=want["dw"], dmu1=want["dmu1"], dmu2=want["dmu2"],
                             dsigma=want["dsigma"])
     return _ORACLE[key]
-
-
-def _partner_capi():
-    """the ctypes binding over libdau_conv_hip_mfma32.so: the same sources with the 32x32x16 tap loop at every radius"""
-    if not _PARTNER:
-        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
-        so = os.path.join(pkg, "libdau_conv_hip_mfma32.so")
-        assert os.path.exists(so), "%s missing: run `make -C dau-convnet_amd/csrc tuning`" % so
-        spec = importlib.util.spec_from_file_location("dau_conv_capi_mfma32", os.path.join(pkg, "_capi.py"))
-        mod = importlib.util.module_from_spec(spec)
-        old = os.environ.get("DAU_CONV_LIB")
-        os.environ["DAU_CONV_LIB"] = so
-        try:
-            spec.loader.exec_module(mod)
-        finally:
-            if old is None:
-                del os.environ["DAU_CONV_LIB"]
-            else:
-                os.environ["DAU_CONV_LIB"] = old
-        _PARTNER.append(mod)
-    return _PARTNER[0]
 
 
 SHAPES = {
@@ -200,7 +175,7 @@ def test_reach_of_a_non_finite_input_in_the_unpaired_chunk(S, channel):
     """An Inf in a channel of the last, unpaired chunk: the non-finite outputs are exactly those of the 32x32x16 build of the same
     call (the outputs of its own image whose taps touch it), and the finite ones meet the bar."""
     from dau_conv import _capi
-    partner = _partner_capi()
+    partner = variant_capi("mfma32")
     N, F, G, H, W = 2, 24, 2, 12, 20
     x, dy, w, mu1, mu2 = _inputs(3, N, S, F, G, H, W)
     xn = x.copy()

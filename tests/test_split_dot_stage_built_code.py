@@ -9,6 +9,7 @@ import tempfile
 import pytest
 
 from test_built_code import PKG, _code_objects, _functions, _kernel_name, _metadata, release  # noqa: F401  (release: the fixture)
+from util import variant_lib
 
 
 def _named(funcs, part):
@@ -21,7 +22,7 @@ def test_release_library_has_no_pass_of_its_own_for_the_xk_maxima(release):
 
 
 def test_stage_ref_build_keeps_the_earlier_staging():
-    so = os.path.join(PKG, "libdau_conv_hip_stage_ref.so")
+    so = variant_lib("stage_ref")
     if not os.path.exists(so):
         pytest.skip("libraries not built")
     with tempfile.TemporaryDirectory() as d:

@@ -12,6 +12,7 @@ import pytest
 
 from test_built_code import PKG, _code_objects, _functions, _kernel_name, _metadata, release  # noqa: F401  (release: the fixture)
 from test_split_dot_built_code import _blocks_that_loop
+from util import variant_lib
 
 K32 = "v_mfma_f32_16x16x32_f16"
 K16 = "v_mfma_f32_32x32x16_f16"
@@ -67,7 +68,7 @@ def test_two_waves_per_simd_and_no_spills():
 
 
 def test_partner_library_keeps_the_32x32x16_loop(release):
-    so = os.path.join(PKG, "libdau_conv_hip_mfma32.so")
+    so = variant_lib("mfma32")
     if not os.path.exists(so):
         pytest.skip("library not built")
     with tempfile.TemporaryDirectory() as d:

@@ -104,19 +104,29 @@ def record_margins(name, got, want, bar):
     return m
 
 
-_TUNING = []
+def region_width(W):
+    """split_dot_configure's choice (k_split_dot.hip) of the split gather-dot's region width for a map W wide"""
+    cost = {rw: -(-(W + 1) // rw) * rw * (rw + 2) * (60 // rw) for rw in (12, 10)}
+    return 12 if cost[12] <= cost[10] else 10
 
 
-def tuning_capi():
-    """A second instance of the ctypes binding, over libdau_conv_hip_tuning.so (`make tuning`: the same sources with
-    -DDAU_TUNING).  Only that build reads the variant-pinning environment variables (DAU_GATHER_VARIANT, DAU_DOT_RW, ...), which the
-    variant tests use to run the kernels production picks for large batches on shapes the oracle finishes in seconds."""
-    if not _TUNING:
+PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
+_VARIANTS = {}
+_TUNING = []          # empty until the tuning binding is loaded, then holds it (tests/conftest.py patches what is in it)
+
+
+def variant_lib(name):
+    """libdau_conv_hip_<name>.so of `make tuning`: "tuning", or a variant of csrc/Makefile's table (`make print-variants`)"""
+    return os.path.join(PKG, "libdau_conv_hip_%s.so" % name)
+
+
+def variant_capi(name):
+    """A further instance of the ctypes binding, over variant_lib(name); loaded once per name."""
+    if name not in _VARIANTS:
         import importlib.util
-        pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dau-convnet_amd", "dau_conv")
-        so = os.path.join(pkg, "libdau_conv_hip_tuning.so")
+        so = variant_lib(name)
         assert os.path.exists(so), "%s missing: run `make -C dau-convnet_amd/csrc tuning` (or __graft_entry__.build())" % so
-        spec = importlib.util.spec_from_file_location("dau_conv_capi_tuning", os.path.join(pkg, "_capi.py"))
+        spec = importlib.util.spec_from_file_location("dau_conv_capi_" + name, os.path.join(PKG, "_capi.py"))
         mod = importlib.util.module_from_spec(spec)
         old = os.environ.get("DAU_CONV_LIB")
         os.environ["DAU_CONV_LIB"] = so
@@ -127,5 +137,14 @@ def tuning_capi():
                 del os.environ["DAU_CONV_LIB"]
             else:
                 os.environ["DAU_CONV_LIB"] = old
-        _TUNING.append(mod)
+        _VARIANTS[name] = mod
+    return _VARIANTS[name]
+
+
+def tuning_capi():
+    """The binding over libdau_conv_hip_tuning.so (the same sources with -DDAU_TUNING).  Only that build reads the
+    variant-pinning environment variables (DAU_GATHER_VARIANT, DAU_DOT_RW, ...), which the variant tests use to run the kernels
+    production picks for large batches on shapes the oracle finishes in seconds."""
+    if not _TUNING:
+        _TUNING.append(variant_capi("tuning"))
     return _TUNING[0]
