@@ -16,6 +16,8 @@
 //      ES1[oct][fb][Vy][Vx][16 f][8 img]        the same with the hi limb only: bf16 activations (below)
 //    Exact power-of-two scales per (s, k) and per f bring each maximum to [2^13, 2^14); the maxima are taken over finite values only
 //    (an Inf / NaN does not remove the scaling of the other channels).  The epilogue undoes them exactly.
+//    XS comes straight from x where the plan allows (sd_xk_walk_kernel below: the filter computed twice, no fp32 copy in between);
+//    other plans filter into the fp32 copy XK (blur4_pack_kernel<K, true>, which also takes the maxima) and split it (sd_stage_x_kernel).
 //  * Main kernel.  Workgroup = (chunk of (image octet, region) items, 16 output channels, 16 input channels, 4 units); region =
 //    4 rows x RW columns of q; the ES window of the 16 channels (RH + 2R rows x RW + 2R columns x 512 B) sits in LDS as a ring of
 //    rows, the items walking down column strips so that each copies only its RH new rows, one item ahead.  A wave owns
@@ -118,7 +120,7 @@ __device__ __forceinline__ bool finite_abs(float v, float* a) {
     return *a <= FLT_MAX;
 }
 
-// max |Xk| per (input channel, kind) is taken by blur4_pack itself while it writes XK (launch_blur4_pack's kmax).
+// On the XK chain max |Xk| per (input channel, kind) is taken by blur4_pack itself while it writes XK (launch_blur4_pack's kmax).
 // -DDAU_SD_STAGE_REF (libdau_conv_hip_stage_ref.so of `make tuning`) keeps the staging that came before: this pass over XK and
 // the sd_stage_e_kernel with one thread per position -- the bit-exact reference of tests/test_gpu_split_dot_stage_fused.py and
 // the A side of kernel-level timings.
@@ -235,6 +237,211 @@ __global__ void __launch_bounds__(256) sd_stage_x_kernel(const float* __restrict
             dst[0] = hi; dst[1] = lo;
         }
     }
+}
+
+// XS straight from x, without the fp32 copy XK in between (NCHW plans with an instantiated prefilter support): the filter is
+// computed twice, by the two instantiations of ONE kernel text.  STORE = false keeps only max |Xk| per (input channel, kind),
+// as the keys of blur4_pack_kernel<K, true>; STORE = true filters again, scales, splits and stores the limbs.  x is read twice
+// (0.41 GB each at the flagship shape) instead of XK being written and read back (1.64 GB each).  Every value is, bit for bit, the
+// one blur4_pack_kernel writes: the same masking of the loads, the same fma chains in the same order (k_blur4_pack_body.hpp).
+//  * A wave (= a workgroup) takes kXwCols columns Tx of one (octet, input channel) and walks down the rows Ty.  Lane 4 c + p owns
+//    column c and the image pair p of the octet (v_pk_fma_f32 on the pair, as blur4_pack packs its pair).
+//  * Per step one raw row of the eight images (the tile's columns plus the filter's reach) goes through LDS, [column][8 images]:
+//    a lane reads the K neighbours of its column as K ds_read_b64, lane-linear.  Two row buffers, so that one wave-level barrier
+//    per row orders the writes of a row before its reads (LDS serves a wave's instructions in order).  The loads of the rows
+//    kXwAhead steps on are in flight meanwhile.
+//  * The K horizontally filtered rows (h1, h2, h3) live in a register ring; the row loop is unrolled K times, so that every slot
+//    is a fixed register.  The vertical pass of output row y runs out of the ring once row y + (K - 1) / 2 is in.
+//  * Store: a lane holds one dword of the hi and one of the lo piece of its column for each kind.  The row's pieces are put
+//    together in LDS in the order of XS, [kind][column][limb][8 images], and go out as two 16-byte stores per lane, 32 consecutive
+//    lanes to 512 consecutive bytes.  The zero row / column in front, those behind the image and the absent images of a partial
+//    octet come out of the same code as masked values.
+constexpr int kXwCols = 16;             // Tx columns per wave
+constexpr int kXwAhead = 3;             // rows whose loads are in flight
+constexpr int kXwOut = kNumK * kXwCols * 2 * 4;   // dwords of a tile row of XS
+struct XkWalkArgs {
+    const float* x;
+    const float* taps;                  // filters + kTaps1dOffset
+    unsigned* xmax;                     // [S][4 kinds] float bits
+    h8* xs;
+    int N, S, H, W, XTr, XTc, nct, act;
+    Guard guard;
+};
+
+__device__ __forceinline__ void xw_wave_sync() {         // orders a wave's LDS writes before the reads of its other lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+template <int N, class F>
+__device__ __forceinline__ void xw_unroll(F&& f) {       // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
+    [&]<int... I>(std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
+}
+// fma(a, {t, t}, c) on an image pair with t one half of a PAIR of taps held in two scalar registers: the op_sel bits pick the half
+// for both lanes.  (As a splat vector hipcc keeps {t, t} per tap: 2 x 6 x K scalar registers, more than there are, and the taps
+// of some loops end up in vector registers.)  The instruction -- and its rounding -- is the v_pk_fma_f32 of blur4_pack_kernel.
+template <int HALF>
+__device__ __forceinline__ f2 xw_fma_tap(f2 a, unsigned long taps, f2 c) {
+    f2 d;
+    if constexpr (HALF == 0) asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(d) : "v"(a), "s"(taps), "v"(c));
+    else asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(d) : "v"(a), "s"(taps), "v"(c));
+    return d;
+}
+
+template <int K, bool STORE, int AF>
+__device__ __forceinline__ void sd_xk_walk(const XkWalkArgs& a, float* lds) {
+    typedef int i4s __attribute__((ext_vector_type(4)));
+    typedef _Float16 h2s __attribute__((ext_vector_type(2)));
+    typedef typename RawAct<AF>::type Raw;
+    constexpr int KR = (K - 1) / 2, CW = kXwCols + 2 * KR, NL = (8 * CW + 63) / 64, kBuf = NL * 64;
+    static_assert(kXwAhead < K, "the rows in flight are slots of the unrolled loop");
+    int t = blockIdx.x;
+    const int ct = t % a.nct; t /= a.nct;
+    const int s = t % a.S, oct = t / a.S;
+    const int lane = threadIdx.x, c = lane >> 2, p = lane & 3;
+    const int H = a.H, W = a.W;
+    const int tx0 = ct * kXwCols, x = tx0 + c - 1;
+    const float* tp[6] = {a.taps + kTapGX * kTapPitch, a.taps + kTapAX * kTapPitch, a.taps + kTapCX * kTapPitch,
+                          a.taps + kTapGY * kTapPitch, a.taps + kTapAY * kTapPitch, a.taps + kTapBY * kTapPitch};
+    unsigned long tq[6][(K + 1) / 2];                   // taps 2 j and 2 j + 1 (the array's pitch holds the one past an odd K)
+#pragma unroll
+    for (int f = 0; f < 6; ++f)
+#pragma unroll
+        for (int j = 0; j < (K + 1) / 2; ++j) tq[f][j] = __builtin_bit_cast(unsigned long, f2{tp[f][2 * j], tp[f][2 * j + 1]});
+    // The raw row of the tile: 8 images x CW columns (image x = tx0 - 1 - KR + column), NL loads per lane, a lane's loads of
+    // one image running along x.  Image slot n of the octet: itself if n < N; the absent second image of the last pair is
+    // 0 * (its partner's value), as blur4_pack computes it (m1); beyond the last pair, +0.  A load outside the row or of an
+    // absent image reads a valid element and is masked.  Slots past the 8 * CW values write the buffer's spare words.
+    long poff[NL];
+    int lw[NL];
+    float mf[NL];
+    bool keep[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) {
+        const int tt = l * 64 + lane, tc = tt < 8 * CW ? tt : 8 * CW - 1;
+        const int img = tc / CW, col = tc - img * CW;
+        const int n = oct * 8 + img;
+        const bool second = (n & 1) && n - 1 < a.N;          // (n >= N) the second image of a pair whose first exists
+        const int src = n < a.N ? n : second ? n - 1 : oct * 8;
+        const int xx = tx0 - 1 - KR + col;
+        keep[l] = tt < 8 * CW && xx >= 0 && xx < W && (n < a.N || second);
+        mf[l] = n < a.N ? 1.0f : 0.0f;
+        poff[l] = ((long)src * a.S + s) * H * W + (xx < 0 ? 0 : xx < W ? xx : W - 1);
+        lw[l] = tt < 8 * CW ? col * 8 + img : tt;
+    }
+    constexpr unsigned kKeyZero = 1u << 24;              // (the keys of blur4_pack_kernel<K, true>)
+    unsigned km[4] = {kKeyZero, kKeyZero, kKeyZero, kKeyZero}, seen[4] = {0u, 0u, 0u, 0u};
+    float sc[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if constexpr (STORE) sc[k] = ldexpf(1.0f, sd_shift(a.xmax[s * kNumK + k]));
+        else seen[k] = __hip_atomic_load(a.xmax + s * kNumK + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // stream row r = u - 1 - KR enters at step u; output row Ty = u - (K - 1) (image row y = Ty - 1) leaves at step u.  The steps
+    // are rounded up to whole rounds of the unrolled loop and a step has no branch but the one around its stores: the steps
+    // before the first output row and after the last one compute on zeros and store nothing.
+    const int steps = (a.XTr + K - 1 + K - 1) / K * K;
+    Raw rv[K][NL];
+    f2 hr[K][3];                                         // ring: slot, filter (h1, h2, h3)
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+        for (int f = 0; f < 3; ++f) hr[i][f] = f2{0.0f, 0.0f};
+    auto load_row = [&](int u, Raw* dst) {
+        const int r = u - 1 - KR, rc = r < 0 ? 0 : r < H ? r : H - 1;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) dst[l] = load_raw<AF>(a.x, poff[l] + (long)rc * W);
+    };
+#pragma unroll
+    for (int d = 0; d < kXwAhead; ++d) load_row(d, rv[d]);
+    // piece lane + 64 i of the tile row: kind 2 i + lane / 32, column (lane % 32) / 2, limb lane % 2
+    const size_t plane = (size_t)a.XTr * a.XTc;
+    h8* const out = a.xs + ((size_t)(oct * a.S + s) * kNumK + (lane >> 5)) * plane * 2 + (size_t)tx0 * 2 + (lane & 31);
+    const bool col_in = tx0 + ((lane & 31) >> 1) < a.XTc;
+    float* obuf = lds + 2 * kBuf;
+    auto step = [&](auto pc, int u) {
+        constexpr int P = decltype(pc)::value;
+        load_row(u + kXwAhead, rv[(P + kXwAhead) % K]);
+        const int r = u - 1 - KR;
+        const bool row_in = r >= 0 && r < H;
+        float* buf = lds + (u & 1) * kBuf;
+#pragma unroll
+        for (int l = 0; l < NL; ++l) buf[lw[l]] = mask_act(mf[l] * act_of(rv[P][l]), keep[l] && row_in);
+        xw_wave_sync();
+        f2 h[3] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+        xw_unroll<K>([&](auto ic) {
+            constexpr int I = decltype(ic)::value, i = I;
+            const f2 v = *reinterpret_cast<const f2*>(buf + (c + i) * 8 + 2 * p);
+#pragma unroll
+            for (int f = 0; f < 3; ++f) h[f] = xw_fma_tap<I & 1>(v, tq[f][I / 2], h[f]);
+        });
+#pragma unroll
+        for (int f = 0; f < 3; ++f) hr[P][f] = h[f];
+        const int ty = u - (K - 1), y = ty - 1;
+        f2 o[4] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
+        xw_unroll<K>([&](auto jc) {
+            constexpr int J = decltype(jc)::value, sl = (P + 1 + J) % K;   // (P + 1: the slot of stream row y - KR)
+            const unsigned long gy = tq[3][J / 2], ay = tq[4][J / 2], by = tq[5][J / 2];
+            const f2 b1 = hr[sl][0], b2 = hr[sl][1], b3 = hr[sl][2];
+            o[0] = xw_fma_tap<J & 1>(b1, gy, o[0]);
+            o[1] = xw_fma_tap<J & 1>(b2, gy, o[1]);
+            o[2] = xw_fma_tap<J & 1>(b1, ay, o[2]);
+            o[3] = xw_fma_tap<J & 1>(b3, gy, o[3]);
+            o[3] = xw_fma_tap<J & 1>(b1, by, o[3]);
+        });
+        // (rows and columns outside the image: +0, whatever the sums over the neighbouring rows gave)
+        const bool in = y >= 0 && y < H && x >= 0 && x < W;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float v0 = mask_act(o[k].x, in), v1 = mask_act(o[k].y, in);
+            if constexpr (!STORE) {
+                km[k] = max(max(km[k], (__float_as_uint(v0) << 1) + kKeyZero), (__float_as_uint(v1) << 1) + kKeyZero);
+            } else {
+                h2s hi, lo;
+                _Float16 hh, ll;
+                split_limbs(v0 * sc[k], &hh, &ll);
+                hi[0] = hh; lo[0] = ll;
+                split_limbs(v1 * sc[k], &hh, &ll);
+                hi[1] = hh; lo[1] = ll;
+                obuf[(k * kXwCols + c) * 8 + p] = __builtin_bit_cast(float, hi);
+                obuf[(k * kXwCols + c) * 8 + 4 + p] = __builtin_bit_cast(float, lo);
+            }
+        }
+        if constexpr (STORE) {
+            xw_wave_sync();
+            const i4s piece0 = *reinterpret_cast<const i4s*>(obuf + lane * 4);
+            const i4s piece1 = *reinterpret_cast<const i4s*>(obuf + (64 + lane) * 4);
+            if (col_in && ty >= 0 && ty < a.XTr) {
+                h8* dst = out + (size_t)ty * a.XTc * 2;
+                dst[0] = __builtin_bit_cast(h8, piece0);
+                dst[2 * plane * 2] = __builtin_bit_cast(h8, piece1);
+            }
+        }
+    };
+#pragma unroll 1
+    for (int u0 = 0; u0 < steps; u0 += K) {
+        xw_unroll<K>([&](auto pc) { step(pc, u0 + decltype(pc)::value); });
+    }
+    if constexpr (!STORE) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned m = km[k];
+            for (int w = 32; w >= 1; w >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, w));
+            // a maximum only grows: what does not exceed the value read when the wave began changes nothing
+            const unsigned bits = (m - kKeyZero) >> 1;
+            if (lane == 0 && bits > seen[k]) atomicMax(a.xmax + s * kNumK + k, bits);
+        }
+    }
+}
+
+template <int K, bool STORE>
+__global__ void __launch_bounds__(64) sd_xk_walk_kernel(const XkWalkArgs a) {
+    constexpr int kBuf = (8 * (kXwCols + K - 1) + 63) / 64 * 64;
+    __shared__ __attribute__((aligned(16))) float lds[2 * kBuf + (STORE ? kXwOut : 0)];
+    if (!guard_pass(a.guard)) return;
+    with_act(a.act, [&](auto actc) { sd_xk_walk<K, STORE, decltype(actc)::value>(a, lds); });
 }
 
 // ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W] (fp32 or f16: act).  An f16 dy times the power-of-two scale is its own
@@ -756,6 +963,37 @@ void launch_sd(hipStream_t st, const SdArgs* a, int grid) {
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kSdWaves * 64), lds, st, *a);
 }
+// Whether the x side of a plan is staged by sd_xk_walk_kernel (from the plan's shape alone): NCHW activations and an instantiated
+// prefilter support.  Everything else -- NHWC plans, other supports -- keeps blur4_pack -> XK -> sd_stage_x_kernel, and so does
+// every plan of the xk_copy build (-DDAU_SD_XK_COPY, libdau_conv_hip_xk_copy.so of `make tuning`: the A/B partner of the walking
+// kernels and the bit-exact reference of tests/test_gpu_split_dot_xk_walk.py) and of the stage_ref build.
+bool sd_walks(const SplitDotConfig& c) {
+#if defined(DAU_SD_XK_COPY) || defined(DAU_SD_STAGE_REF)
+    return false;
+#else
+    const SdGeom g = sd_geom(c);
+    const long nct = (g.XTc + kXwCols - 1) / kXwCols;
+    return !c.nhwc && (c.blur_k == 5 || c.blur_k == 7 || c.blur_k == 9) && (long)g.octs * c.sh.S * nct < (1L << 31);
+#endif
+}
+template <int K, bool STORE>
+void launch_xk_walk(hipStream_t st, const XkWalkArgs& a, int grid) {
+    hipLaunchKernelGGL((sd_xk_walk_kernel<K, STORE>), dim3(grid), dim3(64), 0, st, a);
+}
+template <bool STORE>
+void dispatch_xk_walk(hipStream_t st, const SplitDotConfig& c, const SdGeom& g, const float* x, const float* filters, unsigned* xmax,
+                      h8* xs, const Guard& guard) {
+    XkWalkArgs a{};
+    a.x = x; a.taps = filters + kTaps1dOffset; a.xmax = xmax; a.xs = xs;
+    a.N = c.sh.N; a.S = c.sh.S; a.H = c.sh.H; a.W = c.sh.W; a.XTr = g.XTr; a.XTc = g.XTc; a.act = c.act;
+    a.nct = (g.XTc + kXwCols - 1) / kXwCols;
+    a.guard = guard;
+    const int grid = g.octs * c.sh.S * a.nct;
+    if (c.blur_k == 5) launch_xk_walk<5, STORE>(st, a, grid);
+    else if (c.blur_k == 7) launch_xk_walk<7, STORE>(st, a, grid);
+    else launch_xk_walk<9, STORE>(st, a, grid);
+}
+
 void dispatch_sd(int RW, int e_limbs, hipStream_t st, const SdArgs* a, int grid) {
     if (e_limbs == 1) {
         if (RW == 10) launch_sd<10, 1>(st, a, grid);
@@ -820,8 +1058,11 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     (void)hipMemsetAsync(xmax, 0, (size_t)(s.S * kNumK + s.F) * 4, st);
     (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
     const int HW = s.H * s.W;
+    const bool walks = sd_walks(c);
+    h8* xs = reinterpret_cast<h8*>(ws + l.xs_off);
 #ifndef DAU_SD_STAGE_REF
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax, c.nhwc != 0);
+    if (walks) dispatch_xk_walk<false>(st, c, g, x, filters, xmax, xs, guard);
+    else launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax, c.nhwc != 0);
 #else
     launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, nullptr, c.nhwc != 0);
     const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
@@ -835,8 +1076,8 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
         const int esplit = std::max(1, std::min(16, 2048 / std::max(1, s.F)));
         hipLaunchKernelGGL(sd_absmax_e_kernel, dim3(s.F * esplit), dim3(256), 0, st, dy, s.N, s.F, HW, esplit, c.act, emax, guard);
     }
-    hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc,
-                       reinterpret_cast<h8*>(ws + l.xs_off), guard);
+    if (walks) dispatch_xk_walk<true>(st, c, g, x, filters, xmax, xs, guard);
+    else hipLaunchKernelGGL(sd_stage_x_kernel, dim3(8192), dim3(256), 0, st, xk, xmax, s.N, g.NP, s.S, s.H, s.W, g.octs, g.XTr, g.XTc, xs, guard);
     if (c.e_limbs == 1) {
         const int nct = (g.EXs + kSe1TX - 1) / kSe1TX, tx = (g.EXs + nct - 1) / nct;  // column tiles of a window row, evenly wide
         if (c.nhwc) {
