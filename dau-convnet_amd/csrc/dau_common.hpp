@@ -70,10 +70,10 @@ constexpr int kNhwcArg = 0x100;
 template <class T> struct NhwcOut : T {};
 template <class T> struct IsNhwcOut : std::false_type {};
 template <class T> struct IsNhwcOut<NhwcOut<T>> : std::true_type {};
-// The fused epilogue of a gather-sum's store (dau_conv_forward_epilogue): y = act(sum + bias[f]), act the identity or ReLU, in fp32
-// before the store's one rounding.  Like the NHWC instantiations these are kernels of their own, marked the same way -- kEpiArg or'ed
+// The fused epilogue of a gather-sum's store (dau_conv_forward_epilogue / _residual): y = act((sum + bias[f]) + r[n,f,h,w]), act the
+// identity or ReLU, in fp32 before the store's one rounding.  Like the NHWC instantiations these are kernels of their own, marked the same way -- kEpiArg or'ed
 // into the template's first int argument, the gather-sum's traits wrapped in EpiOut<> -- so that a call without an epilogue runs the
-// kernels it ran before.  One instantiation serves bias, ReLU and both: which of them apply is a kernel argument.
+// kernels it ran before.  One instantiation serves bias, residual, ReLU and their combinations: which of them apply is a kernel argument.
 constexpr int kEpiArg = 0x200;
 template <class T> struct EpiOut : T {};
 template <class T> struct IsEpiOut : std::false_type {};
@@ -82,14 +82,20 @@ template <class T> struct IsNhwcOut<EpiOut<T>> : IsNhwcOut<T> {};
 struct Epilogue {
     const float* bias = nullptr;     // [Cout] fp32, or none
     bool relu = false;
-    bool on() const { return bias != nullptr || relu; }
+    // dau_conv_forward_residual: an array of y's shape, format and layout, added after the bias and before the activation -- or none.
+    // Read only, never y itself.  A run-time pointer inside the same instantiations: one wave-uniform branch per store.
+    const float* residual = nullptr;
+    bool on() const { return bias != nullptr || relu || residual != nullptr; }
 };
-// act(v + b) of the value v the kernel would have stored.  The add is an fp32 add of THAT value: the empty asm in front keeps a
+// act((v + b) + r) of the value v the kernel would have stored.  Each add is an fp32 add of THAT value: the empty asm in front keeps a
 // multiply that produced v from being contracted into it, the one behind keeps the add out of a 16-bit store's conversion
-// (v_fma_mixlo_f16 rounds the exact sum once; the unfused form rounds the fp32 sum).  ReLU as torch.relu: a NaN stays a NaN.
-__device__ __forceinline__ float epilogue_value(float v, float b, bool has_bias, bool relu) {
+// (v_fma_mixlo_f16 rounds the exact sum once; the unfused form rounds the fp32 sum).  The order is fixed, bias first and residual
+// second: for float32 the bits of relu((y + bias) + r).  ReLU as torch.relu: a NaN stays a NaN.
+__device__ __forceinline__ float epilogue_value(float v, float b, bool has_bias, bool relu, float r = 0.0f, bool has_res = false) {
     asm("" : "+v"(v));
     if (has_bias) v = v + b;
+    asm("" : "+v"(v));
+    if (has_res) v = v + r;
     asm("" : "+v"(v));
     return (relu && v <= 0.0f) ? 0.0f : v;
 }

@@ -431,7 +431,8 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
 
 // One gather-sum pass: y from x (kFwd: S -> F, unit table [S][G][F]) or dx from the error (kDx: F -> S, mirrored Gaussian, table
 // [F][G][S] with negated offsets).  `ws`: the tiled workspace, or the direct path's blurred copy.
-// epi (tiled plans, kFwd): the fused epilogue of the stores; a pass of several offset windows gives it to the last window's store
+// epi (tiled plans, kFwd): the fused epilogue of the stores; a pass of several offset windows gives it to the last window's store.
+// Its residual is indexed like `out`: a batch slab reads the images it writes.
 void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float* in, float* out, const float* filters,
                     const UnitRef* table, Status* status, void* ws, const Epilogue& epi = Epilogue{}) {
     const Shape& s = p->sh;
@@ -458,13 +459,15 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
         for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {                 // one slab unless the staged copy exceeds the budget
             const float* ins = slab_ptr(in, (size_t)n0 * cin * s.H * s.W, p->esize());
             float* outs = slab_ptr(out, (size_t)n0 * cout * s.H * s.W, p->esize());
+            Epilogue epis = epi;
+            if (epi.residual) epis.residual = slab_ptr(epi.residual, (size_t)n0 * cout * s.H * s.W, p->esize());
             if (m == kTiledGather) {
                 const TiledConfig& cfg = bs.tiled[dir];
                 const int nwin = tiled_gather_windows(cfg);
                 for (int window = 0; window < nwin; ++window) {   // one pass unless the bucket is 32
                     tiled_gather_prepare(st, cfg, ins, filters, mirrored, table, ws, window, g);
                     ProfScope prof(p, dir, st);
-                    tiled_gather_run(st, cfg, outs, ws, window > 0, g, window + 1 == nwin ? epi : Epilogue{});
+                    tiled_gather_run(st, cfg, outs, ws, window > 0, g, window + 1 == nwin ? epis : Epilogue{});
                 }
             } else {                                                       // a dense member: one GEMM per slab
                 const DenseFns& fn = kDense[m - kSplit2];
@@ -473,9 +476,9 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
                 ProfScope prof(p, dir, st);
                 if (ring) {                                                // the ring pass, then the GEMM whose epilogue adds its sums
                     ring_run(st, bs.ringcfg[dir], s3::split_gather_staged(cfg, ws), ring_ws, status, g);
-                    s3::split_gather_run_add(st, cfg, outs, ring_partial(bs.ringcfg[dir], ring_ws), ws, g, epi);
+                    s3::split_gather_run_add(st, cfg, outs, ring_partial(bs.ringcfg[dir], ring_ws), ws, g, epis);
                 } else {
-                    fn.run(st, cfg, outs, ws, g, epi);
+                    fn.run(st, cfg, outs, ws, g, epis);
                 }
             }
         }
@@ -798,6 +801,24 @@ int dau_conv_forward_epilogue(const dau_conv_plan* p, void* stream, const float*
     Epilogue epi;
     epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
     epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
+    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
+}
+
+int dau_conv_forward_residual(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
+                              const float* mu2, const float* sigma, const float* bias, const float* residual, int epilogue,
+                              float* y, void* workspace, size_t workspace_bytes) {
+    if (!residual) return dau_conv_forward_epilogue(p, stream, x, w, mu1, mu2, sigma, bias, epilogue, y, workspace, workspace_bytes);
+    // the residual is no epilogue bit: it is taken where a bias is (dau_conv_epilogue_supported(p, DAU_EPILOGUE_BIAS)), also with epilogue == 0
+    if (!p || (epilogue & ~(DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU))) return dau_conv_epilogue_supported(p, epilogue);
+    if (p->algo_fwd != DAU_ALGO_TILED)
+        return fail(DAU_INVALID_ARGUMENT, "the direct kernels take no fused residual (this plan's forward pass runs on them)");
+    if (p->d.flags & DAU_FLAG_DENSE_BF16)
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 plans take no fused residual (the bf16-product forms have no epilogue)");
+    if ((epilogue & DAU_EPILOGUE_BIAS) && !bias) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_BIAS without a bias");
+    Epilogue epi;
+    epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
+    epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
+    epi.residual = residual;
     return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
 }
 

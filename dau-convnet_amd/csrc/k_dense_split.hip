@@ -609,6 +609,8 @@ struct SplitArgs {
 struct SplitArgsEpi : SplitArgs {
     const float* bias;        // [Cout] fp32 added to the sums before the store's rounding, or null
     int relu;                 // ... then ReLU
+    const float* residual;    // out's shape, format and layout: added after the bias, before the ReLU; or null
+    int res_vec;              // NHWC: Cout is a multiple of four and the RESIDUAL's base is aligned for loads of four channels
 };
 
 // RG: row groups (of four rows) per workgroup.  2: the eight waves are 4 (32 channels) x 2 (row groups), a wave owns the NSUB tiles of its
@@ -625,6 +627,9 @@ struct SplitArgsEpi : SplitArgs {
 // in out_act), element stores otherwise.  The values and their one rounding are the NCHW epilogue's.
 // NSUBN | kEpiArg: the store is act(v + bias[f]) of the value v the kernel would have stored (with ADD: after the ring's partial sum has
 // joined), in fp32 before the one rounding; the bias is read in the epilogue, after the tap loop, with the channel clamped to Cout - 1.
+// With a residual (a run-time pointer: a wave-uniform branch per store) it is act((v + bias[f]) + r[o]), r read at out's index o in
+// out's format: the NHWC forms with one 16- or 8-byte load per group of four channels where Cout is a multiple of four and the
+// RESIDUAL's base is aligned (res_vec, whatever out's own alignment), element loads with the channel clamped otherwise.
 constexpr int kNhwcVecOut = 0x100;
 template <int NSUBN, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
 __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::conditional<(NSUBN & kEpiArg) != 0, SplitArgsEpi, SplitArgs>::type a) {
@@ -718,12 +723,32 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
     const bool vec_out = NHWC && (a.out_act & kNhwcVecOut) != 0;
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
     const float* bias_ptr = nullptr;
-    bool relu = false;
+    const float* res_ptr = nullptr;
+    bool relu = false, vec_res = false;
     if constexpr (EPI) { bias_ptr = a.bias; relu = a.relu != 0; }
-    // EPI: act(v + bias[f]) of the value the store would have rounded (the channel clamped: a padded channel's value is not stored)
-    auto finished = [&](float v, int f) __attribute__((always_inline)) {
+    // The residual's pointer and its alignment flag are read from the argument segment AFTER the tap loop (the empty asm ties the
+    // address to a sum), as the exact gather reads its epilogue arguments.  Read up front with the bias pointer, they stay in SGPRs
+    // across the loop, and tests/test_built_code.py (test_hot_kernels_touch_no_scratch_between_their_mfmas, at most 8 lane moves
+    // between a kernel's first and last MFMA) then counted 10 in s3::split_gather_kernel<7 | kNhwcArg | kEpiArg, 2, true, false, true>,
+    // the tall-tile NHWC ADD form; with the late read every form is within that test's limit again.
+    auto read_residual = [&](float tie) __attribute__((always_inline)) {
+        if constexpr (EPI) {
+            unsigned long kargs = (unsigned long)__builtin_amdgcn_kernarg_segment_ptr();   // (the kernel's one parameter: offset 0)
+            asm volatile("" : "+s"(kargs) : "v"(tie));
+            const auto* late = reinterpret_cast<const __attribute__((address_space(4))) SplitArgsEpi*>(kargs);
+            res_ptr = late->residual;
+            vec_res = NHWC && late->res_vec != 0;
+        }
+    };
+    // EPI: act((v + bias[f]) + r) of the value the store would have rounded (the channel clamped: a padded channel's value is not stored)
+    auto finished = [&](float v, int f, float r) __attribute__((always_inline)) {
         const int fc = f < out_c ? f : out_c - 1;
-        return epilogue_value(v, bias_ptr ? bias_ptr[fc] : 0.0f, bias_ptr != nullptr, relu);
+        return epilogue_value(v, bias_ptr ? bias_ptr[fc] : 0.0f, bias_ptr != nullptr, relu, r, res_ptr != nullptr);
+    };
+    // the residual's element `o`, widened exactly from out's format
+    auto residual_at = [&](long o) __attribute__((always_inline)) {
+        if constexpr (H16) return load_act_t<kActF16>(res_ptr, o);
+        else return out_bf16 ? load_act_t<kActBF16>(res_ptr, o) : res_ptr[o];
     };
     // ADD: the GEMM's sum joins the ring pass's in fp32, and the store rounds THAT fp32 value once more.  Left to itself hipcc folds
     // the multiply-add into the binary16 store's conversion (v_fma_mixlo_f16), which rounds the exact sum to binary16 at once: not
@@ -740,6 +765,35 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
         if constexpr (NHWC) {
             const long pix = ((long)n * out_h + y) * out_w + x;
             float v[4];
+            float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (EPI) {
+                if (res_ptr) {
+                    const long o = pix * out_c + f0;
+                    if (vec_res) {                             // (Cout is a multiple of four: a group lies inside or outside as a whole)
+                        if (f0 < out_c) {
+                            if constexpr (H16) {
+                                typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                                const f16x4 q = *reinterpret_cast<const f16x4*>(reinterpret_cast<const unsigned short*>(res_ptr) + o);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k) r[k] = (float)q[k];
+                            } else if (out_bf16) {
+                                const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(res_ptr) + o);
+                                r[0] = __uint_as_float(q.x << 16); r[1] = __uint_as_float(q.x & 0xffff0000u);
+                                r[2] = __uint_as_float(q.y << 16); r[3] = __uint_as_float(q.y & 0xffff0000u);
+                            } else {
+                                const float4 q = *reinterpret_cast<const float4*>(res_ptr + o);
+                                r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
+                            }
+                        }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {          // (clamped address; the value is not stored)
+                            const int fc = f0 + k < out_c ? f0 + k : out_c - 1;
+                            r[k] = residual_at(pix * out_c + fc);
+                        }
+                    }
+                }
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if constexpr (ADD) {
@@ -748,7 +802,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
                 } else {
                     v[k] = s[k] * inv_w * inv_x;
                 }
-                if constexpr (EPI) v[k] = finished(v[k], f0 + k);
+                if constexpr (EPI) v[k] = finished(v[k], f0 + k, r[k]);
             }
             const long o = pix * out_c + f0;
             if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
@@ -783,7 +837,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
                         float v;
                         if constexpr (ADD) v = joined(s[k], inv_w, inv_x, part_ptr[o]);
                         else v = s[k] * inv_w * inv_x;
-                        v = finished(v, f);
+                        v = finished(v, f, res_ptr ? residual_at(o) : 0.0f);
                         if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
                         else store_act(out_ptr, o, v, out_bf16, false);
                     } else
@@ -899,6 +953,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
     // the scales are undone by two exact power-of-two multiplies, 1 / sw then this image's 1 / sx[n]: their product may lie outside
     // the fp32 range where the result does not
     const float inv_w = a.sc->inv_sw, inv_x = scales_inv_sx(a.sc, a.N)[n];
+    read_residual(sum[0][0]);
     const int y = rowb + prow + prr;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -1049,6 +1104,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
     }
     // epilogue: C/D layout of a 16x16 tile: column (pixel) = lane & 15, row (channel) = 4 (lane >> 4) + i; the scales as below
     const float inv_w = a.sc->inv_sw, inv_x = scales_inv_sx(a.sc, a.N)[n];
+    read_residual(sum[0][0][0]);
 #pragma unroll
     for (int p = 0; p < NG; ++p) {
         const int y = rowb + prow + (p & 1) * GR + qr, x = colb + TW * (ptile + (p >> 1)) + qc;
@@ -1238,10 +1294,12 @@ void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* pa
     a.out = out; a.partial = partial;
     a.N = c.N; a.Cout = c.Cout; a.CoutP = g.CoutP; a.H = c.H; a.W = c.W; a.Hs = g.Hs; a.Ws = g.Ws; a.nchunk = g.nchunk;
     a.out_act = c.act; a.guard = guard;
-    a.bias = epilogue.bias; a.relu = epilogue.relu ? 1 : 0;
+    a.bias = epilogue.bias; a.relu = epilogue.relu ? 1 : 0; a.residual = epilogue.residual;
     const bool epi = epilogue.on();
     const bool nhwc = c.nhwc != 0;
     if (nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(out) % (c.act == kActF32 ? 16 : 8) == 0) a.out_act |= kNhwcVecOut;
+    // (the residual is another allocation: its own base decides whether its groups of four channels are loaded at once)
+    a.res_vec = epilogue.residual && nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(epilogue.residual) % (c.act == kActF32 ? 16 : 8) == 0;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
         a.nrb = rg == 2 ? g.nrb8 : g.nrb4;
         if (!a.nrb) continue;

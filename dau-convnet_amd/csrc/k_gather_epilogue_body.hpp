@@ -48,7 +48,9 @@
                     const long o = NHWC ? nhwc_index(n, f, gy, gx, DAU_E.Cout, DAU_E.H, DAU_E.W) : ((long)n * DAU_E.Cout + f) * plane_out + (long)gy * DAU_E.W + gx;
                     if constexpr (EPI) {
                         const float sum = DAU_E.accumulate ? load_act(DAU_E.out, o, H16 ? (int)kActF16 : DAU_E.act) + v : v;
-                        const float r = epilogue_value(sum, DAU_E.bias ? DAU_E.bias[f] : 0.0f, DAU_E.bias != nullptr, DAU_E.relu != 0);
+                        const float res = DAU_E.residual ? load_act(DAU_E.residual, o, H16 ? (int)kActF16 : DAU_E.act) : 0.0f;
+                        const float r = epilogue_value(sum, DAU_E.bias ? DAU_E.bias[f] : 0.0f, DAU_E.bias != nullptr, DAU_E.relu != 0, res,
+                                                       DAU_E.residual != nullptr);
                         if constexpr (H16) store_act_t<kActF16>(DAU_E.out, o, r, false);
                         else store_act(DAU_E.out, o, r, DAU_E.act != 0, false);
                     } else

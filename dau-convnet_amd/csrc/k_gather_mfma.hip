@@ -441,6 +441,7 @@ struct GatherArgs {
 struct GatherArgsEpi : GatherArgs {
     const float* bias;         // [Cout] fp32 added to the sums before the store's rounding, or null
     int relu;                  // ... then ReLU
+    const float* residual;     // out's shape, format and layout: added after the bias, before the ReLU; or null
 };
 
 // TX, TY : regular 8x8 tiles of one plane;  PITCH: staged pitch (positions);  EDGE: two extra edge tiles per plane
@@ -984,7 +985,7 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.ut_stride = (unsigned)ut_stride_bytes(c.G, g.fb, g.nwin1 > 1);
     a.zpitch = (unsigned)(g.pw + 2);
     a.debug = c.debug;
-    a.bias = epi.bias; a.relu = epi.relu ? 1 : 0;
+    a.bias = epi.bias; a.relu = epi.relu ? 1 : 0; a.residual = epi.residual;
     const int grid = ((c.NP * c.patches + g.sk - 1) / g.sk) * a.nfb;
     const size_t lds = lds_bytes(c, g);
     dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16, c.nhwc != 0, epi.on());

@@ -94,6 +94,8 @@ def _load():
         lib.dau_conv_epilogue_supported.argtypes = [vp, ctypes.c_int]
         lib.dau_conv_forward_epilogue.argtypes = [vp, vp, fp, fp, fp, fp, fp, fp, ctypes.c_int, fp, vp, ctypes.c_size_t]
         lib.dau_conv_epilogue_backward.argtypes = [vp, vp, fp, fp, ctypes.c_int, fp, fp, vp, ctypes.c_size_t]
+    if hasattr(lib, "dau_conv_forward_residual"):        # (likewise: the residual add of that epilogue)
+        lib.dau_conv_forward_residual.argtypes = [vp, vp, fp, fp, fp, fp, fp, fp, fp, ctypes.c_int, fp, vp, ctypes.c_size_t]
     lib.dau_conv_last_status.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
     lib.dau_conv_filters.argtypes = [vp, vp, fp, fp]
     lib.dau_conv_unit_table.argtypes = [vp, vp, fp, fp, fp, ctypes.c_int, vp]
@@ -218,16 +220,33 @@ class Plan(object):
         _check(lib.dau_conv_epilogue_supported(self._h, int(epilogue)))
         return True
 
-    def forward(self, x, w, mu1, mu2, sigma, bias=None, relu=False):
-        """y, or with bias ([F] float32) / relu the fused epilogue y = act(sum + bias[f]): one fp32 add and a clamp on the value the
-        plain call stores, before the store's one rounding; y keeps the plan's dtype and layout."""
+    def _residual_supported(self):
+        """True if forward() takes a residual: where it takes a bias.  Raises InvalidArgumentError naming the reason otherwise."""
+        if not hasattr(lib, "dau_conv_forward_residual"):
+            raise InvalidArgumentError("this build of the library has no fused residual")
+        try:
+            return self.epilogue_supported(EPILOGUE_BIAS)
+        except InvalidArgumentError as e:
+            raise InvalidArgumentError("no fused residual: %s" % e)
+
+    def forward(self, x, w, mu1, mu2, sigma, bias=None, relu=False, residual=None):
+        """y, or with bias ([F] float32) / residual / relu the fused epilogue y = act((sum + bias[f]) + residual[n,f,h,w]): fp32 adds
+        in that order and a clamp on the value the plain call stores, before the store's one rounding; y keeps the plan's dtype and
+        layout.  residual: a tensor like y (shape, dtype, layout) that is only read; it must not share memory with anything the call
+        writes.  A residual without bias or relu is a plain fused add."""
         pshape = (1, self.S, self.G, self.F)
+        if residual is not None:             # (first: a plan that takes none is refused whatever the tensors are)
+            self._residual_supported()
+            yshape = (self.N, self.F, self.H, self.W)
+            if tuple(residual.shape) != yshape:      # (the shape before the device: a refusal that names the shape wherever the tensor lives)
+                raise InvalidArgumentError("residual has shape %s, expected %s" % (tuple(residual.shape), yshape))
+            _req(residual, "residual", yshape, self.io_dtype, self._io_format)
         _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
         for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
             _req(t, n, pshape)
         if bias is not None:
             _req(bias, "bias", (self.F,))
-        dev = _same_device(x, w, mu1, mu2, sigma, bias)
+        dev = _same_device(x, w, mu1, mu2, sigma, bias, residual)
         epilogue = (EPILOGUE_BIAS if bias is not None else 0) | (EPILOGUE_RELU if relu else 0)
         if epilogue:
             self.epilogue_supported(epilogue)
@@ -235,7 +254,11 @@ class Plan(object):
         with torch.cuda.device(dev):
             y = torch.empty((self.N, self.F, self.H, self.W), dtype=self.io_dtype, device=dev, memory_format=self._io_format)
             ws = self._workspace(PASS_FORWARD, dev)
-            if epilogue:
+            if residual is not None:
+                _check(lib.dau_conv_forward_residual(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma),
+                                                     _ptr(bias) if bias is not None else None, _ptr(residual), epilogue, _ptr(y),
+                                                     _ptr(ws), ws.numel()))
+            elif epilogue:
                 _check(lib.dau_conv_forward_epilogue(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma),
                                                      _ptr(bias), epilogue, _ptr(y), _ptr(ws), ws.numel()))
             else:

@@ -229,15 +229,19 @@ def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_AL
 
 class _DAUConvFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, input, weights, mu1, mu2, sigma, st, bias=None, relu=False):
+    def forward(ctx, input, weights, mu1, mu2, sigma, st, bias=None, relu=False, residual=None):
         weights, mu1, mu2, sigma = _c(weights), _c(mu1), _c(mu2), _c(sigma)
         # a channels_last input runs the NHWC plan where there is one: no copy of x (it is saved as it is), y channels_last
         plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
         input = _act(input, plan)
         _check_before(plan, st["check_offsets"])
-        # bias / relu: the epilogue fused into the store (dau_conv() asks the plan first); y is then saved for the ReLU mask
-        y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu) \
-            if (bias is not None or relu) else plan.forward(input, weights, mu1, mu2, sigma)
+        # bias / residual / relu: the epilogue fused into the store (dau_conv() asks the plan first); y is then saved for the ReLU mask
+        if residual is not None:
+            y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu,
+                             residual=_act(residual, plan))
+        else:
+            y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu) \
+                if (bias is not None or relu) else plan.forward(input, weights, mu1, mu2, sigma)
         _check_after(plan, st["check_offsets"])
         ctx.save_for_backward(*((input, weights, mu1, mu2, sigma) + ((y,) if relu else ())))
         ctx.plan, ctx.st, ctx.relu = plan, st, bool(relu)
@@ -251,20 +255,23 @@ class _DAUConvFunction(torch.autograd.Function):
         for i, bit in enumerate((_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
             if ctx.needs_input_grad[i]:
                 need |= bit
-        n_in = len(ctx.needs_input_grad)             # 6, or 8 with (bias, relu)
+        n_in = len(ctx.needs_input_grad)             # 6, 8 with (bias, relu), 9 with the residual
         need_dbias = n_in > 6 and ctx.needs_input_grad[6]
-        if need == 0 and not need_dbias:
+        need_dres = n_in > 8 and ctx.needs_input_grad[8]
+        if need == 0 and not need_dbias and not need_dres:
             return (None,) * n_in
         _check_before(ctx.plan, ctx.st["check_offsets"])
         grad = _act(grad, ctx.plan)
         dbias = None
-        if need_dbias or (ctx.relu and need):
+        if need_dbias or (ctx.relu and (need or need_dres)):
             # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient (local: it is not exchanged)
             dz, dbias = ctx.plan.epilogue_backward(grad, y, relu=ctx.relu, need_dbias=need_dbias)
             if dz is not None:
                 grad = dz
+        # the residual joins the sum before the activation: its gradient IS the gradient of the sum (dz, or grad without a ReLU)
+        dres = grad if need_dres else None
         if need == 0:
-            return ((None,) * 6 + (dbias, None))[:n_in]
+            return ((None,) * 6 + (dbias, None, dres))[:n_in]
         group = ctx.st["process_group"]
         param_need = need & ~_capi.NEED_DX
         if group is not None and param_need and _group_size(group) > 1:
@@ -273,7 +280,7 @@ class _DAUConvFunction(torch.autograd.Function):
         else:
             out = ctx.plan.backward(input, grad, weights, mu1, mu2, sigma, need)
         _check_after(ctx.plan, ctx.st["check_offsets"])
-        return (out + (None, dbias, None))[:n_in]
+        return (out + (None, dbias, None, dres))[:n_in]
 
 
 def _group_size(group):
@@ -316,23 +323,37 @@ def _epilogue_ok(plan):
     return ok
 
 
-def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, **attrs):
+def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residual=None, **attrs):
     """DAUConv op: output[n,f] = sum_{s,g} w * bilinear(blur_sigma(input[n,s]), . + (mu2, mu1)); differentiable.
     input (and so output) float32, bfloat16 or float16; the parameters are used as float32 whatever their floating dtype.
     bias ([F]) and activation (None or "relu"): output = act(output + bias[f]) fused into the kernels' store -- one fp32 add and a
     clamp before the one rounding, the output keeps the input's dtype, and backward takes the ReLU mask and the bias gradient (in
     the bias's dtype) in one pass.  Plans that have no fused epilogue (shapes on the direct kernels, dense_bf16) run the op, then
-    `+ bias` and relu in torch, with torch's type promotion."""
+    `+ bias` and relu in torch, with torch's type promotion.
+    residual (the shortcut of a residual block): output = act((output + bias[f]) + residual), the bias first.  A residual of the
+    input's dtype and the output's shape is added inside the store as well -- in fp32, before the one rounding; it is brought to the
+    plan's layout (copied only if needed), only read, and its gradient is the tensor backward hands the DAU passes (no extra pass).
+    Any other residual (another dtype, a shape that broadcasts, a plan without the fused epilogue) is added in torch, with torch's
+    promotion, after the op and its bias and before the activation."""
     if activation not in (None, "relu"):
         raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
+    if residual is not None:
+        out_shape = (input.shape[0], weights.shape[-1]) + tuple(input.shape[2:])
+        if not (residual.dtype == input.dtype and tuple(residual.shape) == out_shape):
+            out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, **attrs) + residual
+            return torch.relu(out) if activation == "relu" else out
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
-    if bias is None and activation is None:
+    if bias is None and activation is None and residual is None:
         return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
         raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), weights.shape[-1]))
     if _epilogue_ok(_get_plan(input, weights, st, _wants_nhwc(input, st))):
-        return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st, None if bias is None else _f32(bias), activation == "relu")
+        args = (input, weights, mu1, mu2, sigma, st, None if bias is None else _f32(bias), activation == "relu")
+        return _DAUConvFunction.apply(*(args if residual is None else args + (residual,)))
+    if residual is not None:
+        out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, **attrs) + residual
+        return torch.relu(out) if activation == "relu" else out
     out = _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     if bias is not None:
         out = out + bias.reshape(1, -1, 1, 1)
@@ -476,12 +497,12 @@ class _DAUConvolution2d(object):
         self.grad_reduce = grad_reduce
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
 
-    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None):
+    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None, residual=None):
         # clip in the graph, so clipped units receive zero mu-gradient (dau_conv.py:190-191)
         m = self.mean_max_allowed_offset
         mu1 = torch.clamp(mu1, min=-m, max=m)
         mu2 = torch.clamp(mu2, min=-m, max=m)
-        return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation,
+        return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual,
                         num_output=self.num_output, number_units_x=self.dau_units[0], number_units_y=self.dau_units[1],
                         number_units_ignore=self.num_dau_units_ignore, kernel_size=self.max_kernel_size,
                         pad=int(self.padding), component_border_bound=self.dau_unit_border_bound,
@@ -724,7 +745,7 @@ class DAUConv2d(nn.Module):
         return s, None
 
     # -- call ---------------------------------------------------------------------------------------
-    def forward(self, inputs):
+    def forward(self, inputs, residual=None):
         if not self.built:
             self.build(tuple(inputs.shape))
             self.to(inputs.device)
@@ -734,9 +755,15 @@ class DAUConv2d(nn.Module):
         if self.fused_epilogue:
             # bias and ReLU inside the op's store; both commute with the slicing that emulates strides > 1
             relu = self.activation in (torch.relu, nn.functional.relu) or isinstance(self.activation, nn.ReLU)
+            bias = self._parameters["bias"] if self.use_bias else None
+            if residual is not None and self.strides > 1:
+                # the residual has the SAMPLED shape: the bias stays in the store, the add and the activation follow the slice
+                outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint, bias=bias)
+                outputs = outputs[:, :, ::self.strides, ::self.strides] + residual
+                return self.activation(outputs) if self.activation is not None else outputs
+            # (a residual joins them in the store: act((sum + bias) + residual); one the op cannot fuse it adds in torch)
             outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
-                                               bias=self._parameters["bias"] if self.use_bias else None,
-                                               activation="relu" if relu else None)
+                                               bias=bias, activation="relu" if relu else None, residual=residual)
             if self.strides > 1:
                 outputs = outputs[:, :, ::self.strides, ::self.strides]
             if self.activation is not None and not relu:
@@ -748,6 +775,8 @@ class DAUConv2d(nn.Module):
             outputs = outputs[:, :, ::self.strides, ::self.strides]
         if self.use_bias:
             outputs = outputs + self._parameters["bias"].reshape(1, self.filters, 1, 1)
+        if residual is not None:
+            outputs = outputs + residual
         if self.activation is not None:
             return self.activation(outputs)
         return outputs

@@ -23,6 +23,7 @@
  *                                     -> BaseDAUConvLayer::Backward_gpu (base_dau_conv_layer.cu:130-363)
  *                                     -> DAUConvBackward::backward_pass (dau_conv_backward.cpp:173-232)
  *   dau_conv_forward_epilogue /       the bias add and activation of the Python layer (plugins/tensorflow/dau_conv/dau_conv.py:500-525)
+ *   dau_conv_forward_residual /       (_residual: with a residual block's shortcut added between the two)
  *   dau_conv_epilogue_backward        fused into the forward store, and their gradients in one pass (no reference kernel: TF's own ops)
  *   dau_conv_backward_param_sums /    the two halves of Backward_gpu's parameter-gradient path: the raw sums of K4
  *   dau_conv_finalize_param_grads     (base_dau_conv_layer.cu:232-241) and its elementwise tail (dmu *= w, ignored units,
@@ -303,6 +304,25 @@ DAU_API int dau_conv_epilogue_supported(const dau_conv_plan *plan, int epilogue)
 DAU_API int dau_conv_forward_epilogue(const dau_conv_plan *plan, void *stream, const float *x, const float *w,
                      const float *mu1, const float *mu2, const float *sigma, const float *bias, int epilogue,
                      float *y, void *workspace, size_t workspace_bytes);
+
+/* dau_conv_forward_epilogue with the shortcut of a residual block added between the reference layer's bias_add and its activation
+ * (plugins/tensorflow/dau_conv/dau_conv.py:500-525; the add itself is the network's, e.g. relu(dau(x) + bias + shortcut)):
+ *   y = act((sum + bias[f]) + residual[n,f,h,w])
+ * in that order -- the bias add first, the residual second, each one float32 add, then the optional ReLU, then the store's one
+ * rounding -- so that float32 activations give the bits of relu((dau_conv_forward(...) + bias) + residual).  `residual` has y's shape,
+ * the plan's activation format (float32 / bfloat16 / binary16 behind the float*, widened exactly) and layout ([N][F][H][W], or
+ * [N][H][W][F] under DAU_FLAG_IO_NHWC), and under batch slabs is indexed by the global image as y is.  It is only read, and it must
+ * NOT overlap y (not checked).  Alignment: none beyond the element's; where F is a multiple of four the NHWC stores load four
+ * channels at once if the residual's OWN base is 16-byte (float32) or 8-byte (16-bit) aligned, whatever y's alignment, and fall back
+ * to element loads otherwise -- same bits.  A NaN or Inf in the residual reaches exactly its own element of y.  With several offset
+ * windows the last window's store takes it: act(((old + v) + bias) + residual).  The residual is NOT an epilogue bit: `epilogue` keeps
+ * DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU, and a residual with epilogue == 0 is a plain fused add.  residual == NULL is
+ * dau_conv_forward_epilogue exactly (with epilogue == 0: dau_conv_forward).  A non-NULL residual is accepted where
+ * dau_conv_epilogue_supported(plan, DAU_EPILOGUE_BIAS) is; plans on the direct kernels and DAU_FLAG_DENSE_BF16 plans are refused
+ * with DAU_INVALID_ARGUMENT.  Backward: dau_conv_epilogue_backward's dz is also the residual's gradient (without ReLU: dy itself). */
+DAU_API int dau_conv_forward_residual(const dau_conv_plan *plan, void *stream, const float *x, const float *w,
+                     const float *mu1, const float *mu2, const float *sigma, const float *bias, const float *residual,
+                     int epilogue, float *y, void *workspace, size_t workspace_bytes);
 
 /* Backward of that epilogue -- what autodiff derives from the reference layer's bias_add and activation (same lines) -- in one pass
  * over dy (and, with DAU_EPILOGUE_RELU, the stored y):

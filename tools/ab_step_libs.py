@@ -6,7 +6,9 @@ build's median against the parent's median plus the parent's own min-max spread)
 --lib TAG=PATH adds further builds to the rounds (e.g. bf16_e2=.../libdau_conv_hip_bf16_e2.so), --bench-args the workload
 (e.g. "--io bf16 --no-check", "--workload c2 --io bf16"), --kernels the kernel-name parts the rocprofv3 line keeps,
 --no-prof leaves the rocprofv3 runs out.  The verdict line then also carries, per profile slot (roofline.kernels of bench.py:
-gather_dot, ...), every build's values, median and max - min over the rounds."""
+gather_dot, ...), every build's values, median and max - min over the rounds.
+--fused-layer FORMAT (fp32, f16, bf16) times, instead of bench.py, the layer step with the bias and the ReLU fused into the store
+(tools/fused_epilogue_step_time.py, its `fused` leg, one round of --steps per process): the epilogue kernels of the two builds."""
 import argparse, csv, glob, json, os, statistics, subprocess, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,12 +23,16 @@ ap.add_argument("--bench-args", default="", help="further bench.py arguments, on
 ap.add_argument("--kernels", default="split_absmax,split_scales,split_stage,split_densify,split_gather_kernel",
                 help="comma-separated parts of the kernel names kept from the rocprofv3 statistics")
 ap.add_argument("--no-prof", action="store_true")
+ap.add_argument("--fused-layer", default=None, metavar="FORMAT", help="time the fused bias + ReLU layer step in this format instead of bench.py")
 args = ap.parse_args()
 OUT = os.path.dirname(os.path.abspath(args.out))
 LIBS = [("parent", os.path.abspath(args.parent_lib))] + [(t.split("=", 1)[0], os.path.abspath(t.split("=", 1)[1])) for t in args.lib] + \
        [("this", os.path.join(ROOT, "dau-convnet_amd", "dau_conv", "libdau_conv_hip.so"))]
 ROUNDS, STEPS, WARMUP = args.rounds, args.steps, args.warmup
 BENCH = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(STEPS), "--warmup", str(WARMUP)] + args.bench_args.split()
+if args.fused_layer:
+    BENCH = [sys.executable, os.path.join("tools", "fused_epilogue_step_time.py"), "--formats", args.fused_layer, "--rounds", "1",
+             "--steps", str(STEPS), "--warmup", str(WARMUP)]
 KEEP = tuple(k for k in args.kernels.split(",") if k)
 os.makedirs(OUT, exist_ok=True)
 lines = open(args.out, "w")
@@ -51,6 +57,11 @@ for rnd in range(ROUNDS):
     for tag, lib in LIBS:
         env = dict(os.environ, DAU_CONV_LIB=lib)
         d = json.loads([l for l in run(BENCH, env, 280).splitlines() if l.startswith("{")][-1])
+        if args.fused_layer:
+            ms[tag].append(d["median_ms"]["fused"])
+            emit(dict(call="fused_epilogue_step_time", round=rnd, build=tag, ms_per_step=d["median_ms"]["fused"], format=args.fused_layer,
+                      steps=STEPS, warmup=WARMUP, build_id=d.get("build_id"), workload=d["workload"]))
+            continue
         ms[tag].append(d["ms_per_step"])
         for k, v in ((d.get("roofline") or {}).get("kernels") or {}).items():
             slots[tag].setdefault(k, []).append(v.get("avg_ms"))
@@ -63,7 +74,7 @@ spread = max(ms["parent"]) - min(ms["parent"])
 emit(dict(call="verdict", rounds=ROUNDS, ms_per_step=ms, median_ms=med, parent_min_max_spread_ms=round(spread, 4),
           this_minus_parent_median_ms=round(med["this"] - med["parent"], 4), within_parent_spread=bool(med["this"] <= med["parent"] + spread),
           slots_avg_ms={t: {k: dict(values=v, median=statistics.median(v), max_minus_min=round(max(v) - min(v), 4)) for k, v in sl.items()}
-                        for t, sl in slots.items()}, bench_args=args.bench_args))
+                        for t, sl in slots.items()}, bench_args=args.bench_args, fused_layer=args.fused_layer))
 
 for tag, lib in ([] if args.no_prof else LIBS):
     d = os.path.join(OUT, "prof_" + tag)
