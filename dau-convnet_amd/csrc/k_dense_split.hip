@@ -53,6 +53,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "dau_tiled.hpp"
 
@@ -344,7 +345,8 @@ struct SplitStageArgs {
     _Float16* xs;
     int N, C, H, W, mirrored;
     int Hs, Ws, nchunk;
-    int RB, nbands, nsegs;   // rows per band, bands and 64-column segments per plane
+    int RB, nbands, nsegs;   // rows per band, bands and 64-column segments per plane (walking form: STAGED rows per band, bands, column tiles)
+    int TW;                  // walking form: staged columns per tile
     int vec;                 // rows are whole 4-element pieces (W % 4 == 0, base aligned)
     Guard guard;
 };
@@ -587,6 +589,182 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
     const float sx = scales_sx(a.sc)[n];                           // this image's scale (n is uniform over the workgroup)
     if (x1 - x0 <= 32) split_stage_walk<K, 4>(rawl, py, sx, lane & 31, (lane >> 5) * 4, ya, yb, y0, x0, x1, a.Ws, xhi, xlo);
     else split_stage_walk<K, 8>(rawl, py, sx, lane, 0, ya, yb, y0, x0, x1, a.Ws, xhi, xlo);
+}
+
+// ------------------------------------------------------------------------------------------------
+// staging, walking form (NCHW inputs; -DDAU_SPLIT_STAGE_REF keeps the kernel above for every plan: libdau_conv_hip_split_stage_ref.so,
+// the bit-for-bit reference of tests/test_gpu_split_stage_walk.py and the A/B partner).  The kernel above runs its phases one after
+// the other -- the band's raw window to LDS, barrier, horizontal pass, barrier, vertical pass and stores -- so a workgroup's loads,
+// arithmetic and stores never overlap.  Here a wave (= a workgroup) owns (image, group of 8 channels, tile of <= 64 STAGED columns,
+// band of staged rows) and walks down the rows, as sd_xk_walk_kernel (k_split_dot.hip) does:
+//  * Lane = staged column cs0 + lane (image column x = cs - R); on tiles of <= 32 columns each half wave takes four of the channels.
+//    The tiles cut the STAGED row, so the zero border left and right of the image (and the rows above and below it) are lanes and
+//    steps of the same code whose values are masked to +0: every unit of the plane is written by exactly one store.
+//  * Per step one raw row of the eight channels (the tile's columns plus the filter's reach) goes through LDS, channel pairs interleaved:
+//    element loads, branch free (clamped address, masked value: rows / columns outside the image and the absent channels of a ragged
+//    last group are +0).  Two row buffers and one wave-level barrier per row; the loads of the rows kAhead steps on are in flight.
+//  * Horizontal pass from LDS, acc = fma(row[x - kr + i], gx[i], acc) for i = 0 .. K - 1 from acc = 0 -- split_stage_rows' order.  The K
+//    filtered rows live in a register ring; the row loop is unrolled K times, so that every slot is a fixed register.  Vertical pass
+//    in split_stage_walk's order, then * sx[n], hi = f16(v), lo = f16(v - hi) and one hi and one lo store per lane, consecutive lanes
+//    to consecutive units.  The fmas are v_pk_fma_f32 on channel pairs: per element the same fused multiply-add.
+// ------------------------------------------------------------------------------------------------
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void stage_wave_sync() {     // orders a wave's LDS writes before the reads of its other lanes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int N, class F>
+__device__ __forceinline__ void stage_unroll(F&& f) {   // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>)
+    [&]<int... I>(std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }(std::make_integer_sequence<int, N>{});
+}
+#ifndef DAU_SPLIT_WALK_AHEAD
+#define DAU_SPLIT_WALK_AHEAD 2
+#endif
+constexpr int stage_walk_buf(int K) { return (8 * (64 + K - 1) + 63) / 64 * 64; }   // floats of one row buffer (the 64-column form's)
+
+template <int K, int A, int NCH>
+__device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, float* lds, int n, int grp, int cs0, int cs1, int b0, int b1) {
+    typedef typename RawAct<A>::type Raw;
+    typedef _Float16 f16xn __attribute__((ext_vector_type(NCH)));
+    constexpr int kr = (K - 1) / 2, CW = (NCH == 8 ? 64 : 32) + K - 1, kBuf = stage_walk_buf(K);
+    constexpr int CWL = CW < 64 ? CW : 64, XT = CW - CWL, NX = (8 * XT + 63) / 64, NL = 8 + NX;   // (see the loads below)
+    constexpr int kAhead = K > 3 ? DAU_SPLIT_WALK_AHEAD : 2;   // rows whose loads are in flight (slots of the unrolled loop: < K)
+    static_assert(8 * CW <= kBuf, "the eight channels' rows lie inside the row buffer");
+    const int lane = threadIdx.x, col = NCH == 8 ? lane : lane & 31, ch0 = NCH == 8 ? 0 : (lane >> 5) * 4;
+    const int H = a.H, W = a.W;
+    const long plane = (long)H * W;
+    const float* px = a.taps + (a.mirrored ? kTapGXR : kTapGX) * kTapPitch;
+    const float* py = a.taps + (a.mirrored ? kTapGYR : kTapGY) * kTapPitch;
+    f32x2 gx[K], gy[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) { gx[j] = f32x2{px[j], px[j]}; gy[j] = f32x2{py[j], py[j]}; }
+    // The raw row of the tile: 8 channels x CW columns (image x = cs0 - R - kr + column) as NL loads per lane.  Load l < 8 is
+    // channel l, lane = column (the first 64 columns: one contiguous run per load, one lane offset for all eight); the columns
+    // beyond the 64th of the eight channels share NX further loads, XT columns per channel.  A load outside the row or of an
+    // absent channel reads a valid element of the image and is masked.  A value sits at buf[channel pair][column][channel of the
+    // pair], so that one 8-byte LDS read is the operand of a packed fma.
+    const int xm = cs0 - kDR - kr + lane;
+    const bool okm = lane < CWL && xm >= 0 && xm < W;
+    const unsigned offm = (unsigned)(xm < 0 ? 0 : xm < W ? xm : W - 1);
+    unsigned offx[NX > 0 ? NX : 1], posx[NX > 0 ? NX : 1], okx = 0u;       // (elements from the group's first channel: 8 planes, 32 bits)
+#pragma unroll
+    for (int e = 0; e < NX; ++e) {
+        const int tt = e * 64 + lane, tc = tt < 8 * XT ? tt : 0;
+        const int ch = XT > 0 ? tc / (XT > 0 ? XT : 1) : 0, cl = 64 + tc - ch * XT;
+        const bool chan = grp * 8 + ch < a.C;
+        const int xx = cs0 - kDR - kr + cl;
+        okx |= (tt < 8 * XT ? 1u : 0u) << (2 * e) | (tt < 8 * XT && chan && xx >= 0 && xx < W ? 2u : 0u) << (2 * e);
+        offx[e] = (unsigned)((chan ? ch : 0) * plane) + (unsigned)(xx < 0 ? 0 : xx < W ? xx : W - 1);
+        posx[e] = (unsigned)((ch >> 1) * 2 * CW + cl * 2 + (ch & 1));
+    }
+    const long gbase = ((long)n * a.C + (grp * 8 < a.C ? grp * 8 : 0)) * plane;
+    const float sx = scales_sx(a.sc)[n];                // this image's scale
+    // stream row (image row b0 - R - kr + u) enters at step u; staged row rs = b0 + u - (K - 1) leaves at step u.  The steps are
+    // rounded up to whole rounds of the unrolled loop and a step has no branch but the one around its stores: the steps before the
+    // band's first row and after its last one compute on clamped rows and store nothing.
+    const int steps = (b1 - b0 + K - 1 + K - 1) / K * K;
+    Raw rv[K][NL];
+    f32x2 ring[K][NCH / 2];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+        for (int cp = 0; cp < NCH / 2; ++cp) ring[i][cp] = f32x2{0.0f, 0.0f};
+    auto load_row = [&](int u, Raw* dst) {
+        const int r = b0 - kDR - kr + u, rc = r < 0 ? 0 : r < H ? r : H - 1;
+        const long rowbase = gbase + (long)rc * W;
+#pragma unroll
+        for (int l = 0; l < 8; ++l) dst[l] = load_raw<A>(a.in, rowbase + (grp * 8 + l < a.C ? l : 0) * plane + (long)offm);
+#pragma unroll
+        for (int e = 0; e < NX; ++e) dst[8 + e] = load_raw<A>(a.in, rowbase + (long)offx[e]);
+    };
+#pragma unroll
+    for (int d = 0; d < kAhead; ++d) load_row(d, rv[d]);
+    const int chunk = grp >> 1, half = grp & 1;
+    const long splane = (long)a.Hs * a.Ws;
+    u32x4* const xhi = reinterpret_cast<u32x4*>(a.xs) + ((((long)n * a.nchunk + chunk) * 2 + 0) * 2 + half) * splane;
+    u32x4* const xlo = xhi + 2 * splane;
+    const int cs = cs0 + col, x = cs - kDR;
+    const bool col_in = x >= 0 && x < W, col_st = cs < cs1;
+    auto step = [&](auto pc, int u) {
+        constexpr int P = decltype(pc)::value;
+        load_row(u + kAhead, rv[(P + kAhead) % K]);
+        const int r = b0 - kDR - kr + u;
+        const bool row_in = r >= 0 && r < H;
+        float* buf = lds + (u & 1) * kBuf;
+        if (CWL == 64 || lane < CWL) {
+#pragma unroll
+            for (int l = 0; l < 8; ++l)
+                buf[(l >> 1) * 2 * CW + lane * 2 + (l & 1)] = mask_act(act_of(rv[P][l]), okm && row_in && grp * 8 + l < a.C);
+        }
+#pragma unroll
+        for (int e = 0; e < NX; ++e)
+            if ((okx >> (2 * e)) & 1u) buf[posx[e]] = mask_act(act_of(rv[P][8 + e]), ((okx >> (2 * e)) & 2u) && row_in);
+        stage_wave_sync();
+        f32x2 h[NCH / 2];
+#pragma unroll
+        for (int cp = 0; cp < NCH / 2; ++cp) h[cp] = f32x2{0.0f, 0.0f};
+        const f32x2* row = reinterpret_cast<const f32x2*>(buf) + (ch0 / 2) * CW + col;
+        // (two channel pairs at a time: the LDS reads in flight are registers)
+#pragma unroll
+        for (int c0 = 0; c0 < NCH / 2; c0 += 2) {
+            stage_unroll<K>([&](auto ic) {
+                constexpr int I = decltype(ic)::value;
+#pragma unroll
+                for (int cp = c0; cp < c0 + 2; ++cp) h[cp] = __builtin_elementwise_fma(row[cp * CW + I], gx[I], h[cp]);
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int cp = 0; cp < NCH / 2; ++cp) ring[P][cp] = h[cp];
+        const int rs = b0 + u - (K - 1), y = rs - kDR;
+        f32x2 o[NCH / 2];
+#pragma unroll
+        for (int cp = 0; cp < NCH / 2; ++cp) o[cp] = f32x2{0.0f, 0.0f};
+        stage_unroll<K>([&](auto jc) {
+            constexpr int J = decltype(jc)::value, sl = (P + 1 + J) % K;   // (P + 1: the slot of stream row y - kr)
+#pragma unroll
+            for (int cp = 0; cp < NCH / 2; ++cp) o[cp] = __builtin_elementwise_fma(ring[sl][cp], gy[J], o[cp]);
+        });
+        // (rows and columns outside the image: +0 in both limbs, whatever the sums over the neighbouring rows gave)
+        const bool in = col_in && y >= 0 && y < H;
+        f16xn oh, ol;
+#pragma unroll
+        for (int ch = 0; ch < NCH; ++ch) {
+            float acc = o[ch / 2][ch & 1];
+            acc *= sx;
+            const _Float16 hi = (_Float16)acc;
+            oh[ch] = in ? hi : (_Float16)0.0f;
+            ol[ch] = in ? (_Float16)(acc - (float)hi) : (_Float16)0.0f;
+        }
+        if (col_st && rs >= b0 && rs < b1) {
+            const long o16 = ((long)rs * a.Ws + cs) * 16 + ch0 * 2;
+            *reinterpret_cast<f16xn*>(reinterpret_cast<char*>(xhi) + o16) = oh;
+            *reinterpret_cast<f16xn*>(reinterpret_cast<char*>(xlo) + o16) = ol;
+        }
+    };
+#pragma unroll 1
+    for (int u0 = 0; u0 < steps; u0 += K) {
+        stage_unroll<K>([&](auto pc) { step(pc, u0 + decltype(pc)::value); });
+    }
+}
+
+// (four waves per SIMD -- 128 registers -- up to a support of 7, where the ring and the rows in flight fit)
+#ifndef DAU_SPLIT_WALK_WAVES
+#define DAU_SPLIT_WALK_WAVES 4
+#endif
+template <int K, int A>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 7 ? DAU_SPLIT_WALK_WAVES : 2))) split_stage_walk_kernel(const SplitStageArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[2 * stage_walk_buf(K)];
+    if (!guard_pass(a.guard)) return;
+    int t = blockIdx.x;
+    const int seg = t % a.nsegs; t /= a.nsegs;
+    const int band = t % a.nbands; t /= a.nbands;
+    const int grp = t % (2 * a.nchunk), n = t / (2 * a.nchunk);      // chunk = grp / 2, half = grp & 1
+    const int cs0 = seg * a.TW, cs1 = cs0 + a.TW < a.Ws ? cs0 + a.TW : a.Ws;
+    const int b0 = band * a.RB, b1 = b0 + a.RB < a.Hs ? b0 + a.RB : a.Hs;
+    if (a.TW <= 32) split_stage_walk_tile<K, A, 4>(a, lds, n, grp, cs0, cs1, b0, b1);
+    else split_stage_walk_tile<K, A, 8>(a, lds, n, grp, cs0, cs1, b0, b1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1205,6 +1383,39 @@ const void* stage_for(int blur_k, int act, bool nhwc = false) {
     }
 #undef DAU_SPLIT_STAGE
 }
+// the walking form of the staging: NCHW inputs (-DDAU_SPLIT_STAGE_REF: never)
+const void* stage_walk_for(int blur_k, int act) {
+#ifdef DAU_SPLIT_STAGE_REF
+    return nullptr;
+#else
+#define DAU_SPLIT_STAGE_WALK(K) case K: return act == kActF16 ? reinterpret_cast<const void*>(split_stage_walk_kernel<K, kActF16>) : \
+                                               act == kActBF16 ? reinterpret_cast<const void*>(split_stage_walk_kernel<K, kActBF16>) : \
+                                                                 reinterpret_cast<const void*>(split_stage_walk_kernel<K, kActF32>)
+    switch (blur_k) {
+        DAU_SPLIT_STAGE_WALK(3);
+        DAU_SPLIT_STAGE_WALK(5);
+        DAU_SPLIT_STAGE_WALK(7);
+        DAU_SPLIT_STAGE_WALK(9);
+        DAU_SPLIT_STAGE_WALK(11);
+        default: return nullptr;
+    }
+#undef DAU_SPLIT_STAGE_WALK
+#endif
+}
+// Its tiles and bands.  The staged row in equal tiles of at most 64 columns.  One band -- a wave walks the whole plane -- where that
+// already gives the box two waves per SIMD (2048: the north-star pass is 4096 waves of 68 steps); smaller passes cut the plane into
+// bands of at least 2 K rows (a band filters the K - 1 rows around it again).
+void stage_walk_plan(const DenseConfig& c, const SplitGeom& g, SplitStageArgs* s) {
+    s->nsegs = (g.Ws + 63) / 64;
+    s->TW = (g.Ws + s->nsegs - 1) / s->nsegs;
+    s->nsegs = (g.Ws + s->TW - 1) / s->TW;
+    const long waves = (long)c.N * 2 * g.nchunk * s->nsegs;
+    long nb = (2048 + waves - 1) / waves;
+    nb = std::min<long>(nb, std::max(1, g.Hs / (2 * c.blur_k)));
+    const int rb = DAU_TUNE_INT("DAU_SPLIT_STAGE_WALK_RB", 0);   // tuning build: staged rows per band
+    s->RB = rb > 0 ? rb : (int)((g.Hs + nb - 1) / nb);
+    s->nbands = (g.Hs + s->RB - 1) / s->RB;
+}
 // bands of rows whose raw window (eight channels, rows of kSP floats) stays below ~52 KiB of LDS: three workgroups per CU
 void stage_plan(const DenseConfig& c, int* RB, int* nbands, size_t* lds) {
     const int kr = (c.blur_k - 1) / 2;
@@ -1270,6 +1481,12 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     s.in = in; s.taps = filters + kTaps1dOffset; s.sc = sc; s.xs = xs;
     s.N = c.N; s.C = c.Cin; s.H = c.H; s.W = c.W; s.mirrored = mirrored ? 1 : 0;
     s.Hs = g.Hs; s.Ws = g.Ws; s.nchunk = g.nchunk; s.guard = guard;
+    if (const void* walk = c.nhwc ? nullptr : stage_walk_for(c.blur_k, c.act)) {
+        stage_walk_plan(c, g, &s);
+        void* args[] = {&s};
+        (void)hipLaunchKernel(walk, dim3(c.N * 2 * g.nchunk * s.nbands * s.nsegs), dim3(64), args, 0, st);
+        return;
+    }
     size_t lds;
     stage_plan(c, &s.RB, &s.nbands, &lds);
     s.nsegs = (c.W + 63) / 64;
