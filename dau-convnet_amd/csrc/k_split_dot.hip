@@ -447,13 +447,131 @@ __global__ void __launch_bounds__(64) sd_xk_walk_kernel(const XkWalkArgs a) {
 // ES[oct][fb][Vy][Vx][limb][16 f][8] from dy[N][F][H][W] (fp32 or f16: act).  An f16 dy times the power-of-two scale is its own
 // hi limb; its lo limb is zero.
 #ifndef DAU_SD_STAGE_REF
-// A workgroup writes one window row (oct, fb, Vy) -- a column tile of it where the row is wider than kSeTX positions.  A thread
+constexpr int kSeTX = 80;               // window columns per workgroup of the row kernels: 40 KiB of LDS, four workgroups per CU
+#endif
+#if !defined(DAU_SD_STAGE_REF) && !defined(DAU_SD_STAGE_E_ROWS)
+// The walking form (NCHW plans).  A wave (= a workgroup) owns (octet, block of 16 channels, tile of kSeCols window columns, band of
+// window rows) and walks down the band's rows, as sd_xk_walk_kernel does:
+//  * Lane 16 j + c owns window column vx0 + c and the four channels j, j + 4, j + 8, j + 12 of the block for the whole walk; its 32
+//    element loads of a row (4 channels x the octet's 8 images) are one lane offset per channel plus a wave-uniform (image, row)
+//    base, so the row loop holds no division.  A load instruction reads 16 consecutive x of four channels.
+//  * The loads of the row kSeAhead steps on are in flight while the current row is processed: the row loop is unrolled over the
+//    ring of raw rows, so that every slot is a fixed register.
+//  * A lane then holds the eight images of its (channel, column) pairs: it scales, splits and puts the hi and the lo piece where
+//    they go in the row's image in LDS -- position-major, the 32 pieces of a position permuted by (position & 7) as in the row
+//    kernel below, so that the eight lanes of a ds_write_b128 group (eight consecutive x, one channel) reach all 32 banks.  Two
+//    row images, one wave-level barrier per row.  The row leaves as 16-byte pieces, lane-linear: 1 KiB of ES per store instruction.
+//  * Halo rows and columns, the row / column the edge rule drops, the absent images of a ragged octet and the absent channels of a
+//    ragged block are loads of a valid element masked to +0 (0 * scale = +0 in both limbs): one code path, and every 16-byte piece
+//    of ES is written by exactly one store.
+//  * The grid runs (column tile, band, block, octet), column tile fastest, under xcd_contiguous_id: the tiles of a row, whose loads
+//    share 128-byte lines, go to one L2.
+// -DDAU_SD_STAGE_E_ROWS (libdau_conv_hip_stage_e_rows.so of `make tuning`) keeps the workgroup-per-window-row kernel below: the A/B
+// partner; -DDAU_SD_STAGE_REF keeps the oldest form (one thread per position), the bit-exact reference of
+// tests/test_gpu_split_dot_stage_e_walk.py.
+constexpr int kSeCols = 16;             // window columns per wave: an 8 KiB row image
+constexpr int kSeAhead = 1;             // rows whose loads are in flight (32 loads per lane and row; vmcnt counts to 63)
+struct SeWalkArgs {
+    const float* dy;
+    const unsigned* emax;               // [F] float bits
+    h8* es;
+    int N, F, H, W, nfb, EYs, EXs, nct, nbands, RB, wlim, hlim, act;
+    Guard guard;
+};
+
+template <int AF>
+__device__ __forceinline__ void sd_stage_e_walk(const SeWalkArgs& a, h8* lds) {
+    typedef typename RawAct<AF>::type Raw;
+    constexpr int kRing = kSeAhead + 1, kRow = kSeCols * 32;   // kRow: 16-byte pieces of a row image
+    int t = xcd_contiguous_id(blockIdx.x, gridDim.x);
+    const int ct = t % a.nct; t /= a.nct;
+    const int band = t % a.nbands; t /= a.nbands;
+    const int fb = t % a.nfb, oct = t / a.nfb;
+    const int lane = threadIdx.x, c = lane & (kSeCols - 1), j = lane >> 4;
+    const int H = a.H, W = a.W;
+    const long plane = (long)H * W;
+    const int vx0 = ct * kSeCols, x = vx0 + c - (kSdR + 1);
+    const bool col_in = x >= 0 && x < a.wlim;
+    long off[4];                                         // elements from (image, first channel of the block, row)
+    float sc[4];
+    bool keep[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const int fl = j + 4 * m, f = fb * kSdFB + fl;
+        keep[m] = col_in && f < a.F;
+        sc[m] = f < a.F ? ldexpf(1.0f, sd_shift(a.emax[f])) : 0.0f;
+        off[m] = (f < a.F ? fl : 0) * plane + (x < 0 ? 0 : x < W ? x : W - 1);
+    }
+    const int b0 = band * a.RB, b1 = min(b0 + a.RB, a.EYs);
+    // the steps are rounded up to whole rounds of the unrolled loop: a step past the band's last row loads a clamped row and
+    // stores nothing
+    const int steps = (b1 - b0 + kRing - 1) / kRing * kRing;
+    Raw rv[kRing][32];
+    auto load_row = [&](int vy, Raw* dst) {
+        const int y = vy - (kSdR + 1), yc = y < 0 ? 0 : y < H ? y : H - 1;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int n = oct * 8 + i;
+            const long rowbase = (((long)(n < a.N ? n : oct * 8) * a.F + fb * kSdFB) * H + yc) * W;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) dst[4 * i + m] = load_raw<AF>(a.dy, rowbase + off[m]);
+        }
+    };
+#pragma unroll
+    for (int d = 0; d < kSeAhead; ++d) load_row(b0 + d, rv[d]);
+    h8* const out = a.es + (((size_t)oct * a.nfb + fb) * a.EYs * a.EXs + vx0) * 32 + lane;
+    auto step = [&](auto pc, int u) {
+        constexpr int P = decltype(pc)::value;
+        const int vy = b0 + u, y = vy - (kSdR + 1);
+        load_row(vy + kSeAhead, rv[(P + kSeAhead) % kRing]);
+        const bool row_in = y >= 0 && y < a.hlim;
+        h8* buf = lds + (u & 1) * kRow;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int fl = j + 4 * m;
+            h8 hi, lo;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float v = mask_act(act_of(rv[P][4 * i + m]), keep[m] && row_in && oct * 8 + i < a.N);
+                _Float16 h, l;
+                split_limbs(v * sc[m], &h, &l);
+                hi[i] = h; lo[i] = l;
+            }
+            buf[c * 32 + (fl ^ (c & 7))] = hi;
+            buf[c * 32 + ((kSdFB + fl) ^ (c & 7))] = lo;
+        }
+        xw_wave_sync();
+        // piece lane + 64 i of the row image: position 2 i + lane / 32, piece lane % 32
+        h8 piece[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int lx = 2 * i + (lane >> 5);
+            piece[i] = buf[lx * 32 + ((lane & 31) ^ (lx & 7))];
+        }
+        h8* dst = out + (size_t)vy * a.EXs * 32;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (vy < b1 && vx0 + 2 * i + (lane >> 5) < a.EXs) dst[64 * i] = piece[i];
+    };
+#pragma unroll 1
+    for (int u0 = 0; u0 < steps; u0 += kRing) {
+        xw_unroll<kRing>([&](auto pc) { step(pc, u0 + decltype(pc)::value); });
+    }
+}
+
+__global__ void __launch_bounds__(64) sd_stage_e_kernel(const SeWalkArgs a) {
+    __shared__ h8 lds[2 * kSeCols * 32];
+    if (!guard_pass(a.guard)) return;
+    with_act(a.act, [&](auto actc) { sd_stage_e_walk<decltype(actc)::value>(a, lds); });
+}
+#elif !defined(DAU_SD_STAGE_REF)
+// (the form before the walking one) A workgroup writes one window row (oct, fb, Vy) -- a column tile of it where the row is wider
+// than kSeTX positions.  A thread
 // takes one (channel, x) of the row's image part: its eight loads (the octet's images) run along x across the lanes, it scales
 // and splits in registers and puts the two 16-byte pieces of its eight values where they go in the row's image in LDS; then
 // the workgroup copies the image out, 16 bytes per lane, consecutive lanes to consecutive addresses.  Halo rows and columns
 // (the edge rule's dropped row / column included) are plain zero stores.  The 32 pieces of a position are permuted by
 // (position & 7), so that the eight lanes of a ds_write_b128 group (eight consecutive x, one channel) reach all 32 banks.
-constexpr int kSeTX = 80;               // window columns per workgroup: 40 KiB of LDS, four workgroups per CU
 __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict__ dy, const unsigned* __restrict__ emax, int N,
                                                          int F, int H, int W, int nfb, int EYs, int EXs, int nct, int TX,
                                                          int drop_col, int drop_row, int act, h8* __restrict__ es,
@@ -1096,8 +1214,24 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
                            s.H, s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
         return;
     }
+#ifndef DAU_SD_STAGE_E_ROWS
+    // Bands: about two rounds of the ten waves per CU that the row images leave room for (5120 waves: the north-star pass is 1280
+    // (octet, block, tile) columns in 4 bands of 17 rows), no band below four rows
+    SeWalkArgs w{};
+    w.dy = dy; w.emax = emax; w.es = reinterpret_cast<h8*>(ws + l.es_off);
+    w.N = s.N; w.F = s.F; w.H = s.H; w.W = s.W; w.nfb = g.nfb; w.EYs = g.EYs; w.EXs = g.EXs;
+    w.nct = (g.EXs + kSeCols - 1) / kSeCols;
+    w.wlim = drop_col ? s.W - 1 : s.W; w.hlim = drop_row ? s.H - 1 : s.H; w.act = c.act; w.guard = guard;
+    const long cols = (long)g.octs * g.nfb * w.nct, nb = (5120 + cols - 1) / cols;
+    const int rb = DAU_TUNE_INT("DAU_SD_STAGE_E_RB", 0);     // tuning build: window rows per band
+    w.RB = rb > 0 ? rb : std::max(4, (int)((g.EYs + nb - 1) / nb));
+    w.nbands = (g.EYs + w.RB - 1) / w.RB;
+    hipLaunchKernelGGL(sd_stage_e_kernel, dim3((unsigned)(cols * w.nbands)), dim3(64), 0, st, w);
+    return;
+#else
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3((unsigned)(g.octs * g.nfb * g.EYs * nct)), dim3(256), 0, st, dy, emax, s.N, s.F, s.H,
                        s.W, g.nfb, g.EYs, g.EXs, nct, tx, drop_col, drop_row, c.act, reinterpret_cast<h8*>(ws + l.es_off), guard);
+#endif
 #else
     hipLaunchKernelGGL(sd_stage_e_kernel, dim3(4096), dim3(256), 0, st, dy, emax, s.N, s.F, s.H, s.W, g.octs, g.nfb, g.EYs, g.EXs,
                        drop_col, drop_row, c.act, c.nhwc, reinterpret_cast<h8*>(ws + l.es_off), guard);
