@@ -85,8 +85,14 @@ struct Epilogue {
     // dau_conv_forward_residual: an array of y's shape, format and layout, added after the bias and before the activation -- or none.
     // Read only, never y itself.  A run-time pointer inside the same instantiations: one wave-uniform branch per store.
     const float* residual = nullptr;
-    bool on() const { return bias != nullptr || relu || residual != nullptr; }
+    // DAU_FLAG_INPUT_RELU, the dx pass: the layer's raw x -- out's shape, format and layout -- or none.  The store becomes
+    // (gate[o] <= 0) ? 0 : v, the rule of a threshold at zero (a NaN gate passes v through), after everything above and before the
+    // store's one rounding.  Like the residual a run-time pointer inside the same instantiations, read after the tap loop.
+    const float* gate = nullptr;
+    bool on() const { return bias != nullptr || relu || residual != nullptr || gate != nullptr; }
 };
+// the gate of a store: v where the gate's element is > 0 or a NaN, +0 elsewhere
+__device__ __forceinline__ float gate_value(float v, float g) { return g <= 0.0f ? 0.0f : v; }
 // act((v + b) + r) of the value v the kernel would have stored.  Each add is an fp32 add of THAT value: the empty asm in front keeps a
 // multiply that produced v from being contracted into it, the one behind keeps the add out of a 16-bit store's conversion
 // (v_fma_mixlo_f16 rounds the exact sum once; the unfused form rounds the fp32 sum).  The order is fixed, bias first and residual
@@ -109,6 +115,10 @@ __device__ __forceinline__ int xcd_contiguous_id(int b, int nblk) {
     return (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + idx;
 }
 // v where keep, +0 elsewhere, as a bit mask: with a select hipcc moves the load that produced v under a branch on `keep`
+// DAU_FLAG_INPUT_RELU: the ReLU in front of the layer, applied where a staging kernel widens the x it has loaded: (v <= 0) ? +0 : v, so
+// a NaN stays a NaN and -0 becomes +0.  `on` is a kernel argument (wave-uniform): the same kernels stage dy for the dx pass, unclamped.
+// A select on the loaded value, no branch around the load.
+__device__ __forceinline__ float relu_in(float v, bool on) { return (on && v <= 0.0f) ? 0.0f : v; }
 __device__ __forceinline__ float mask_act(float v, bool keep) { return __uint_as_float(__float_as_uint(v) & (keep ? 0xffffffffu : 0u)); }
 // Load phase of the staging kernels: rows_ x cols_ items of one plane split over the nw waves of its wave group, the loads of
 // kLoadBatch items issued back to back before the first of them is stored to LDS.  These kernels are HBM bound, and a wave with

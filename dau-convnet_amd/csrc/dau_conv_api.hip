@@ -432,7 +432,7 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
 // One gather-sum pass: y from x (kFwd: S -> F, unit table [S][G][F]) or dx from the error (kDx: F -> S, mirrored Gaussian, table
 // [F][G][S] with negated offsets).  `ws`: the tiled workspace, or the direct path's blurred copy.
 // epi (tiled plans, kFwd): the fused epilogue of the stores; a pass of several offset windows gives it to the last window's store.
-// Its residual is indexed like `out`: a batch slab reads the images it writes.
+// Its residual is indexed like `out`: a batch slab reads the images it writes.  Likewise its gate (kDx of a DAU_FLAG_INPUT_RELU plan: the raw x).
 void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float* in, float* out, const float* filters,
                     const UnitRef* table, Status* status, void* ws, const Epilogue& epi = Epilogue{}) {
     const Shape& s = p->sh;
@@ -461,6 +461,7 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
             float* outs = slab_ptr(out, (size_t)n0 * cout * s.H * s.W, p->esize());
             Epilogue epis = epi;
             if (epi.residual) epis.residual = slab_ptr(epi.residual, (size_t)n0 * cout * s.H * s.W, p->esize());
+            if (epi.gate) epis.gate = slab_ptr(epi.gate, (size_t)n0 * cout * s.H * s.W, p->esize());
             if (m == kTiledGather) {
                 const TiledConfig& cfg = bs.tiled[dir];
                 const int nwin = tiled_gather_windows(cfg);
@@ -548,6 +549,9 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     const bool nhwc = (flags & DAU_FLAG_IO_NHWC) != 0;
     if (nhwc && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
+    const bool in_relu = (flags & DAU_FLAG_INPUT_RELU) != 0;
+    if (in_relu && (flags & DAU_FLAG_DENSE_BF16))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_INPUT_RELU excludes DAU_FLAG_DENSE_BF16 (the bf16-product forms have no input prologue)");
 
     std::unique_ptr<dau_conv_plan> p(new (std::nothrow) dau_conv_plan());
     if (!p) return fail(DAU_INTERNAL, "out of host memory");
@@ -563,6 +567,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     // storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does
     // (the staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ
     // likewise the layout: an NHWC plan is the NCHW plan of the same desc, its configs marked after they are made (addresses only)
+    // and the input ReLU: the plan of the same desc, the configs that stage x (forward gather-sum, parameter gradients) marked
     const int act = f16 ? kActF16 : bf16 ? kActBF16 : kActF32;
     const char* budget_env = getenv("DAU_WORKSPACE_BUDGET_GB");
     const double budget_bytes = (budget_env ? atof(budget_env) : 12.0) * 1e9;
@@ -596,6 +601,8 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                 bs.tiled[dir].nhwc = nhwc;
                 for (int m = kSplit2; m <= kSplit4; ++m) bs.dense[m - kSplit2][dir].nhwc = nhwc;
             }
+            bs.tiled[kFwd].in_relu = in_relu;
+            for (int m = kSplit2; m <= kSplit4; ++m) bs.dense[m - kSplit2][kFwd].in_relu = in_relu;
             bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
             if (bs.ring) {
                 bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
@@ -607,6 +614,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             Shape sn = s; sn.N = n;
             bs.has[kTiledDot] = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
             bs.tiled_dot.nhwc = nhwc;
+            bs.tiled_dot.in_relu = in_relu;
             return dot_bytes(bs);
         };
         // slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
@@ -645,6 +653,7 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             bs.has[kSplitDot] = split_allowed && whole_dot && interp2d && (split_forced || fill) &&
                                 split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
             bs.sdot.nhwc = nhwc;
+            bs.sdot.in_relu = in_relu;
         }
     }
     const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
@@ -653,6 +662,8 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                     f16 ? "DAU_FLAG_IO_F16" : "DAU_FLAG_IO_BF16");
     if (nhwc && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC needs the tiled kernels, which do not support this shape / algo");
+    if (in_relu && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_INPUT_RELU needs the tiled kernels, which do not support this shape / algo");
     if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
     p->algo_fwd = (desc->algo != DAU_ALGO_DIRECT && fwd_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
     p->algo_bwd = (desc->algo != DAU_ALGO_DIRECT && dot_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
@@ -898,6 +909,9 @@ int check_backward_ws(const dau_conv_plan* p, void* workspace, size_t workspace_
 int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, const float* dy, const float* w,
                       const float* mu1, const float* mu2, const float* sigma, float* dx, float* dw, float* dmu1,
                       float* dmu2, float* dsigma, void* workspace, size_t workspace_bytes, int need_mask) {
+    // (x: the parameter gradients read it; so does the dx pass of a DAU_FLAG_INPUT_RELU plan, as its mask)
+    if (p && !x && (p->d.flags & DAU_FLAG_INPUT_RELU) && (need_mask & DAU_NEED_DX))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_INPUT_RELU: the input-gradient pass masks dx by x, which is null");
     if (!p || !x || !dy || !w || !mu1 || !mu2 || !sigma || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
     if (((need_mask & DAU_NEED_DX) && !dx) || ((need_mask & DAU_NEED_DW) && !dw) ||
         ((need_mask & DAU_NEED_DMU1) && !dmu1) || ((need_mask & DAU_NEED_DMU2) && !dmu2) ||
@@ -924,7 +938,10 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
         const bool fresh = !(need_mask & param_mask);     // this call has not looked at the offsets yet
         launch_prepare_units(st, w, mu1, mu2, s, 0, flags, p->bucket, true, ws.table_t, fresh ? ws.status : nullptr,
                              p->host_status, p->d.number_units_ignore);
-        run_gather_sum(p, st, kDx, dy, dx, ws.filters, ws.table_t, ws.status, ws.gather_dx);
+        // DAU_FLAG_INPUT_RELU: the ReLU's backward in the store, dx = (x <= 0) ? 0 : sum, from the raw x at the store's own index
+        Epilogue gate;
+        if (flags & DAU_FLAG_INPUT_RELU) gate.gate = x;
+        run_gather_sum(p, st, kDx, dy, dx, ws.filters, ws.table_t, ws.status, ws.gather_dx, gate);
     }
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;

@@ -25,6 +25,7 @@ struct TiledConfig {
     int debug;        // DAU_GATHER_DEBUG at plan creation (timing experiments)
     int act;          // storage format of the activations in and out (ActFormat, dau_common.hpp)
     int nhwc;         // DAU_FLAG_IO_NHWC: in and out are [N][H][W][C] arrays (set by the plan after configure; addresses only)
+    int in_relu;      // DAU_FLAG_INPUT_RELU (set by the plan after configure, forward direction only): prepare clamps `in` at zero as it loads it
 };
 
 bool tiled_gather_configure(int N, int Cin, int Cout, int G, int H, int W, int R, int blur_k, int act, TiledConfig* cfg);
@@ -52,6 +53,8 @@ struct DenseConfig {
     int nsub;         // 8-pixel subtiles per column block = kernel instantiation
     int ftiles;       // 32-channel accumulator tiles per wave (2: four waves per workgroup, 1: eight)
     int nhwc;         // DAU_FLAG_IO_NHWC (the split forms only): in and out are [N][H][W][C] arrays (set by the plan after configure)
+    int in_relu;      // DAU_FLAG_INPUT_RELU (the split forms, forward direction only; set by the plan after configure): prepare clamps `in`
+                      // at zero as it loads it, the per-image maxima included
 };
 // The functions exist once per offset radius of the dense form, in the namespaces r4 (|mu| <= 4: 9 x 9 taps) and r3 (|mu| <= 3:
 // 7 x 7): the same source compiled twice (Makefile); `R` of configure must be the namespace's radius.
@@ -133,6 +136,7 @@ struct TiledDotConfig {
     int ignore;           // number_units_ignore: binned window passes give those units no slot
     int debug;
     int nhwc;             // DAU_FLAG_IO_NHWC: x and dy are [N][H][W][C] arrays (set by the plan after configure)
+    int in_relu;          // DAU_FLAG_INPUT_RELU: x is clamped at zero as it is loaded (set by the plan after configure)
 };
 
 bool tiled_dot_configure(const Shape& sh, int R, int blur_k, int act, int ignore, TiledDotConfig* cfg);
@@ -148,8 +152,10 @@ void tiled_dot_init(const TiledDotConfig& cfg);
 // The four derivative-filtered copies of x, staged position-major (k_gather_dot.hip): x[N,C,H,W] -> xk[NP][cstride][Hp][Wp][4][2].
 // kmax (optional, [cstride][4 kinds] float bits, zeroed by the caller): max |value| per (channel, kind) over the finite values,
 // taken while they are written (a kernel instantiation of its own: callers that pass none run the plain one)
+// in_relu: x is clamped at zero as it is widened (DAU_FLAG_INPUT_RELU; a kernel argument, the same instantiations)
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax = nullptr, bool nhwc = false);
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax = nullptr, bool nhwc = false,
+                       bool in_relu = false);
 void blur4_pack_init(int blur_k, bool kmax = false, bool nhwc = false);
 bool blur4_pack_fits(int blur_k, int Hp, int Wp);
 
@@ -169,6 +175,7 @@ struct SplitDotConfig {
     int act;              // storage format of x and dy (ActFormat)
     int e_limbs;          // binary16 limbs of the staged error: 2, or 1 for bf16 activations
     int nhwc;             // DAU_FLAG_IO_NHWC: x and dy are [N][H][W][C] arrays (set by the plan after configure)
+    int in_relu;          // DAU_FLAG_INPUT_RELU: x is clamped at zero as it is loaded (set by the plan after configure)
 };
 bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);

@@ -56,6 +56,7 @@ __global__ void __launch_bounds__(512) DAU_BLUR4_KERNEL(const Blur4Args a) {
         }
     };
     // raw window -> LDS, the loads of a batch in flight together (load_phase, dau_common.hpp)
+    const bool ri = a.relu_in != 0;
     auto fill = [&](auto actc) {
         constexpr int AF = decltype(actc)::value;
         struct Raw2 { typename RawAct<AF>::type v0, v1; };
@@ -69,7 +70,7 @@ __global__ void __launch_bounds__(512) DAU_BLUR4_KERNEL(const Blur4Args a) {
             [&](int r, int xl, Raw2 v) {
                 const int yy = oy0 - kr + r, xx = ox0 - kr + xl;
                 const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                A[r * lw + xl] = f2{mask_act(m0 * act_of(v.v0), in), mask_act(m1 * act_of(v.v1), in)};
+                A[r * lw + xl] = f2{mask_act(m0 * relu_in(act_of(v.v0), ri), in), mask_act(m1 * relu_in(act_of(v.v1), ri), in)};
             });
     };
     with_act(a.act, fill);

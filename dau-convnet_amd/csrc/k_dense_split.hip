@@ -203,15 +203,19 @@ __device__ __forceinline__ long absmax_head(const void* p, long per, int elem_by
 // aligned to a vector load (S * H * W = 7 * 9 * 6 elements): `head` scalar elements, whole four-element pieces from the first
 // aligned address, the tail scalar again -- a maximum does not depend on which load fetched an element.  Every workgroup also
 // takes its share of the unit table.
+// relu_in (DAU_FLAG_INPUT_RELU): the maximum of the CLAMPED input, x' = (x <= 0) ? 0 : x -- the scales, and with them the staged
+// limbs, are those of the plan without the flag on x'.  One mask: with the sign bit kept, a negative value's bits lie above every
+// finite magnitude and finite_bits drops them like an Inf.
 __global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restrict__ in, long per, int gpi, int act, const UnitRef* __restrict__ table,
-                                                           long units, unsigned* __restrict__ partial, int cap, const Guard guard) {
+                                                           long units, unsigned* __restrict__ partial, int cap, const Guard guard, int relu_in) {
     if (!guard_pass(guard)) return;
     unsigned mx = 0, mw = 0;
+    const unsigned keep = relu_in ? 0xffffffffu : 0x7fffffffu, keep_hi = keep & 0xffff0000u;
     const int n = blockIdx.x / gpi, j = blockIdx.x - n * gpi;
     const long stride = (long)gpi * blockDim.x, t0 = j * (long)blockDim.x + threadIdx.x;
     if (act == kActF16) {
         // the widened values' bits, so that the maximum (and the scales) are those of the same input given as fp32
-        auto wide = [](unsigned h) { return finite_bits(__float_as_uint(f16_bits_to_float(h)) & 0x7fffffffu); };
+        auto wide = [keep](unsigned h) { return finite_bits(__float_as_uint(f16_bits_to_float(h)) & keep); };
         const unsigned short* e = reinterpret_cast<const unsigned short*>(in) + n * per;
         const long head = absmax_head(e, per, 2, 8), n4 = (per - head) / 4;
         const uint2* p = reinterpret_cast<const uint2*>(e + head);    // four f16 per load
@@ -226,20 +230,20 @@ __global__ void __launch_bounds__(256) split_absmax_kernel(const float* __restri
         const uint2* p = reinterpret_cast<const uint2*>(e + head);    // four bf16 per load
         for (long i = t0; i < n4; i += stride) {
             const uint2 v = p[i];
-            mx = max(mx, max(max(finite_bits((v.x << 16) & 0x7fffffffu), finite_bits(v.x & 0x7fff0000u)),
-                             max(finite_bits((v.y << 16) & 0x7fffffffu), finite_bits(v.y & 0x7fff0000u))));
+            mx = max(mx, max(max(finite_bits((v.x << 16) & keep), finite_bits(v.x & keep_hi)),
+                             max(finite_bits((v.y << 16) & keep), finite_bits(v.y & keep_hi))));
         }
-        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(((unsigned)e[i < head ? i : i + n4 * 4] << 16) & 0x7fffffffu));
+        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(((unsigned)e[i < head ? i : i + n4 * 4] << 16) & keep));
     } else {
         const float* e = in + n * per;
         const long head = absmax_head(e, per, 4, 16), n4 = (per - head) / 4;
         const uint4* p = reinterpret_cast<const uint4*>(e + head);
         for (long i = t0; i < n4; i += stride) {
             const uint4 v = p[i];
-            mx = max(mx, max(max(finite_bits(v.x & 0x7fffffffu), finite_bits(v.y & 0x7fffffffu)),
-                             max(finite_bits(v.z & 0x7fffffffu), finite_bits(v.w & 0x7fffffffu))));
+            mx = max(mx, max(max(finite_bits(v.x & keep), finite_bits(v.y & keep)),
+                             max(finite_bits(v.z & keep), finite_bits(v.w & keep))));
         }
-        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(__float_as_uint(e[i < head ? i : i + n4 * 4]) & 0x7fffffffu));
+        for (long i = t0; i < per - n4 * 4; i += stride) mx = max(mx, finite_bits(__float_as_uint(e[i < head ? i : i + n4 * 4]) & keep));
     }
     for (long u = blockIdx.x * (long)blockDim.x + threadIdx.x; u < units; u += (long)gridDim.x * blockDim.x) {
         const UnitRef r = table[u];
@@ -348,6 +352,7 @@ struct SplitStageArgs {
     int RB, nbands, nsegs;   // rows per band, bands and 64-column segments per plane (walking form: STAGED rows per band, bands, column tiles)
     int TW;                  // walking form: staged columns per tile
     int vec;                 // rows are whole 4-element pieces (W % 4 == 0, base aligned)
+    int relu_in;             // DAU_FLAG_INPUT_RELU, forward direction: the widened input is clamped at zero, (v <= 0) ? +0 : v
     Guard guard;
 };
 
@@ -457,6 +462,7 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
     const int x0 = seg * 64, x1 = x0 + 64 < a.W ? x0 + 64 : a.W;
     const int lh = y1 - y0 + 2 * kr;
     const long plane = (long)a.H * a.W;
+    const bool ri = a.relu_in != 0;
     if constexpr (NHWC) {
         // ---- raw window -> LDS: piece (r, j, part) covers image row y0 - kr + r, column x0 - 8 + j, channels grp*8 + part*CPP .. + CPP - 1
         constexpr int CPP = A == kActF32 ? 4 : 8, PARTS = 8 / CPP;
@@ -504,7 +510,7 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
                 const int i = i0 + u * kStageThreads, part = i % PARTS, rj = i / PARTS, r = rj / kSP, j = rj - r * kSP;
                 if (i < pieces) {
 #pragma unroll
-                    for (int k = 0; k < CPP; ++k) rawl[(r * 8 + part * CPP + k) * kSP + j] = v[u][k];
+                    for (int k = 0; k < CPP; ++k) rawl[(r * 8 + part * CPP + k) * kSP + j] = relu_in(v[u][k], ri);
                 }
             }
         }
@@ -551,7 +557,8 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
 #pragma unroll
             for (int u = 0; u < UB; ++u) {
                 const int i = i0 + u * kStageThreads;
-                if (i < pieces) *reinterpret_cast<float4*>(rawl + (long)i * 4) = v[u];      // piece i sits at [r][ch][4q]: i * 4 floats
+                if (i < pieces)                                                                // piece i sits at [r][ch][4q]: i * 4 floats
+                    *reinterpret_cast<float4*>(rawl + (long)i * 4) = make_float4(relu_in(v[u].x, ri), relu_in(v[u].y, ri), relu_in(v[u].z, ri), relu_in(v[u].w, ri));
             }
         }
     }
@@ -686,6 +693,7 @@ __device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, f
     u32x4* const xlo = xhi + 2 * splane;
     const int cs = cs0 + col, x = cs - kDR;
     const bool col_in = x >= 0 && x < W, col_st = cs < cs1;
+    const bool ri = a.relu_in != 0;
     auto step = [&](auto pc, int u) {
         constexpr int P = decltype(pc)::value;
         load_row(u + kAhead, rv[(P + kAhead) % K]);
@@ -695,11 +703,11 @@ __device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, f
         if (CWL == 64 || lane < CWL) {
 #pragma unroll
             for (int l = 0; l < 8; ++l)
-                buf[(l >> 1) * 2 * CW + lane * 2 + (l & 1)] = mask_act(act_of(rv[P][l]), okm && row_in && grp * 8 + l < a.C);
+                buf[(l >> 1) * 2 * CW + lane * 2 + (l & 1)] = mask_act(relu_in(act_of(rv[P][l]), ri), okm && row_in && grp * 8 + l < a.C);
         }
 #pragma unroll
         for (int e = 0; e < NX; ++e)
-            if ((okx >> (2 * e)) & 1u) buf[posx[e]] = mask_act(act_of(rv[P][8 + e]), ((okx >> (2 * e)) & 2u) && row_in);
+            if ((okx >> (2 * e)) & 1u) buf[posx[e]] = mask_act(relu_in(act_of(rv[P][8 + e]), ri), ((okx >> (2 * e)) & 2u) && row_in);
         stage_wave_sync();
         f32x2 h[NCH / 2];
 #pragma unroll
@@ -789,6 +797,9 @@ struct SplitArgsEpi : SplitArgs {
     int relu;                 // ... then ReLU
     const float* residual;    // out's shape, format and layout: added after the bias, before the ReLU; or null
     int res_vec;              // NHWC: Cout is a multiple of four and the RESIDUAL's base is aligned for loads of four channels
+    const float* gate;        // out's shape, format and layout: the store is (gate <= 0) ? 0 : value, after everything else (the dx pass
+                              // of DAU_FLAG_INPUT_RELU: the layer's raw x); or null
+    int gate_vec;             // ... and the GATE's own base likewise
 };
 
 // RG: row groups (of four rows) per workgroup.  2: the eight waves are 4 (32 channels) x 2 (row groups), a wave owns the NSUB tiles of its
@@ -808,6 +819,8 @@ struct SplitArgsEpi : SplitArgs {
 // With a residual (a run-time pointer: a wave-uniform branch per store) it is act((v + bias[f]) + r[o]), r read at out's index o in
 // out's format: the NHWC forms with one 16- or 8-byte load per group of four channels where Cout is a multiple of four and the
 // RESIDUAL's base is aligned (res_vec, whatever out's own alignment), element loads with the channel clamped otherwise.
+// With a gate (likewise a run-time pointer and a wave-uniform branch) the value is then masked, (g[o] <= 0) ? 0 : value, g read like the
+// residual, by its own alignment flag (gate_vec).
 constexpr int kNhwcVecOut = 0x100;
 template <int NSUBN, int RG = 2, bool TT = false, bool H16 = false, bool ADD = false>
 __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::conditional<(NSUBN & kEpiArg) != 0, SplitArgsEpi, SplitArgs>::type a) {
@@ -902,7 +915,8 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
     const int out_c = a.Cout, out_h = a.H, out_w = a.W;
     const float* bias_ptr = nullptr;
     const float* res_ptr = nullptr;
-    bool relu = false, vec_res = false;
+    const float* gate_ptr = nullptr;
+    bool relu = false, vec_res = false, vec_gate = false;
     if constexpr (EPI) { bias_ptr = a.bias; relu = a.relu != 0; }
     // The residual's pointer and its alignment flag are read from the argument segment AFTER the tap loop (the empty asm ties the
     // address to a sum), as the exact gather reads its epilogue arguments.  Read up front with the bias pointer, they stay in SGPRs
@@ -916,6 +930,8 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
             const auto* late = reinterpret_cast<const __attribute__((address_space(4))) SplitArgsEpi*>(kargs);
             res_ptr = late->residual;
             vec_res = NHWC && late->res_vec != 0;
+            gate_ptr = late->gate;
+            vec_gate = NHWC && late->gate_vec != 0;
         }
     };
     // EPI: act((v + bias[f]) + r) of the value the store would have rounded (the channel clamped: a padded channel's value is not stored)
@@ -923,10 +939,37 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
         const int fc = f < out_c ? f : out_c - 1;
         return epilogue_value(v, bias_ptr ? bias_ptr[fc] : 0.0f, bias_ptr != nullptr, relu, r, res_ptr != nullptr);
     };
-    // the residual's element `o`, widened exactly from out's format
-    auto residual_at = [&](long o) __attribute__((always_inline)) {
-        if constexpr (H16) return load_act_t<kActF16>(res_ptr, o);
-        else return out_bf16 ? load_act_t<kActBF16>(res_ptr, o) : res_ptr[o];
+    // element `o` of the residual or the gate, widened exactly from out's format
+    auto element_at = [&](const float* ptr, long o) __attribute__((always_inline)) {
+        if constexpr (H16) return load_act_t<kActF16>(ptr, o);
+        else return out_bf16 ? load_act_t<kActBF16>(ptr, o) : ptr[o];
+    };
+    // NHWC: the four channels f0 .. f0 + 3 of pixel `pix` of the residual or the gate (vec: one load; else element loads, clamped address)
+    auto load4 = [&](const float* ptr, bool vec, long pix, int f0, float (&r)[4]) __attribute__((always_inline)) {
+        const long o = pix * out_c + f0;
+        if (vec) {                                         // (Cout is a multiple of four: a group lies inside or outside as a whole)
+            if (f0 < out_c) {
+                if constexpr (H16) {
+                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+                    const f16x4 q = *reinterpret_cast<const f16x4*>(reinterpret_cast<const unsigned short*>(ptr) + o);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) r[k] = (float)q[k];
+                } else if (out_bf16) {
+                    const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(ptr) + o);
+                    r[0] = __uint_as_float(q.x << 16); r[1] = __uint_as_float(q.x & 0xffff0000u);
+                    r[2] = __uint_as_float(q.y << 16); r[3] = __uint_as_float(q.y & 0xffff0000u);
+                } else {
+                    const float4 q = *reinterpret_cast<const float4*>(ptr + o);
+                    r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                  // (clamped address; the value is not stored)
+                const int fc = f0 + k < out_c ? f0 + k : out_c - 1;
+                r[k] = element_at(ptr, pix * out_c + fc);
+            }
+        }
     };
     // ADD: the GEMM's sum joins the ring pass's in fp32, and the store rounds THAT fp32 value once more.  Left to itself hipcc folds
     // the multiply-add into the binary16 store's conversion (v_fma_mixlo_f16), which rounds the exact sum to binary16 at once: not
@@ -945,32 +988,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
             float v[4];
             float r[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if constexpr (EPI) {
-                if (res_ptr) {
-                    const long o = pix * out_c + f0;
-                    if (vec_res) {                             // (Cout is a multiple of four: a group lies inside or outside as a whole)
-                        if (f0 < out_c) {
-                            if constexpr (H16) {
-                                typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-                                const f16x4 q = *reinterpret_cast<const f16x4*>(reinterpret_cast<const unsigned short*>(res_ptr) + o);
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) r[k] = (float)q[k];
-                            } else if (out_bf16) {
-                                const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(res_ptr) + o);
-                                r[0] = __uint_as_float(q.x << 16); r[1] = __uint_as_float(q.x & 0xffff0000u);
-                                r[2] = __uint_as_float(q.y << 16); r[3] = __uint_as_float(q.y & 0xffff0000u);
-                            } else {
-                                const float4 q = *reinterpret_cast<const float4*>(res_ptr + o);
-                                r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
-                            }
-                        }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {          // (clamped address; the value is not stored)
-                            const int fc = f0 + k < out_c ? f0 + k : out_c - 1;
-                            r[k] = residual_at(pix * out_c + fc);
-                        }
-                    }
-                }
+                if (res_ptr) load4(res_ptr, vec_res, pix, f0, r);
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -981,6 +999,14 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
                     v[k] = s[k] * inv_w * inv_x;
                 }
                 if constexpr (EPI) v[k] = finished(v[k], f0 + k, r[k]);
+            }
+            if constexpr (EPI) {
+                if (gate_ptr) {
+                    float g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    load4(gate_ptr, vec_gate, pix, f0, g);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = gate_value(v[k], g[k]);
+                }
             }
             const long o = pix * out_c + f0;
             if (vec_out) {                                     // (Cout is a multiple of four: the whole group lies inside)
@@ -1015,7 +1041,8 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
                         float v;
                         if constexpr (ADD) v = joined(s[k], inv_w, inv_x, part_ptr[o]);
                         else v = s[k] * inv_w * inv_x;
-                        v = finished(v, f, res_ptr ? residual_at(o) : 0.0f);
+                        v = finished(v, f, res_ptr ? element_at(res_ptr, o) : 0.0f);
+                        if (gate_ptr) v = gate_value(v, element_at(gate_ptr, o));
                         if constexpr (H16) store_act_t<kActF16>(out_ptr, o, v, false);
                         else store_act(out_ptr, o, v, out_bf16, false);
                     } else
@@ -1473,7 +1500,8 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     _Float16* wsd = reinterpret_cast<_Float16*>(ws + g.hdr_bytes + g.xs_bytes);
     const long per = (long)c.Cin * c.H * c.W, units = (long)c.Cin * c.G * c.Cout;
     const int gpi = absmax_groups_per_image(c.N, per), cap = kPartials + c.N;
-    hipLaunchKernelGGL(split_absmax_kernel, dim3(c.N * gpi), dim3(256), 0, st, in, per, gpi, c.act, table, units, partial, cap, guard);
+    hipLaunchKernelGGL(split_absmax_kernel, dim3(c.N * gpi), dim3(256), 0, st, in, per, gpi, c.act, table, units, partial, cap, guard,
+                       (c.in_relu && !mirrored) ? 1 : 0);
     hipLaunchKernelGGL(split_scales_kernel, dim3(c.N + 1), dim3(256), 0, st, partial, c.N, gpi, cap, c.G, sc, guard);
     hipLaunchKernelGGL(split_densify_kernel, dim3(g.nchunk * (g.CoutP / (kScT / 16))), dim3(kScT), 0, st, table, c.Cin, c.G, c.Cout, g.CoutP,
                        g.nchunk, sc, wsd, guard);
@@ -1481,6 +1509,7 @@ void split_gather_prepare(hipStream_t st, const DenseConfig& c, const float* in,
     s.in = in; s.taps = filters + kTaps1dOffset; s.sc = sc; s.xs = xs;
     s.N = c.N; s.C = c.Cin; s.H = c.H; s.W = c.W; s.mirrored = mirrored ? 1 : 0;
     s.Hs = g.Hs; s.Ws = g.Ws; s.nchunk = g.nchunk; s.guard = guard;
+    s.relu_in = (c.in_relu && !mirrored) ? 1 : 0;
     if (const void* walk = c.nhwc ? nullptr : stage_walk_for(c.blur_k, c.act)) {
         stage_walk_plan(c, g, &s);
         void* args[] = {&s};
@@ -1517,6 +1546,8 @@ void run_split(hipStream_t st, const DenseConfig& c, float* out, const float* pa
     if (nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(out) % (c.act == kActF32 ? 16 : 8) == 0) a.out_act |= kNhwcVecOut;
     // (the residual is another allocation: its own base decides whether its groups of four channels are loaded at once)
     a.res_vec = epilogue.residual && nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(epilogue.residual) % (c.act == kActF32 ? 16 : 8) == 0;
+    a.gate = epilogue.gate;
+    a.gate_vec = epilogue.gate && nhwc && c.Cout % 4 == 0 && reinterpret_cast<uintptr_t>(epilogue.gate) % (c.act == kActF32 ? 16 : 8) == 0;
     for (int rg = 2; rg >= 1; --rg) {                        // the eight-row blocks, then the block of four rows where there is one
         a.nrb = rg == 2 ? g.nrb8 : g.nrb4;
         if (!a.nrb) continue;

@@ -315,6 +315,7 @@ struct Blur4Args {
     unsigned* kmax;             // KMAX kernels: max |value| per (channel, kind) over the finite values stored (float bits)
     int N, C, cstride, H, W, k, Hp, Wp;
     int act;                    // storage format of the input (ActFormat)
+    int relu_in;                // DAU_FLAG_INPUT_RELU: the input is clamped at zero as it is widened
     int ppb, items;             // windows per workgroup (small maps) and windows in total
     unsigned lds_item_floats;   // LDS floats per window
     int WY, WX, nwy, nwx;       // output window (rows x columns of the Hp x Wp plane) and windows per plane
@@ -1298,14 +1299,14 @@ const void* blur4_pack_for(int blur_k, bool kmax = false, bool nhwc = false) {
 // x[N,C,H,W] (nhwc: [N,H,W,C]) -> xk[NP][cstride][Hp][Wp][4 kinds][2 images] (fp32), zero beyond the image and in the channel slots C..cstride-1;
 // kmax != nullptr: kmax[cstride][4 kinds] (float bits, zeroed by the caller) receives max |value| over the finite values
 void launch_blur4_pack(hipStream_t st, const float* x, const float* filters, int N, int C, int cstride, int H, int W, int Hp,
-                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax, bool nhwc) {
+                       int Wp, int blur_k, int act, float* xk, const Guard& guard, unsigned* kmax, bool nhwc, bool in_relu) {
     int wy, wx; size_t blur_lds;
     blur4_plan(blur_k, Hp, Wp, &wy, &wx, &blur_lds);
     const void* kern = blur4_pack_for(blur_k, kmax != nullptr, nhwc);
     Blur4Args b{};
     b.guard = guard;
     b.in = x; b.taps = filters + kTaps1dOffset; b.xk = xk; b.kmax = kmax;
-    b.N = N; b.C = C; b.cstride = cstride; b.H = H; b.W = W; b.k = blur_k; b.Hp = Hp; b.Wp = Wp; b.act = act;
+    b.N = N; b.C = C; b.cstride = cstride; b.H = H; b.W = W; b.k = blur_k; b.Hp = Hp; b.Wp = Wp; b.act = act; b.relu_in = in_relu ? 1 : 0;
     b.WY = wy; b.WX = wx; b.nwy = (Hp + wy - 1) / wy; b.nwx = (Wp + wx - 1) / wx;
     // small windows: several per workgroup, so that the 512 threads have rows to share
     const int elems = wy * wx;
@@ -1389,7 +1390,7 @@ void tiled_dot_prepare(hipStream_t st, const TiledDotConfig& c, const float* x, 
     }
     // channel slots beyond S (padding of the last input-channel block) are written as zero planes by the kernel
     launch_blur4_pack(st, x, filters, s.N, s.S, s_pad, s.H, s.W, g.Hp, g.Wp, c.blur_k, c.act, reinterpret_cast<float*>(ws + l.xk_off), guard,
-                      nullptr, c.nhwc != 0);
+                      nullptr, c.nhwc != 0, c.in_relu != 0);
     if (g.nsub1 > 1) {
         const DotGeometry::Pass& ps = g.pass[0];
         hipLaunchKernelGGL(dot_worklist_kernel, dim3(g.nsub1 * g.nsub1 * g.nfb * ps.nsb), dim3(1024), 0, st, table_bare, s.S, s.G, s.F,

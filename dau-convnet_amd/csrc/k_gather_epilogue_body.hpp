@@ -49,8 +49,9 @@
                     if constexpr (EPI) {
                         const float sum = DAU_E.accumulate ? load_act(DAU_E.out, o, H16 ? (int)kActF16 : DAU_E.act) + v : v;
                         const float res = DAU_E.residual ? load_act(DAU_E.residual, o, H16 ? (int)kActF16 : DAU_E.act) : 0.0f;
-                        const float r = epilogue_value(sum, DAU_E.bias ? DAU_E.bias[f] : 0.0f, DAU_E.bias != nullptr, DAU_E.relu != 0, res,
-                                                       DAU_E.residual != nullptr);
+                        float r = epilogue_value(sum, DAU_E.bias ? DAU_E.bias[f] : 0.0f, DAU_E.bias != nullptr, DAU_E.relu != 0, res,
+                                                 DAU_E.residual != nullptr);
+                        if (gate_ptr) r = gate_value(r, load_act(gate_ptr, o, H16 ? (int)kActF16 : DAU_E.act));
                         if constexpr (H16) store_act_t<kActF16>(DAU_E.out, o, r, false);
                         else store_act(DAU_E.out, o, r, DAU_E.act != 0, false);
                     } else

@@ -212,6 +212,7 @@ struct BlurPackArgs {
     float* staged;
     int mirrored, N, C, H, W, R, k;
     int act;                    // storage format of the input (ActFormat)
+    int relu_in;                // DAU_FLAG_INPUT_RELU, forward direction: the input is clamped at zero as it is widened
     int cy, cx;                 // offset-window centre (0 unless the bucket is cut into windows)
     int ph, pw, npx, npy;
     int rows, pitch, cols, strip_cols;
@@ -286,6 +287,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
         }
     };
     // raw window -> LDS, the loads of a batch in flight together (load_phase, dau_common.hpp)
+    const bool ri = a.relu_in != 0;
     auto fill = [&](auto actc) {
         constexpr int AF = decltype(actc)::value;
         struct Raw2 { typename RawAct<AF>::type v0, v1; };
@@ -299,7 +301,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(DAU_BL
             [&](int r, int xl, Raw2 v) {
                 const int yy = ya0 - kr + r, xx = xa0 - kr + xl;
                 const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
-                A[r * lw + xl] = f2{mask_act(act_of(v.v0), in), mask_act(m1 * act_of(v.v1), in)};
+                A[r * lw + xl] = f2{mask_act(relu_in(act_of(v.v0), ri), in), mask_act(m1 * relu_in(act_of(v.v1), ri), in)};
             });
     };
     with_act(a.act, fill);
@@ -443,6 +445,15 @@ struct GatherArgsEpi : GatherArgs {
     int relu;                  // ... then ReLU
     const float* residual;     // out's shape, format and layout: added after the bias, before the ReLU; or null
 };
+// ... and their ONE kernel parameter: GatherArgsEpi at offset 0, which gather_body copies late as it always did, and behind it the gate
+// of the dx pass of a DAU_FLAG_INPUT_RELU plan -- out's shape, format and layout: the store is (gate <= 0) ? 0 : value; or null.  The
+// gate is read from the argument segment by itself (a scalar load at its offset): inside the copied struct it changed the copy.
+struct GatherArgsGate {
+    GatherArgsEpi e;
+    const float* gate;
+};
+constexpr size_t kGateArgOffset = sizeof(GatherArgsEpi);     // (a struct of pointers and ints: its size is a multiple of the pointer's)
+static_assert(sizeof(GatherArgsGate) == kGateArgOffset + sizeof(const float*), "the gate lies right behind GatherArgsEpi");
 
 // TX, TY : regular 8x8 tiles of one plane;  PITCH: staged pitch (positions);  EDGE: two extra edge tiles per plane
 // SPLIT  : waves sharing one output channel (tiles are dealt out in contiguous ranges)
@@ -736,14 +747,17 @@ __device__ __forceinline__ void gather_body(const Args& a, char* smem, int lane,
     // from the argument segment HERE, after the tap loop (the empty asm ties the address to an accumulator), instead of sitting in
     // SGPRs across it: the stacked-plane kernels have none to spare, and what does not fit is moved through VGPR lanes between
     // the MFMAs.  The other instantiations run the same text (k_gather_epilogue_body.hpp) on their arguments as they are.
+    const float* gate_ptr = nullptr;
     if constexpr (EPI) {
-        // (Args is the kernel's ONE parameter -- gather_mfma_kernel(const Args a) -- so it lies at offset 0 of the argument segment;
+        // (Args lies at offset 0 of the kernel's ONE parameter -- gather_mfma_kernel(const GatherArgsGate a), a.e -- so at offset 0 of the argument segment;
         // a second parameter in front of it would have to move this address along)
         static_assert(std::is_trivially_copyable<Args>::value, "the argument struct is copied bytewise from the argument segment");
         unsigned long kargs = (unsigned long)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(kargs) : "v"(acc[0][0][0]));
         Args late;                                            // (copied member-free: the argument segment is another address space)
         __builtin_memcpy(&late, reinterpret_cast<const __attribute__((address_space(4))) char*>(kargs), sizeof(Args));
+        typedef const float* gate_t;
+        gate_ptr = *reinterpret_cast<const __attribute__((address_space(4))) gate_t*>(kargs + kGateArgOffset);
         // (run as a lambda on the copy: hipcc then keeps the copy's SGPRs out of the tap loop's allocation)
         auto epilogue = [&](const Args& e) __attribute__((always_inline)) {
 #define DAU_E e
@@ -759,8 +773,9 @@ __device__ __forceinline__ void gather_body(const Args& a, char* smem, int lane,
 }
 
 template <class T, bool H16>
-__global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const typename std::conditional<IsEpiOut<T>::value, GatherArgsEpi, GatherArgs>::type a) {
+__global__ void __launch_bounds__(T::kThreads) gather_mfma_kernel(const typename std::conditional<IsEpiOut<T>::value, GatherArgsGate, GatherArgs>::type ka) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const auto& a = [&]() -> const auto& { if constexpr (IsEpiOut<T>::value) return ka.e; else return ka; }();
     if (!guard_pass(a.guard)) return;
     constexpr int SPLIT = T::SPLIT;
     const int lane = threadIdx.x & 63;
@@ -795,7 +810,7 @@ namespace {
 // nhwc: the instantiations that store [N][H][W][Cout] (DAU_FLAG_IO_NHWC)
 // epi: the instantiations whose store is act(sum + bias[f]) (dau_conv_forward_epilogue)
 template <class T>
-void launch_variant(hipStream_t st, const GatherArgsEpi* a, int grid, size_t lds, bool h16, bool nhwc, bool epi) {
+void launch_variant(hipStream_t st, const GatherArgsGate* a, int grid, size_t lds, bool h16, bool nhwc, bool epi) {
     if (epi) {
         auto kern = nhwc ? (h16 ? gather_mfma_kernel<EpiOut<NhwcOut<T>>, true> : gather_mfma_kernel<EpiOut<NhwcOut<T>>, false>)
                          : (h16 ? gather_mfma_kernel<EpiOut<T>, true> : gather_mfma_kernel<EpiOut<T>, false>);
@@ -806,10 +821,10 @@ void launch_variant(hipStream_t st, const GatherArgsEpi* a, int grid, size_t lds
     auto kern = nhwc ? (h16 ? gather_mfma_kernel<NhwcOut<T>, true> : gather_mfma_kernel<NhwcOut<T>, false>)
                      : (h16 ? gather_mfma_kernel<T, true> : gather_mfma_kernel<T, false>);
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, static_cast<const GatherArgs&>(*a));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::kThreads), lds, st, static_cast<const GatherArgs&>(a->e));
 }
 
-void dispatch_variant(int variant, hipStream_t st, const GatherArgsEpi* a, int grid, size_t lds, bool h16, bool nhwc, bool epi = false) {
+void dispatch_variant(int variant, hipStream_t st, const GatherArgsGate* a, int grid, size_t lds, bool h16, bool nhwc, bool epi = false) {
     switch (variant) {
         case 0: launch_variant<GatherTraits<7, 7, 72, true, 2>>(st, a, grid, lds, h16, nhwc, epi); break;
         case 1: launch_variant<GatherTraits<7, 7, 104, true, 2>>(st, a, grid, lds, h16, nhwc, epi); break;
@@ -931,7 +946,7 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
     // centre of this pass's offset window: staged (row, col) of a patch is the image at (py*ph - Rt + cy + row, ...)
     const int cy = -c.R + g.Rt + 2 * g.Rt * (window / g.nwin1), cx = -c.R + g.Rt + 2 * g.Rt * (window % g.nwin1);
     b.mirrored = mirrored ? 1 : 0; b.N = c.N; b.C = c.Cin; b.H = c.H; b.W = c.W; b.R = g.Rt; b.k = c.blur_k;
-    b.cy = cy; b.cx = cx; b.act = c.act;
+    b.cy = cy; b.cx = cx; b.act = c.act; b.relu_in = (c.in_relu && !mirrored) ? 1 : 0;
     b.ph = g.ph; b.pw = g.pw; b.npx = g.npx; b.npy = g.npy;
     b.rows = g.rows; b.pitch = g.pitch; b.cols = g.cols; b.strip_cols = g.edge ? 2 * g.Rt + 1 : 0;
     b.plane_floats = g.plane_bytes / 4;
@@ -970,7 +985,8 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
 void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* workspace, bool accumulate, const Guard& guard,
                       const Epilogue& epi) {
     const Geometry g = make_geometry(c.H, c.W, c.R, c.G, c.N, c.Cout, c.variant);
-    GatherArgsEpi a{};
+    GatherArgsGate ga{};
+    GatherArgsEpi& a = ga.e;
     a.staged = static_cast<const char*>(workspace);
     a.packed = a.staged + round_up((size_t)c.NP * c.patches * c.Cin * g.plane_bytes, 256);
     a.out = out;
@@ -985,10 +1001,10 @@ void tiled_gather_run(hipStream_t st, const TiledConfig& c, float* out, void* wo
     a.ut_stride = (unsigned)ut_stride_bytes(c.G, g.fb, g.nwin1 > 1);
     a.zpitch = (unsigned)(g.pw + 2);
     a.debug = c.debug;
-    a.bias = epi.bias; a.relu = epi.relu ? 1 : 0; a.residual = epi.residual;
+    a.bias = epi.bias; a.relu = epi.relu ? 1 : 0; a.residual = epi.residual; ga.gate = epi.gate;
     const int grid = ((c.NP * c.patches + g.sk - 1) / g.sk) * a.nfb;
     const size_t lds = lds_bytes(c, g);
-    dispatch_variant(c.variant, st, &a, grid, lds, c.act == kActF16, c.nhwc != 0, epi.on());
+    dispatch_variant(c.variant, st, &ga, grid, lds, c.act == kActF16, c.nhwc != 0, epi.on());
 }
 
 }  // namespace dau

@@ -265,6 +265,7 @@ struct XkWalkArgs {
     unsigned* xmax;                     // [S][4 kinds] float bits
     h8* xs;
     int N, S, H, W, XTr, XTc, nct, act;
+    int relu_in;                        // DAU_FLAG_INPUT_RELU: x is clamped at zero as it is widened (both passes: the maxima are those of the clamped x)
     Guard guard;
 };
 
@@ -361,6 +362,7 @@ __device__ __forceinline__ void sd_xk_walk(const XkWalkArgs& a, float* lds) {
     h8* const out = a.xs + ((size_t)(oct * a.S + s) * kNumK + (lane >> 5)) * plane * 2 + (size_t)tx0 * 2 + (lane & 31);
     const bool col_in = tx0 + ((lane & 31) >> 1) < a.XTc;
     float* obuf = lds + 2 * kBuf;
+    const bool ri = a.relu_in != 0;
     auto step = [&](auto pc, int u) {
         constexpr int P = decltype(pc)::value;
         load_row(u + kXwAhead, rv[(P + kXwAhead) % K]);
@@ -368,7 +370,7 @@ __device__ __forceinline__ void sd_xk_walk(const XkWalkArgs& a, float* lds) {
         const bool row_in = r >= 0 && r < H;
         float* buf = lds + (u & 1) * kBuf;
 #pragma unroll
-        for (int l = 0; l < NL; ++l) buf[lw[l]] = mask_act(mf[l] * act_of(rv[P][l]), keep[l] && row_in);
+        for (int l = 0; l < NL; ++l) buf[lw[l]] = mask_act(mf[l] * relu_in(act_of(rv[P][l]), ri), keep[l] && row_in);
         xw_wave_sync();
         f2 h[3] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};
         xw_unroll<K>([&](auto ic) {
@@ -1103,7 +1105,7 @@ void dispatch_xk_walk(hipStream_t st, const SplitDotConfig& c, const SdGeom& g, 
                       h8* xs, const Guard& guard) {
     XkWalkArgs a{};
     a.x = x; a.taps = filters + kTaps1dOffset; a.xmax = xmax; a.xs = xs;
-    a.N = c.sh.N; a.S = c.sh.S; a.H = c.sh.H; a.W = c.sh.W; a.XTr = g.XTr; a.XTc = g.XTc; a.act = c.act;
+    a.N = c.sh.N; a.S = c.sh.S; a.H = c.sh.H; a.W = c.sh.W; a.XTr = g.XTr; a.XTc = g.XTc; a.act = c.act; a.relu_in = c.in_relu;
     a.nct = (g.XTc + kXwCols - 1) / kXwCols;
     a.guard = guard;
     const int grid = g.octs * c.sh.S * a.nct;
@@ -1180,9 +1182,9 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     h8* xs = reinterpret_cast<h8*>(ws + l.xs_off);
 #ifndef DAU_SD_STAGE_REF
     if (walks) dispatch_xk_walk<false>(st, c, g, x, filters, xmax, xs, guard);
-    else launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax, c.nhwc != 0);
+    else launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, xmax, c.nhwc != 0, c.in_relu != 0);
 #else
-    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, nullptr, c.nhwc != 0);
+    launch_blur4_pack(st, x, filters, s.N, s.S, s.S, s.H, s.W, s.H, s.W, c.blur_k, c.act, xk, guard, nullptr, c.nhwc != 0, c.in_relu != 0);
     const int xsplit = std::max(1, std::min(16, 2048 / std::max(1, s.S)));
     hipLaunchKernelGGL(sd_absmax_x_kernel, dim3(s.S * xsplit), dim3(256), 0, st, xk, g.NP, s.S, HW, xsplit, xmax, guard);
 #endif

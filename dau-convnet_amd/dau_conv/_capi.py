@@ -29,6 +29,7 @@ FLAG_NO_DENSE_SPLIT = 1 << 10      # never (default: the radii that pay for the 
 FLAG_DENSE_SPLIT_OUTLIERS = 1 << 12   # opt-in: calls within +-4 with few units beyond +-3 run the radius-3 two-limb GEMM plus a sparse ring pass
 FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernels and arithmetic, parameters and their gradients float32
 FLAG_IO_NHWC = 1 << 13  # x, y, dy, dx are channels_last: [N][H][W][C] in memory; the NCHW plan of the same desc in everything but addresses
+FLAG_INPUT_RELU = 1 << 14   # a ReLU in front of the layer, fused: x is clamped at zero where the kernels load it, dx is masked by x in its store
 
 ALGO_AUTO, ALGO_DIRECT, ALGO_TILED = 0, 1, 2
 PASS_FORWARD, PASS_BACKWARD, PASS_EPILOGUE_BACKWARD = 1, 2, 3
@@ -181,6 +182,8 @@ class Plan(object):
         self.io_dtype = torch.bfloat16 if int(flags) & FLAG_IO_BF16 else torch.float16 if int(flags) & FLAG_IO_F16 else torch.float32
         # FLAG_IO_NHWC: activations of logical shape [N, C, H, W] with channels_last strides, in and out
         self._io_format = torch.channels_last if int(flags) & FLAG_IO_NHWC else torch.contiguous_format
+        # FLAG_INPUT_RELU: forward() and backward() take the RAW input and compute relu(input) -> DAU and its gradients
+        self.input_relu = bool(int(flags) & FLAG_INPUT_RELU)
         info = _Info()
         _check(lib.dau_conv_plan_get_info(self._h, ctypes.byref(info)))
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}

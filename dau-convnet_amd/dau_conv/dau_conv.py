@@ -69,9 +69,28 @@ def _wants_nhwc(x, settings):
     return True if cl is True else _NHWC_BY_DEFAULT.get(x.dtype, False)
 
 
+# (shape, dtype, attrs) whose FLAG_INPUT_RELU plan the library refused (shapes that fall back to the direct kernels): asked once
+_INPUT_RELU_REFUSED = set()
+
+
 def _get_plan(x, w, settings, nhwc=False):
     """The cached plan of this call.  nhwc: the FLAG_IO_NHWC plan if the library builds one for the shape, else the NCHW plan
-    (Plan.io_layout tells which came back)."""
+    (Plan.io_layout tells which came back).  settings["input_relu"]: the FLAG_INPUT_RELU plan where the library builds one, else
+    the plan without the flag (Plan.input_relu tells which came back; the caller then applies the ReLU itself)."""
+    if settings.get("input_relu") and not (x.dtype == torch.bfloat16 and settings["dense_bf16"]):   # (the flag excludes DAU_FLAG_DENSE_BF16)
+        asked = (tuple(x.shape), tuple(w.shape), x.dtype, x.device.index, settings["kernel_size"], settings["number_units_ignore"],
+                 settings["algo"], _capi.filter_support(settings["sigma_hint"]))
+        if asked not in _INPUT_RELU_REFUSED:
+            try:
+                return _get_plan_with(x, w, settings, nhwc, _capi.FLAG_INPUT_RELU)
+            except _capi.InvalidArgumentError as e:
+                if "DAU_FLAG_INPUT_RELU" not in str(e):
+                    raise
+                _INPUT_RELU_REFUSED.add(asked)   # no tiled kernels for this shape / algo
+    return _get_plan_with(x, w, settings, nhwc, 0)
+
+
+def _get_plan_with(x, w, settings, nhwc, extra_flags):
     N, S, H, W = x.shape
     _, S2, G, F = w.shape
     if S2 != S:
@@ -81,7 +100,7 @@ def _get_plan(x, w, settings, nhwc=False):
         raise _capi.InvalidArgumentError("last dim of weights (%d) must equal num_output (%d)" % (F, settings["num_output"]))
     if settings["stride"] != 1:
         raise _capi.InvalidArgumentError("DAUConv: only stride=1 is supported")  # base_dau_conv_layer.cpp:68-69
-    flags = 0
+    flags = extra_flags
     if settings["use_interpolation"]:
         flags |= _capi.FLAG_USE_INTERPOLATION
     if settings["unit_testing"]:
@@ -243,6 +262,7 @@ class _DAUConvFunction(torch.autograd.Function):
             y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu) \
                 if (bias is not None or relu) else plan.forward(input, weights, mu1, mu2, sigma)
         _check_after(plan, st["check_offsets"])
+        # (an input_relu plan: `input` is the raw tensor -- the ReLU's output is never materialised, nor saved)
         ctx.save_for_backward(*((input, weights, mu1, mu2, sigma) + ((y,) if relu else ())))
         ctx.plan, ctx.st, ctx.relu = plan, st, bool(relu)
         return y
@@ -323,7 +343,14 @@ def _epilogue_ok(plan):
     return ok
 
 
-def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residual=None, **attrs):
+def _input_relu_ok(input, weights, sigma, attrs):
+    """Does the plan of this call take the ReLU in front of it (FLAG_INPUT_RELU)?  Asked once per plan: _get_plan remembers a refusal.
+    -> (answer, the sigma hint the settings were made with: read from the device at most once per call)"""
+    st = dict(_settings(_f32(sigma), **attrs), input_relu=True)
+    return _get_plan(input, _f32(weights), st, _wants_nhwc(input, st)).input_relu, st["sigma_hint"]
+
+
+def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residual=None, input_activation=None, **attrs):
     """DAUConv op: output[n,f] = sum_{s,g} w * bilinear(blur_sigma(input[n,s]), . + (mu2, mu1)); differentiable.
     input (and so output) float32, bfloat16 or float16; the parameters are used as float32 whatever their floating dtype.
     bias ([F]) and activation (None or "relu"): output = act(output + bias[f]) fused into the kernels' store -- one fp32 add and a
@@ -334,16 +361,29 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
     input's dtype and the output's shape is added inside the store as well -- in fp32, before the one rounding; it is brought to the
     plan's layout (copied only if needed), only read, and its gradient is the tensor backward hands the DAU passes (no extra pass).
     Any other residual (another dtype, a shape that broadcasts, a plan without the fused epilogue) is added in torch, with torch's
-    promotion, after the op and its bias and before the activation."""
+    promotion, after the op and its bias and before the activation.
+    input_activation (None or "relu"): output = DAUConv(relu(input)) with the ReLU inside the op (conv -> BatchNorm -> ReLU -> DAU
+    stacks pass the BatchNorm output): the kernels clamp the input where they load it and mask the input gradient by it in its store,
+    so no ReLU pass runs forward or backward and autograd saves the raw input, not a ReLU output.  Bit for bit the results of
+    dau_conv(torch.relu(input), ...).  Plans that cannot take it (shapes on the direct kernels, dense_bf16) apply torch.relu first."""
     if activation not in (None, "relu"):
         raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
+    if input_activation not in (None, "relu"):
+        raise _capi.InvalidArgumentError("input_activation must be None or \"relu\"")
+    if input_activation == "relu":
+        ok, hint = _input_relu_ok(input, weights, sigma, attrs)
+        attrs = dict(attrs, sigma_hint=hint)
+        if not ok:
+            return dau_conv(torch.relu(input), weights, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual, **attrs)
     if residual is not None:
         out_shape = (input.shape[0], weights.shape[-1]) + tuple(input.shape[2:])
         if not (residual.dtype == input.dtype and tuple(residual.shape) == out_shape):
-            out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, **attrs) + residual
+            out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, input_activation=input_activation, **attrs) + residual
             return torch.relu(out) if activation == "relu" else out
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
+    if input_activation == "relu":
+        st["input_relu"] = True          # part of the plan key (_get_plan): the plan takes the raw input
     if bias is None and activation is None and residual is None:
         return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
@@ -352,7 +392,7 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
         args = (input, weights, mu1, mu2, sigma, st, None if bias is None else _f32(bias), activation == "relu")
         return _DAUConvFunction.apply(*(args if residual is None else args + (residual,)))
     if residual is not None:
-        out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, **attrs) + residual
+        out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, input_activation=input_activation, **attrs) + residual
         return torch.relu(out) if activation == "relu" else out
     out = _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     if bias is not None:
@@ -497,12 +537,12 @@ class _DAUConvolution2d(object):
         self.grad_reduce = grad_reduce
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
 
-    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None, residual=None):
+    def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None, residual=None, input_activation=None):
         # clip in the graph, so clipped units receive zero mu-gradient (dau_conv.py:190-191)
         m = self.mean_max_allowed_offset
         mu1 = torch.clamp(mu1, min=-m, max=m)
         mu2 = torch.clamp(mu2, min=-m, max=m)
-        return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual,
+        return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual, input_activation=input_activation,
                         num_output=self.num_output, number_units_x=self.dau_units[0], number_units_y=self.dau_units[1],
                         number_units_ignore=self.num_dau_units_ignore, kernel_size=self.max_kernel_size,
                         pad=int(self.padding), component_border_bound=self.dau_unit_border_bound,
@@ -554,6 +594,13 @@ class DAUConv2d(nn.Module):
     of the contiguous call.  False: today's path: the input is made contiguous, the output is contiguous.  None (default): the
     NHWC plan for the dtypes where it measured faster than converting (`dau_conv._NHWC_BY_DEFAULT`).  Layers with
     `dense_bf16=True` and shapes that run on the direct kernels have no NHWC plan and convert, whatever the argument.
+    `input_activation` (None): an activation applied to the INPUT, in front of the layer.  "relu", `torch.relu`,
+    `torch.nn.functional.relu` or an `nn.ReLU` is fused into the layer (DAU_FLAG_INPUT_RELU): in a `Conv2d -> BatchNorm2d -> ReLU ->
+    DAUConv2d` stack, drop the ReLU module and give the layer the BatchNorm output -- the kernels clamp x where they load it and mask
+    the input gradient by x in its store, so the ReLU's forward and backward passes and its saved output go away; the results are bit
+    for bit those of `layer(torch.relu(x))`.  Any other callable is applied in torch before the layer.  Works with channels_last,
+    autocast, `.half()` / `.bfloat16()`, `fused_epilogue`, `residual=`, `strides > 1` and `process_group=`; layers whose plan cannot
+    take the flag (`dense_bf16=True`, shapes on the direct kernels) run `torch.relu` in front.
     `process_group` (a torch.distributed group, or True for the default one): batch-sharded data parallelism INSIDE the
     layer's backward -- the raw parameter-gradient sums of the local shard are all-reduced (one flat [4,S,G,F] buffer, RCCL
     over xGMI with backend "nccl") while the input gradient is computed, and the elementwise tail runs on the reduced sums;
@@ -574,7 +621,7 @@ class DAUConv2d(nn.Module):
                  dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False, dau_sigma_trainable=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, in_channels=None, check_offsets="async",
                  algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None,
-                 dense_outliers=False, channels_last=None, fused_epilogue=False, **kwargs):
+                 dense_outliers=False, channels_last=None, fused_epilogue=False, input_activation=None, **kwargs):
         super(DAUConv2d, self).__init__()
         self.rank = 2
         self.filters = int(filters)
@@ -628,6 +675,12 @@ class DAUConv2d(nn.Module):
         self.dense_outliers = dense_outliers
         self.channels_last = channels_last
         self.fused_epilogue = bool(fused_epilogue)
+        if not (input_activation is None or input_activation == "relu" or callable(input_activation)):
+            raise ValueError("input_activation must be None, \"relu\" or a callable")
+        self.input_activation = input_activation
+        # a ReLU is fused into the op; any other callable runs in torch in front of it
+        self._input_relu = (isinstance(input_activation, str) and input_activation == "relu") or \
+            input_activation in (torch.relu, nn.functional.relu) or isinstance(input_activation, nn.ReLU)
         self.process_group = process_group
         self.grad_reduce = grad_reduce
         # odd number of units: add one dummy (zero weight, ignored) unit (dau_conv.py:317-329)
@@ -752,24 +805,30 @@ class DAUConv2d(nn.Module):
         if inputs.dim() != self.rank + 2:
             raise ValueError('DAU convolution not supported for input with rank %d' % inputs.dim())
         sigma_t, hint = self._sigma_tensor_and_hint()
+        if self.input_activation is not None and not self._input_relu:
+            inputs = self.input_activation(inputs)
+        in_act = "relu" if self._input_relu else None
         if self.fused_epilogue:
             # bias and ReLU inside the op's store; both commute with the slicing that emulates strides > 1
             relu = self.activation in (torch.relu, nn.functional.relu) or isinstance(self.activation, nn.ReLU)
             bias = self._parameters["bias"] if self.use_bias else None
             if residual is not None and self.strides > 1:
                 # the residual has the SAMPLED shape: the bias stays in the store, the add and the activation follow the slice
-                outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint, bias=bias)
+                outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint, bias=bias,
+                                                   input_activation=in_act)
                 outputs = outputs[:, :, ::self.strides, ::self.strides] + residual
                 return self.activation(outputs) if self.activation is not None else outputs
             # (a residual joins them in the store: act((sum + bias) + residual); one the op cannot fuse it adds in torch)
             outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
-                                               bias=bias, activation="relu" if relu else None, residual=residual)
+                                               bias=bias, activation="relu" if relu else None, residual=residual,
+                                               input_activation=in_act)
             if self.strides > 1:
                 outputs = outputs[:, :, ::self.strides, ::self.strides]
             if self.activation is not None and not relu:
                 return self.activation(outputs)
             return outputs
-        outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint)
+        outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
+                                           input_activation=in_act)
         # strides > 1 are emulated by sampling the stride-1 output (dau_conv.py:497-498)
         if self.strides > 1:
             outputs = outputs[:, :, ::self.strides, ::self.strides]
@@ -854,7 +913,7 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                sigma_initializer=None, sigma_regularizer=None, sigma_constraint=None, biases_initializer=zeros_initializer(),
                biases_regularizer=None, biases_constraint=None, dau_unit_border_bound=0.01, dau_sigma_trainable=False,
                dau_mu_interpolation=True, reuse=None, variables_collections=None, outputs_collections=None,
-               trainable=True, scope=None, dense_outliers=False, fused_epilogue=False):
+               trainable=True, scope=None, dense_outliers=False, fused_epilogue=False, input_activation_fn=None):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -874,7 +933,7 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
         mu2_constraint=mu2_constraint, sigma_constraint=sigma_constraint, bias_constraint=biases_constraint,
         dau_unit_border_bound=dau_unit_border_bound, dau_sigma_trainable=dau_sigma_trainable,
         dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
-        dense_outliers=dense_outliers))
+        dense_outliers=dense_outliers, input_activation=input_activation_fn))
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))
@@ -892,7 +951,7 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                biases_initializer=zeros_initializer(), biases_regularizer=None, dau_unit_border_bound=0.01,
                dau_sigma_trainable=False, dau_aggregation_forbid_positive_dim1=False, dau_mu_interpolation=True,
                reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
-               dense_outliers=False, fused_epilogue=False):
+               dense_outliers=False, fused_epilogue=False, input_activation_fn=None):
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -910,7 +969,7 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
         dau_sigma_trainable=dau_sigma_trainable,
         dau_aggregation_forbid_positive_dim1=dau_aggregation_forbid_positive_dim1,
         dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
-        dense_outliers=dense_outliers))
+        dense_outliers=dense_outliers, input_activation=input_activation_fn))
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))

@@ -191,6 +191,26 @@ enum {
                                                back to the direct kernels).  Alignment: none beyond that of an element -- the 16-byte
                                                load and store paths check the base address and the channel count at run time and
                                                fall back to element-wise access.                                              */
+    DAU_FLAG_INPUT_RELU = 1 << 14,          /* a ReLU in front of the layer, fused into it (conv -> BatchNorm -> ReLU -> DAU: the caller passes
+                                               the BatchNorm output as x, no ReLU pass runs and its output is never materialised).
+                                               dau_conv_forward (and _epilogue / _residual), every parameter-gradient pass and
+                                               dau_conv_backward_param_sums compute exactly -- bit for bit -- what the plan without the flag
+                                               computes on x' = (x <= 0) ? +0 : x: a NaN stays a NaN, -0 becomes +0, 16-bit formats are
+                                               widened first; the clamp sits where the staging kernels widen the x they load (the per-image
+                                               scales of the two-limb members are those of x').  The dx pass of dau_conv_backward stores
+                                               dx = (x <= 0) ? 0 : s, s the value the plan without the flag would store -- the rule of a
+                                               threshold at zero: a NaN x passes s through -- applied after the sum, before the store's one
+                                               rounding, in the last window of a pass of several offset windows: mask(old + v).  x is the
+                                               pointer dau_conv_backward receives anyway (dx's shape, format and layout; under batch slabs
+                                               indexed by the global image) and must be non-NULL with DAU_NEED_DX alone too; where the
+                                               channel count is a multiple of four the NHWC stores load it four channels at once if x's
+                                               OWN base allows (16 bytes float32, 8 bytes 16-bit), element-wise otherwise -- same bits.
+                                               The plan is the plan of the same desc without the flag (members, buckets, windows, slabs,
+                                               dau_conv_plan_info, dau_conv_workspace_bytes); images stay independent.  Combines with
+                                               DAU_FLAG_IO_BF16 / _IO_F16 / _IO_NHWC, the split flags, DAU_FLAG_DENSE_SPLIT_OUTLIERS,
+                                               DAU_FLAG_STATIC_BUCKET and the fused output epilogue and residual of the same call;
+                                               excludes DAU_FLAG_DENSE_BF16; needs the tiled kernels (not DAU_ALGO_DIRECT, nor a shape
+                                               that falls back to the direct kernels).                                          */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
