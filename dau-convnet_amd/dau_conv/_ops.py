@@ -1,0 +1,327 @@
+"""The DAU operator as two opaque PyTorch ops, `dau_conv::conv` and `dau_conv::conv_backward` (torch.library.custom_op), so that a
+layer can sit inside `torch.compile`: Dynamo sees one op with a shape function, and everything that depends on the plan -- the plan
+cache, the library's refusals and the fallbacks they select, the offset status, the host copy of sigma -- happens at run time inside
+the op's implementation, where the tensors are real.  The eager layer does not come through here (dau_conv.py: _DAUConvFunction).
+
+    conv(x, w, mu1, mu2, sigma, bias?, residual?, relu, input_relu, ...settings...) -> y
+        y = act((DAU(relu?(x)) + bias[f]) + residual): what dau_conv() computes for these arguments.  w, mu1, mu2 [1,S,G,F]; sigma
+        [1,S,G,F], or one element that the op tiles; the parameters and the bias of any floating dtype (used as float32).
+        residual, when given, has y's shape and x's dtype (dau_conv() adds any other residual in torch, outside the op).
+    conv_backward(grad, x, w, mu1, mu2, sigma, y?, relu, input_relu, need_mask, need_dbias, ...settings...)
+        -> (dx, dw, dmu1, dmu2, dsigma, dbias): need_mask holds the _capi.NEED_* bits; a gradient that is not asked for comes back as
+        a 0-element tensor.  x is the raw input (of an input_relu call too), y the forward's output, needed with relu only.
+    settings: number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1,
+        use_interpolation, algo, dense_bf16, dense_split (-1: the library's choice, 0: never, 1: always), dense_outliers,
+        channels_last (-1: by dtype, 0, 1) and check_offsets ("async", "on", "off") -- what _settings() normalises, as schema types.
+
+What the shape functions promise, from dtypes, strides and arguments alone:
+    y       [N, F, H, W] in x's dtype; channels_last exactly when _wants_nhwc(x, settings) holds, contiguous otherwise
+    dx      like x, in the format of y's rule
+    dw, dmu1, dmu2, dsigma   [1, S, G, F] float32;  dbias  [F] float32
+Two of today's eager rules depend on the plan, and the implementations bring their results to the promise instead:
+  * a plan without the fused epilogue (shapes on the direct kernels, dense_bf16) adds the bias in torch, where eager lets torch promote
+    -- a bfloat16 output plus a float32 bias is float32 in eager.  Here the sum is rounded to x's dtype, the fused epilogue's rule.
+    Where the bias has x's dtype (after .half() / .bfloat16()) or x is float32 the two agree bit for bit;
+  * a channels_last input whose NHWC plan the library refuses (the direct-kernel shapes) gives a contiguous output in eager.  Here
+    the output and the input gradient are converted to channels_last."""
+import collections
+import weakref
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import _capi
+from . import dau_conv as _impl
+
+_TRI = {None: -1, False: 0, True: 1}
+_UNTRI = {-1: None, 0: False, 1: True}
+_CHECK = {"async": "async", True: "on", False: "off"}
+_UNCHECK = {"async": "async", "on": True, "off": False}
+
+
+def encode_settings(st):
+    """The op's trailing arguments from a _settings() dict, in schema order."""
+    return (st["number_units_ignore"], st["kernel_size"], st["unit_testing"], st["mu_learning_rate_factor"], st["single_dim_kernel"],
+            st["forbid_positive_dim1"], st["use_interpolation"], st["algo"], st["dense_bf16"], _TRI[st["dense_split"]],
+            st["dense_outliers"], _TRI[st["channels_last"]], _CHECK[st["check_offsets"]])
+
+
+def _layout_settings(dense_bf16, channels_last):
+    """All of the settings that _wants_nhwc reads."""
+    if channels_last not in _UNTRI:
+        raise _capi.InvalidArgumentError("channels_last must be -1 (by dtype), 0 or 1")
+    return dict(dense_bf16=bool(dense_bf16), channels_last=_UNTRI[channels_last])
+
+
+# ----------------------------------------------------------------------------------------------
+# the host copy of sigma that sizes the prefilter support and keys the plan
+# ----------------------------------------------------------------------------------------------
+# Per sigma tensor, as DAUConv2d._sigma_tensor_and_hint keeps it for the eager layer: re-read when the tensor has been written since
+# (its version counter) or is another tensor (the object itself, held weakly, and its address), so a fixed sigma costs one read in
+# all and a trainable one a read per optimizer step -- outside the graph either way.  Bounded, least recently used.
+_SIGMA_HOST = collections.OrderedDict()
+_SIGMA_HOST_MAX = 256
+
+
+def _read_sigma(sigma):
+    return float(sigma.detach().reshape(-1)[0].item())
+
+
+def _sigma_hint(sigma):
+    if sigma.numel() != 1:
+        return _read_sigma(sigma)            # a full sigma tensor: the read _settings() performs on every eager call
+    key = (sigma.data_ptr(), sigma.device.index)
+    hit = _SIGMA_HOST.get(key)
+    if hit is not None and hit[0]() is sigma and hit[1] == sigma._version:
+        _SIGMA_HOST.move_to_end(key)
+        return hit[2]
+    value = _read_sigma(sigma)
+    _SIGMA_HOST[key] = (weakref.ref(sigma), sigma._version, value)
+    _SIGMA_HOST.move_to_end(key)
+    while len(_SIGMA_HOST) > _SIGMA_HOST_MAX:
+        _SIGMA_HOST.popitem(last=False)
+    return value
+
+
+def _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
+                  forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last, check_offsets):
+    """The _settings() dict of a real call."""
+    if dense_split not in _UNTRI or check_offsets not in _UNCHECK:
+        raise _capi.InvalidArgumentError("dense_split must be -1, 0 or 1 and check_offsets \"async\", \"on\" or \"off\"")
+    st = _impl._settings(sigma, number_units_ignore=number_units_ignore, num_output=w.shape[-1], kernel_size=kernel_size,
+                         unit_testing=unit_testing, mu_learning_rate_factor=mu_learning_rate_factor, single_dim_kernel=single_dim_kernel,
+                         forbid_positive_dim1=forbid_positive_dim1, use_interpolation=use_interpolation, sigma_hint=_sigma_hint(sigma),
+                         check_offsets=_UNCHECK[check_offsets], algo=algo, dense_split=_UNTRI[dense_split],
+                         dense_outliers=dense_outliers, **_layout_settings(dense_bf16, channels_last))
+    if input_relu:
+        st["input_relu"] = True
+    return st
+
+
+def _tiled(sigma, w):
+    """sigma as the kernels take it: contiguous float32 [1,S,G,F]; one element is tiled."""
+    sigma = _impl._f32(sigma)
+    if sigma.numel() == 1 and w.numel() != 1:
+        sigma = sigma.reshape(1, 1, 1, 1).expand(w.shape)
+    return _impl._c(sigma)
+
+
+def _promised(t, nhwc, dtype):
+    """t in the dtype and with the strides the shape function gave: those of torch.empty in that memory format."""
+    if t.dtype != dtype:
+        t = t.to(dtype)
+    n, c, h, w = t.shape
+    if tuple(t.stride()) == ((h * w * c, 1, w * c, c) if nhwc else (c * h * w, h * w, w, 1)):
+        return t
+    return _empty_act(t, tuple(t.shape), nhwc).copy_(t)
+
+
+def _empty_act(like, shape, nhwc):
+    return torch.empty(shape, dtype=like.dtype, device=like.device,
+                       memory_format=torch.channels_last if nhwc else torch.contiguous_format)
+
+
+def _check_shapes(x, w, residual=None):
+    if x.dim() != 4 or w.dim() != 4:
+        raise _capi.InvalidArgumentError("dau_conv: the input must be [N,S,H,W] and the parameters [1,S,G,F]")
+    if residual is not None and not (residual.dtype == x.dtype and residual.dim() == 4):
+        raise _capi.InvalidArgumentError("dau_conv::conv: the residual must have the input's dtype and the output's shape")
+
+
+# ----------------------------------------------------------------------------------------------
+# dau_conv::conv
+# ----------------------------------------------------------------------------------------------
+@torch.library.custom_op("dau_conv::conv", mutates_args=())
+def conv(x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, bias: Optional[Tensor], residual: Optional[Tensor],
+         relu: bool, input_relu: bool, number_units_ignore: int, kernel_size: int, unit_testing: bool,
+         mu_learning_rate_factor: float, single_dim_kernel: bool, forbid_positive_dim1: bool, use_interpolation: bool, algo: int,
+         dense_bf16: bool, dense_split: int, dense_outliers: bool, channels_last: int, check_offsets: str) -> Tensor:
+    _check_shapes(x, w, residual)
+    st = _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
+                       forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last,
+                       check_offsets)
+    nhwc = _impl._wants_nhwc(x, st)
+    w, mu1, mu2 = (_impl._c(_impl._f32(t)) for t in (w, mu1, mu2))
+    sigma = _tiled(sigma, w)
+    if bias is not None and tuple(bias.shape) != (w.shape[-1],):
+        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), w.shape[-1]))
+    if residual is not None and tuple(residual.shape) != (x.shape[0], w.shape[-1]) + tuple(x.shape[2:]):
+        raise _capi.InvalidArgumentError("dau_conv::conv: the residual must have the input's dtype and the output's shape")
+    plan = _impl._get_plan(x, w, st, nhwc)
+    if input_relu and not plan.input_relu:
+        x = torch.relu(x)                    # the plan cannot take the flag (direct kernels, dense_bf16): the ReLU in front
+    xin = _impl._act(x, plan)
+    _impl._check_before(plan, st["check_offsets"])
+    epilogue = bias is not None or relu or residual is not None
+    if not epilogue:
+        y = plan.forward(xin, w, mu1, mu2, sigma)
+    elif _impl._epilogue_ok(plan):
+        fbias = None if bias is None else _impl._c(_impl._f32(bias))
+        if residual is not None:
+            y = plan.forward(xin, w, mu1, mu2, sigma, bias=fbias, relu=relu, residual=_impl._act(residual, plan))
+        else:
+            y = plan.forward(xin, w, mu1, mu2, sigma, bias=fbias, relu=relu)
+    else:
+        # no fused epilogue: the op, then `+ bias`, `+ residual` and relu in torch, in dau_conv()'s order
+        y = plan.forward(xin, w, mu1, mu2, sigma)
+        if bias is not None:
+            y = y + bias.reshape(1, -1, 1, 1)
+        if residual is not None:
+            y = y + residual
+        if relu:
+            y = torch.relu(y)
+    _impl._check_after(plan, st["check_offsets"])
+    return _promised(y, nhwc, x.dtype)
+
+
+@conv.register_fake
+def _conv_fake(x, w, mu1, mu2, sigma, bias, residual, relu, input_relu, number_units_ignore, kernel_size, unit_testing,
+               mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split,
+               dense_outliers, channels_last, check_offsets):
+    _check_shapes(x, w, residual)
+    nhwc = _impl._wants_nhwc(x, _layout_settings(dense_bf16, channels_last))
+    return _empty_act(x, (x.shape[0], w.shape[-1], x.shape[2], x.shape[3]), nhwc)
+
+
+# ----------------------------------------------------------------------------------------------
+# dau_conv::conv_backward
+# ----------------------------------------------------------------------------------------------
+@torch.library.custom_op("dau_conv::conv_backward", mutates_args=())
+def conv_backward(grad: Tensor, x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, y: Optional[Tensor], relu: bool,
+                  input_relu: bool, need_mask: int, need_dbias: bool, number_units_ignore: int, kernel_size: int, unit_testing: bool,
+                  mu_learning_rate_factor: float, single_dim_kernel: bool, forbid_positive_dim1: bool, use_interpolation: bool,
+                  algo: int, dense_bf16: bool, dense_split: int, dense_outliers: bool, channels_last: int,
+                  check_offsets: str) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    _check_shapes(x, w)
+    if relu and y is None:
+        raise _capi.InvalidArgumentError("dau_conv::conv_backward: relu needs the forward's output")
+    st = _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
+                       forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last,
+                       check_offsets)
+    nhwc = _impl._wants_nhwc(x, st)
+    w, mu1, mu2 = (_impl._c(_impl._f32(t)) for t in (w, mu1, mu2))
+    sigma = _tiled(sigma, w)
+    plan = _impl._get_plan(x, w, st, nhwc)
+    relu_in_front = input_relu and not plan.input_relu
+    if relu_in_front:
+        x = torch.relu(x)
+    xin = _impl._act(x, plan)
+    none = lambda like, dtype=torch.float32: torch.empty((0,), dtype=dtype, device=like.device)
+    need = int(need_mask) & _capi.NEED_ALL
+    if need == 0 and not need_dbias:
+        return (none(x, x.dtype),) + (none(x),) * 5
+    _impl._check_before(plan, st["check_offsets"])
+    grad = _impl._act(grad if grad.dtype == x.dtype else grad.to(x.dtype), plan)
+    dbias = None
+    if need_dbias or (relu and need):
+        if _impl._epilogue_ok(plan):
+            # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient
+            dz, dbias = plan.epilogue_backward(grad, _impl._act(y, plan) if relu else None, relu=relu, need_dbias=need_dbias)
+            if dz is not None:
+                grad = dz
+        else:
+            if relu:
+                grad = torch.where(_impl._act(y, plan) <= 0, torch.zeros((), dtype=grad.dtype, device=grad.device), grad)
+            if need_dbias:
+                dbias = grad.sum_to_size(1, grad.shape[1], 1, 1).reshape(-1).float()
+    out = (None,) * 5
+    if need:
+        out = plan.backward(xin, grad, w, mu1, mu2, sigma, need)
+        _impl._check_after(plan, st["check_offsets"])
+    dx = out[0]
+    if dx is not None:
+        if relu_in_front:
+            dx = torch.where(x <= 0, torch.zeros((), dtype=dx.dtype, device=dx.device), dx)
+        dx = _promised(dx, nhwc, x.dtype)
+    return (none(x, x.dtype) if dx is None else dx,) + tuple(none(x) if t is None else t for t in out[1:]) + \
+        (none(x) if dbias is None else dbias,)
+
+
+@conv_backward.register_fake
+def _conv_backward_fake(grad, x, w, mu1, mu2, sigma, y, relu, input_relu, need_mask, need_dbias, number_units_ignore, kernel_size,
+                        unit_testing, mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1, use_interpolation, algo,
+                        dense_bf16, dense_split, dense_outliers, channels_last, check_offsets):
+    _check_shapes(x, w)
+    nhwc = _impl._wants_nhwc(x, _layout_settings(dense_bf16, channels_last))
+    f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    need = int(need_mask) & _capi.NEED_ALL
+    pshape = (1, w.shape[1], w.shape[2], w.shape[3])
+    dx = _empty_act(x, tuple(x.shape), nhwc) if need & _capi.NEED_DX else torch.empty((0,), dtype=x.dtype, device=x.device)
+    params = tuple(f32(pshape) if need & bit else f32((0,))
+                   for bit in (_capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA))
+    return (dx,) + params + (f32((w.shape[-1],)) if need_dbias else f32((0,)),)
+
+
+# ----------------------------------------------------------------------------------------------
+# autograd of dau_conv::conv
+# ----------------------------------------------------------------------------------------------
+_N_ARGS = 22            # x, w, mu1, mu2, sigma, bias, residual, relu, input_relu and the thirteen settings
+
+
+def _setup_context(ctx, inputs, output):
+    x, w, mu1, mu2, sigma, bias, residual, relu, input_relu = inputs[:9]
+    # the raw input (an input_relu call's ReLU output is never materialised, nor saved) and y only for the ReLU mask
+    ctx.save_for_backward(*((x, w, mu1, mu2, sigma) + ((output,) if relu else ())))
+    ctx.relu, ctx.input_relu, ctx.settings = bool(relu), bool(input_relu), tuple(inputs[9:])
+    need = 0
+    for i, bit in enumerate((_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
+        if ctx.needs_input_grad[i]:
+            need |= bit
+    ctx.need = need
+    ctx.need_dbias = bias is not None and bool(ctx.needs_input_grad[5])
+    ctx.need_dres = residual is not None and bool(ctx.needs_input_grad[6])
+    ctx.param_dtypes = tuple(t.dtype for t in (w, mu1, mu2, sigma))
+    ctx.bias_dtype = None if bias is None else bias.dtype
+    ctx.sigma_shape = tuple(sigma.shape)
+
+
+def _backward(ctx, grad):
+    x, w, mu1, mu2, sigma = ctx.saved_tensors[:5]
+    y = ctx.saved_tensors[5] if ctx.relu else None
+    grads = [None] * _N_ARGS
+    if ctx.need == 0 and not ctx.need_dbias and not ctx.need_dres:
+        return tuple(grads)
+    if ctx.need_dres:
+        # the residual joins the sum before the activation: its gradient IS the gradient of the sum -- grad itself, or with a ReLU
+        # the masked grad (the select the op's epilogue pass computes: no arithmetic, the same bits)
+        grads[6] = grad if not ctx.relu else torch.where(y <= 0, torch.zeros((), dtype=grad.dtype, device=grad.device), grad)
+    if ctx.need or ctx.need_dbias:
+        out = torch.ops.dau_conv.conv_backward(grad, x, w, mu1, mu2, sigma, y, ctx.relu, ctx.input_relu, ctx.need, ctx.need_dbias,
+                                               *ctx.settings)
+        if ctx.need & _capi.NEED_DX:
+            grads[0] = out[0]
+        for i, bit in enumerate((_capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
+            if ctx.need & bit:
+                g = out[1 + i]
+                if i == 3 and tuple(g.shape) != ctx.sigma_shape:
+                    g = g.sum_to_size(1, 1, 1, 1).reshape(ctx.sigma_shape)       # a tiled scalar: the sum over its copies
+                grads[1 + i] = g if g.dtype == ctx.param_dtypes[i] else g.to(ctx.param_dtypes[i])
+        if ctx.need_dbias:
+            grads[5] = out[5] if out[5].dtype == ctx.bias_dtype else out[5].to(ctx.bias_dtype)
+    return tuple(grads)
+
+
+conv.register_autograd(_backward, setup_context=_setup_context)
+
+
+# ----------------------------------------------------------------------------------------------
+# process_group= layers under torch.compile
+# ----------------------------------------------------------------------------------------------
+_PROCESS_GROUP_EAGER = []
+
+
+def process_group_eager():
+    """-> call(fn, *args, **kwargs) that runs fn (today's dau_conv(), or a layer's forward) outside the graph: the overlapped
+    all-reduce of a process_group= layer's backward is not an op.  One graph break per call; fullgraph=True refuses it, naming
+    process_group.  Built on first use (a layer with process_group=
+    builds it at construction): torch._dynamo is not imported with the package."""
+    if not _PROCESS_GROUP_EAGER:
+        import torch._dynamo
+
+        def dau_conv_process_group_eager(fn, *args, **kwargs):
+            return fn(*args, **kwargs)
+
+        _PROCESS_GROUP_EAGER.append(torch._dynamo.disable(
+            dau_conv_process_group_eager, reason="DAUConv with process_group= runs its overlapped all-reduce backward in eager"))
+    return _PROCESS_GROUP_EAGER[0]

@@ -365,7 +365,11 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
     input_activation (None or "relu"): output = DAUConv(relu(input)) with the ReLU inside the op (conv -> BatchNorm -> ReLU -> DAU
     stacks pass the BatchNorm output): the kernels clamp the input where they load it and mask the input gradient by it in its store,
     so no ReLU pass runs forward or backward and autograd saves the raw input, not a ReLU output.  Bit for bit the results of
-    dau_conv(torch.relu(input), ...).  Plans that cannot take it (shapes on the direct kernels, dense_bf16) apply torch.relu first."""
+    dau_conv(torch.relu(input), ...).  Plans that cannot take it (shapes on the direct kernels, dense_bf16) apply torch.relu first.
+    Under torch.compile (torch.compiler.is_compiling()) the call becomes the one opaque op torch.ops.dau_conv.conv (_ops.py), which
+    makes these decisions at run time and reads sigma itself (a sigma_hint= is ignored there); process_group= calls leave the graph."""
+    if torch.compiler.is_compiling():
+        return _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, activation, residual, input_activation, attrs)
     if activation not in (None, "relu"):
         raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
     if input_activation not in (None, "relu"):
@@ -398,6 +402,34 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
     if bias is not None:
         out = out + bias.reshape(1, -1, 1, 1)
     return torch.relu(out) if activation == "relu" else out
+
+
+def _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, activation, residual, input_activation, attrs):
+    """dau_conv() while Dynamo traces: everything decidable from arguments, dtypes and shapes here, the rest inside the op."""
+    if attrs.get("process_group") is not None:
+        # the overlapped all-reduce of _data_parallel_backward is not an op: today's function, outside the graph (one graph break)
+        return _ops.process_group_eager()(dau_conv, input, weights, mu1, mu2, sigma, bias=bias, activation=activation,
+                                          residual=residual, input_activation=input_activation, **attrs)
+    if activation not in (None, "relu"):
+        raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
+    if input_activation not in (None, "relu"):
+        raise _capi.InvalidArgumentError("input_activation must be None or \"relu\"")
+    if residual is not None:
+        out_shape = (input.shape[0], weights.shape[-1]) + tuple(input.shape[2:])
+        if not (residual.dtype == input.dtype and tuple(residual.shape) == out_shape):
+            out = _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, None, None, input_activation, attrs) + residual
+            return torch.relu(out) if activation == "relu" else out
+    st = _settings(sigma, **dict(attrs, sigma_hint=0.0))     # (a placeholder: sigma is not read while tracing)
+    if weights.shape[1] != input.shape[1]:
+        raise _capi.InvalidArgumentError("weights dim 1 (%d) must equal the input channels (%d)" % (weights.shape[1], input.shape[1]))
+    if weights.shape[-1] != st["num_output"]:
+        raise _capi.InvalidArgumentError("last dim of weights (%d) must equal num_output (%d)" % (weights.shape[-1], st["num_output"]))
+    if st["stride"] != 1:
+        raise _capi.InvalidArgumentError("DAUConv: only stride=1 is supported")
+    if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
+        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), weights.shape[-1]))
+    return torch.ops.dau_conv.conv(input, weights, mu1, mu2, sigma, bias, residual, activation == "relu", input_activation == "relu",
+                                   *_ops.encode_settings(st))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -516,6 +548,7 @@ class _DAUConvolution2d(object):
             raise ValueError("Only strides=1 supported.")
         self.num_output = num_output
         self.padding = padding
+        self._pad = int(padding)         # (a Python int: a numpy scalar read while Dynamo traces would put an .item() into the graph)
         self.name = name
         self.dau_units = dau_units
         self.num_dau_units_ignore = num_dau_units_ignore
@@ -535,6 +568,8 @@ class _DAUConvolution2d(object):
         self.channels_last = channels_last
         self.process_group = process_group
         self.grad_reduce = grad_reduce
+        if process_group is not None:
+            _ops.process_group_eager()       # built here, not while Dynamo traces the first call
         self.mean_max_allowed_offset = float(np.floor(self.max_kernel_size / 2.0) - self.dau_unit_border_bound)
 
     def __call__(self, inp, w, mu1, mu2, sigma, sigma_hint=None, bias=None, activation=None, residual=None, input_activation=None):
@@ -545,7 +580,7 @@ class _DAUConvolution2d(object):
         return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual, input_activation=input_activation,
                         num_output=self.num_output, number_units_x=self.dau_units[0], number_units_y=self.dau_units[1],
                         number_units_ignore=self.num_dau_units_ignore, kernel_size=self.max_kernel_size,
-                        pad=int(self.padding), component_border_bound=self.dau_unit_border_bound,
+                        pad=self._pad, component_border_bound=self.dau_unit_border_bound,
                         sigma_lower_bound=self.dau_unit_sigma_bound, mu_learning_rate_factor=self.mu_learning_rate_factor,
                         single_dim_kernel=self.dau_unit_single_dim,
                         forbid_positive_dim1=self.dau_aggregation_forbid_positive_dim1,
@@ -607,6 +642,10 @@ class DAUConv2d(nn.Module):
     weights / mu1 / mu2 / sigma gradients come out identical on every rank, averaged over the ranks (`grad_reduce="mean"`,
     the DistributedDataParallel convention) or summed (`"sum"`).  The bias gradient is ordinary autograd and is not exchanged
     here.  Wrapping such a layer in DistributedDataParallel as well is harmless but redundant (it averages identical values).
+    torch.compile: a built layer (`in_channels=` given, or called once) traces into one opaque op, `torch.ops.dau_conv.conv`, with
+    the offset clamp, the stride slice and an unfused bias / activation as ordinary traced ops around it; every combination above
+    goes through that op, and a trainable sigma does not recompile.  A `process_group=` layer runs outside the graph (one graph
+    break; `fullgraph=True` refuses it).  INTEGRATION.md, "torch.compile", has the details.
     """
 
     # the reference kernels process units in pairs; odd unit counts get one zero-weight ignored unit
@@ -785,6 +824,10 @@ class DAUConv2d(nn.Module):
 
     def _sigma_tensor_and_hint(self):
         s = self.dau_sigma
+        if torch.compiler.is_compiling():
+            # the op takes sigma as it is: it tiles a scalar and keeps the host copy itself (_ops._sigma_hint), at run time -- a
+            # trainable sigma neither recompiles the graph nor puts an .item() into it
+            return s, None
         if s.numel() == 1:
             # tile the scalar to the parameter shape, as the reference graph does (dau_conv.py:429-430)
             # the host copy sizes the prefilter support (2*ceil(5*sigma)+1, base_dau_conv_layer.cpp:146) and keys the plan; it
@@ -804,6 +847,8 @@ class DAUConv2d(nn.Module):
             self.to(inputs.device)
         if inputs.dim() != self.rank + 2:
             raise ValueError('DAU convolution not supported for input with rank %d' % inputs.dim())
+        if self.process_group is not None and torch.compiler.is_compiling():
+            return _ops.process_group_eager()(DAUConv2d.forward, self, inputs, residual)      # one graph break (see _ops.py)
         sigma_t, hint = self._sigma_tensor_and_hint()
         if self.input_activation is not None and not self._input_relu:
             inputs = self.input_activation(inputs)
@@ -914,6 +959,8 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                biases_regularizer=None, biases_constraint=None, dau_unit_border_bound=0.01, dau_sigma_trainable=False,
                dau_mu_interpolation=True, reuse=None, variables_collections=None, outputs_collections=None,
                trainable=True, scope=None, dense_outliers=False, fused_epilogue=False, input_activation_fn=None):
+    """slim-style functional form of DAUConv2d.  Its variables live in a Python-side scope registry (_SCOPES), which Dynamo does not
+    trace: dau_conv2d / dau_conv1d stay eager -- under torch.compile, build the model from the DAUConv2d / DAUConv1d modules."""
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -952,6 +999,8 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                dau_sigma_trainable=False, dau_aggregation_forbid_positive_dim1=False, dau_mu_interpolation=True,
                reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
                dense_outliers=False, fused_epilogue=False, input_activation_fn=None):
+    """slim-style functional form of DAUConv1d; like dau_conv2d it keeps its variables in the Python-side scope registry and stays
+    eager under torch.compile."""
     if data_format not in [None, 'NCHW']:
         raise ValueError('Invalid data_format: %r' % (data_format,))
     if inputs.dim() != 4:
@@ -978,3 +1027,7 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
     if outputs_collections is not None:
         outputs_collections.append(outputs)
     return outputs
+
+
+# the opaque ops of the torch.compile path; imported last: _ops.py uses this module's helpers
+from . import _ops  # noqa: E402

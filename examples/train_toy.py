@@ -3,7 +3,10 @@ reference's constructor arguments) inside an ordinary PyTorch training loop.  Of
 operator's own gradients; `mu_learning_rate_factor` scales them inside the op as in the reference
 (plugins/tensorflow/src/dau_conv_grad_op.cpp:297-303).
 
-    python examples/train_toy.py [--steps 60]
+    python examples/train_toy.py [--steps 60] [--compile [--backend inductor]]
+
+--compile wraps the student in torch.compile: each DAU layer becomes one opaque op (torch.ops.dau_conv.conv) of a single graph, runs
+the same kernels on the same bits, and the losses printed are those of the eager run.
 """
 import argparse
 import os
@@ -16,7 +19,7 @@ import torch
 import dau_conv
 
 
-def run(steps=60, seed=0, verbose=True):
+def run(steps=60, seed=0, verbose=True, compile=False, backend="inductor"):
     torch.manual_seed(seed)
     dev = torch.device("cuda", 0)
     teacher = dau_conv.DAUConv2d(filters=16, dau_units=(2, 2), max_kernel_size=9, use_bias=False, in_channels=8,
@@ -31,10 +34,11 @@ def run(steps=60, seed=0, verbose=True):
                            mu_learning_rate_factor=10, fused_epilogue=True),
     ).to(dev)
     opt = torch.optim.Adam(student.parameters(), lr=3e-3)
+    model = torch.compile(student, backend=backend) if compile else student
     losses = []
     for step in range(steps):
         x = torch.rand(16, 8, 32, 32, device=dev)
-        loss = torch.nn.functional.mse_loss(student(x), teacher(x))
+        loss = torch.nn.functional.mse_loss(model(x), teacher(x))
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -47,5 +51,8 @@ def run(steps=60, seed=0, verbose=True):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
-    l = run(ap.parse_args().steps)
+    ap.add_argument("--compile", action="store_true", help="wrap the student in torch.compile")
+    ap.add_argument("--backend", default="inductor", help="torch.compile backend (aot_eager needs no code generation)")
+    args = ap.parse_args()
+    l = run(args.steps, compile=args.compile, backend=args.backend)
     print("loss %.5f -> %.5f" % (l[0], l[-1]))
