@@ -212,6 +212,11 @@ struct Status {
     // ("outlier units", counted by prepare_units_kernel), bit 31 set by the ring pass of a call whose gather-sum ran as the
     // radius-3 GEMM plus ring (k_dense_ring.hip; dau_conv_gather_outlier_status reports both)
     unsigned int pad[2];
+    // DAU_FLAG_DENSE_SPLIT_LINE.  line[0]: the units of the call's gather-sum table that do NOT lie on the row of their pixel
+    // (oy != 0 or a weight on the row below that is not zero -- a NaN counts; ignored units count too), counted by
+    // prepare_units_kernel.  line[1]: the radius of the line member that ran the pass (written by its scales kernel), 0 if none did.
+    unsigned int line[2];
+    unsigned int pad2[2];
 };
 constexpr unsigned kRingTakenBit = 0x80000000u;
 
@@ -235,12 +240,20 @@ struct Guard {
     float lo, hi;
     unsigned cnt_lo = 0u, cnt_hi = 0xffffffffu;
     float cnt_upto = INFINITY;
+    // DAU_FLAG_DENSE_SPLIT_LINE (Status.line[0], the units off the line).  +R: a line member, runs only where that count is 0.
+    // -R: a member that shares offsets within +-R with a line member, runs there only where the count is not 0.  0: any.
+    // Kernels only READ the status block through their guard, with one exception: the scales kernel of a line member whose guard
+    // has passed writes its radius to Status::line[1] (k_dense_split.hip, split_scales_kernel under DAU_SPLIT_1D).
+    int line = 0;
 };
 __device__ __forceinline__ bool guard_pass(const Guard& g) {
     if (!g.status) return true;
     const float mx = __uint_as_float(g.status->max_abs_mu_bits);
     const unsigned cnt = g.status->pad[1] & ~kRingTakenBit;
-    return mx > g.lo && mx <= g.hi && (mx > g.cnt_upto || (cnt >= g.cnt_lo && cnt <= g.cnt_hi));
+    if (!(mx > g.lo && mx <= g.hi && (mx > g.cnt_upto || (cnt >= g.cnt_lo && cnt <= g.cnt_hi)))) return false;
+    if (g.line == 0) return true;
+    const bool on_line = g.status->line[0] == 0u;
+    return g.line > 0 ? on_line : (mx > (float)-g.line || !on_line);
 }
 
 // One prepared unit for the gather kernels: integer displacement and the four
@@ -261,9 +274,10 @@ void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k,
 // k_units.hip
 // host_status (may be null): pinned host copy of the status block, written by the last workgroup to finish
 // count_ignore: the units left out of the status block's outlier count (-1: `ignore`; the input-gradient table ignores no unit)
+// line_status (may be null; DAU_FLAG_DENSE_SPLIT_LINE): the status block whose line[0] takes the count of this table's units off the line
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
-                          Status* status, HostStatus* host_status, int count_ignore = -1);
+                          Status* status, HostStatus* host_status, int count_ignore = -1, Status* line_status = nullptr);
 void launch_finalize_grads(hipStream_t st, const float* r4, const float* w, Shape sh, int ignore, float lr,
                            int need_mask, bool single_dim, float* dw, float* dmu1, float* dmu2, float* dsigma);
 // k_direct.hip  (DAU_ALGO_DIRECT: plain kernels, any shape)

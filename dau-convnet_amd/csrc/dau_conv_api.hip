@@ -81,6 +81,7 @@ int edge_disabled(int size) {
 enum Member {
     kTiledGather,                // gather-sum (y and dx): the exact tiled kernels of the set's bucket
     kSplit2, kSplit3, kSplit4,   // ... the two-limb f16 dense GEMM of radius 2 / 3 / 4 (k_dense_split.hip: fp32 accuracy)
+    kLine4, kLine8,              // ... its line forms, one row of 9 / 17 taps (DAU_FLAG_DENSE_SPLIT_LINE: calls whose units lie on a line)
     kBf16R3, kBf16R4,            // ... the densified bf16 implicit GEMM of radius 3 / 4 (k_dense_bf16.hip; DAU_FLAG_DENSE_BF16)
     kTiledDot,                   // parameter gradients: the exact tiled gather-dot
     kSplitDot,                   // ... the two-limb f16 GEMM with the bilinear corners as rows (k_split_dot.hip: fp32 accuracy)
@@ -89,12 +90,13 @@ enum Member {
 };
 enum PassKind { kGatherSum, kGatherDot };
 // the offsets a bucket-4 member covers (its device guard's upper end)
-constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 3, 4, 0, 4, 3, 4};
+constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 4, 8, 3, 4, 0, 4, 3, 4};
 constexpr int kFirst[2] = {kTiledGather, kTiledDot}, kEnd[2] = {kTiledDot, kNumMembers};   // the members of a pass kind
 // The radius-4 bf16 member runs in place of its set's exact kernels; every other non-exact member has an arithmetic of its own
 // and goes ahead of the bucket sets under its own guard.
 constexpr int kDense4[2] = {kBf16R4, kWgradR4};
 constexpr bool goes_ahead(int m) { return m != kTiledGather && m != kTiledDot && m != kBf16R4 && m != kWgradR4; }
+constexpr bool is_line(int m) { return m == kLine4 || m == kLine8; }
 
 // gather-sum directions, which are also their profile slots: y from x (S -> F) and dx from the error (F -> S)
 enum Dir { kFwd, kDx };
@@ -114,6 +116,8 @@ const DenseFns kDense[] = {
     {s2::split_gather_configure, s2::split_gather_workspace_bytes, s2::split_gather_init, s2::split_gather_prepare, s2::split_gather_run},
     {s3::split_gather_configure, s3::split_gather_workspace_bytes, s3::split_gather_init, s3::split_gather_prepare, s3::split_gather_run},
     {s4::split_gather_configure, s4::split_gather_workspace_bytes, s4::split_gather_init, s4::split_gather_prepare, s4::split_gather_run},
+    {l4::split_gather_configure, l4::split_gather_workspace_bytes, l4::split_gather_init, l4::split_gather_prepare, l4::split_gather_run},
+    {l8::split_gather_configure, l8::split_gather_workspace_bytes, l8::split_gather_init, l8::split_gather_prepare, l8::split_gather_run},
     {r3::dense_gather_configure, r3::dense_gather_workspace_bytes, r3::dense_gather_init, r3::dense_gather_prepare, run_plain<r3::dense_gather_run>},
     {r4::dense_gather_configure, r4::dense_gather_workspace_bytes, r4::dense_gather_init, r4::dense_gather_prepare, run_plain<r4::dense_gather_run>},
 };
@@ -177,15 +181,14 @@ size_t dot_bytes(const BucketSet& bs) {
     return need;
 }
 
-// Does the dense form of radius r pay against the exact gather?  MFMA work per pass in fp32-rate MAC units: the dense GEMM runs
-// (2r+1)^2 taps x 3 limb products at 16x the fp32 rate over the PADDED tile (8-row / 8-column blocks, 128 output channels, 16 input
+// Does the dense form of `taps` taps ((2r+1)^2; a line form: 2r+1) pay against the exact gather?  MFMA work per pass in fp32-rate
+// MAC units: the dense GEMM runs its taps x 3 limb products at 16x the fp32 rate over the PADDED tile (8-row / 8-column blocks, 128 output channels, 16 input
 // channels) plus its staging, at ~55 % of the f16 roof; the exact gather 4 MACs per live unit at ~60 % of the fp32 roof on maps
 // of 32 pixels and more, ~45 % on smaller ones (measured, same box, gather + staging per pass against the exact gather: NS radius 3
 // 5.4 + 0.5 against 8.9 ms at four units, radius 4 8.5 + 0.5 against 9.4; radius 2 2.9 + 0.5 against 5.4 at two units; C1 27 x 27
 // radius 3 0.36 / 0.42 + 0.07 against 0.60 / 0.51).  On whole tiles radius 2 pays from two units per channel pair on, radius 3 from
 // three, radius 4 from four.
-bool split_pays(int r, int Cin, int Cout, int G_live, int H, int W) {
-    const double taps = (2.0 * r + 1) * (2.0 * r + 1);
+bool split_pays(double taps, int Cin, int Cout, int G_live, int H, int W) {
     const double hp = (H + 7) / 8 * 8, wp = (W + 7) / 8 * 8, fp = (Cout + 127) / 128 * 128, sp = (Cin + 15) / 16 * 16;
     const double dense = hp * wp * (fp * sp * taps * 3.0 / 16.0 / 0.55 + sp * 430.0);
     const double exact = (double)H * W * Cout * Cin * G_live * 4.0 / ((H < 32 || W < 32) ? 0.45 : 0.60);
@@ -294,7 +297,9 @@ int status_error(const dau_conv_plan* p, float mx, bool nan_seen) {
 // its exact kernels: as the static set of a one-bucket plan, as the hinted set, or guarded by (lo, 4] ahead of them.
 // With the radius-3 + ring member: it shares the offsets (3, 4] with what follows it -- the radius-4 member, the hinted or the static
 // set -- and the call's outlier-unit count tells them apart: the ring member at most ring_limit, the others more (or offsets beyond 4).
-constexpr int kMaxCandidates = 7;
+// With line members (DAU_FLAG_DENSE_SPLIT_LINE): they go first, under (-1, 4] and (4, 8], and run where the call's table has no unit
+// off the line; every member that follows and shares offsets with them runs there only where it has one -- the flag-off plan's kernels.
+constexpr int kMaxCandidates = 9;
 int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
     const BucketSet* s0 = &p->sets[0];
@@ -316,17 +321,28 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
     int n = 0;
     float lo = -1.0f;
     bool with_ring = false;
+    int line_r = 0;                                          // the offsets the line members cover
+    for (int m = kLine4; m <= kLine8 && kind == kGatherSum; ++m) {
+        if (!s0->has[m]) continue;
+        Guard g{dev_status, (float)line_r - (line_r ? 0.0f : 1.0f), (float)kRadius[m]};
+        g.line = kRadius[m];
+        out[n++] = Candidate{s0, g, m};
+        line_r = kRadius[m];
+    }
     auto add = [&](const BucketSet* b, int member, float hi) {
         Guard g{dev_status, lo, hi};
+        if (lo < (float)line_r) g.line = -line_r;
         if (with_ring && lo < 4.0f) { g.cnt_lo = s0->ring_limit + 1; g.cnt_upto = 4.0f; }
         out[n++] = Candidate{b, g, member};
         lo = hi;
     };
     for (int m = kFirst[kind]; m < kEnd[kind]; ++m) {
-        if (!(goes_ahead(m) && s0->has[m])) continue;
+        if (!(goes_ahead(m) && s0->has[m]) || is_line(m)) continue;
         add(s0, m, (float)kRadius[m]);
         if (m == kSplit3 && s0->ring) {
-            out[n++] = Candidate{s0, Guard{dev_status, 3.0f, 4.0f, 0u, s0->ring_limit}, kSplit3, true};
+            Guard g{dev_status, 3.0f, 4.0f, 0u, s0->ring_limit};
+            g.line = -line_r;
+            out[n++] = Candidate{s0, g, kSplit3, true};
             with_ring = true;
         }
     }
@@ -543,6 +559,10 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
     if ((flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_OUTLIERS excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
+    if ((flags & DAU_FLAG_DENSE_SPLIT_LINE) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL");
+    if ((flags & DAU_FLAG_DENSE_SPLIT_LINE) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
     if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
         (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
@@ -589,8 +609,22 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                 bool want = b == 4 && bs.has[kTiledGather];
                 if (m == kBf16R4) want = want && want_dense;
                 else if (m == kBf16R3) want = want && bs.has[kBf16R4];
-                else want = want && split_allowed && (split_forced || (split_pays(r, s.S, s.F, g_live, s.H, s.W) &&
-                                                                       split_pays(r, s.F, s.S, g_live, s.H, s.W)));
+                else if (is_line(m)) continue;               // (below)
+                else want = want && split_allowed && (split_forced || (split_pays((2.0 * r + 1) * (2.0 * r + 1), s.S, s.F, g_live, s.H, s.W) &&
+                                                                       split_pays((2.0 * r + 1) * (2.0 * r + 1), s.F, s.S, g_live, s.H, s.W)));
+                DenseConfig* cfg = bs.dense[m - kSplit2];
+                bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
+                            kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
+            }
+            // the line members: bucket 4's set like the others; radius 8 where the plan's offsets reach it and radius 4 is held
+            for (int m = kLine4; m <= kLine8; ++m) {
+                const int r = kRadius[m];
+                // (DAU_FLAG_STATIC_BUCKET: no per-call selection, the flag is inert as the outliers flag is)
+                const bool want = b == 4 && bs.has[kTiledGather] && (flags & DAU_FLAG_DENSE_SPLIT_LINE) && split_allowed &&
+                                  !(flags & DAU_FLAG_STATIC_BUCKET) &&
+                                  (m == kLine4 || (bucket >= 8 && bs.has[kLine4])) &&
+                                  (split_forced || (split_pays(2.0 * r + 1, s.S, s.F, g_live, s.H, s.W) &&
+                                                    split_pays(2.0 * r + 1, s.F, s.S, g_live, s.H, s.W)));
                 DenseConfig* cfg = bs.dense[m - kSplit2];
                 bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
                             kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
@@ -599,10 +633,10 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
             // (the input-gradient table ignores no unit, and the count leaves them out)
             for (int dir : {kFwd, kDx}) {
                 bs.tiled[dir].nhwc = nhwc;
-                for (int m = kSplit2; m <= kSplit4; ++m) bs.dense[m - kSplit2][dir].nhwc = nhwc;
+                for (int m = kSplit2; m <= kLine8; ++m) bs.dense[m - kSplit2][dir].nhwc = nhwc;
             }
             bs.tiled[kFwd].in_relu = in_relu;
-            for (int m = kSplit2; m <= kSplit4; ++m) bs.dense[m - kSplit2][kFwd].in_relu = in_relu;
+            for (int m = kSplit2; m <= kLine8; ++m) bs.dense[m - kSplit2][kFwd].in_relu = in_relu;
             bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
             if (bs.ring) {
                 bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
@@ -755,6 +789,8 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
         for (int m = kSplit2; m <= kSplit4; ++m)
             if (s0[m]) info->gather_dense_split |= 1 << kRadius[m];
     if (plan->sets[0].ring) info->gather_dense_split |= 1 << 5;
+    if (plan->dynamic && tiled_fwd && s0[kLine4]) info->gather_dense_split |= 1 << 6;
+    if (plan->dynamic && tiled_fwd && s0[kLine8]) info->gather_dense_split |= 1 << 7;
     return DAU_OK;
 }
 
@@ -780,7 +816,7 @@ int forward_pass(const dau_conv_plan* p, void* stream, const float* x, const flo
     DAU_HIP(hipMemsetAsync(ws.status, 0, sizeof(Status), st));
     launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters);
     launch_prepare_units(st, w, mu1, mu2, p->sh, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table, ws.status,
-                         p->host_status);
+                         p->host_status, -1, p->sets[0].has[kLine4] ? ws.status : nullptr);
     run_gather_sum(p, st, kFwd, x, y, ws.filters, ws.table, ws.status, ws.gather, epi);
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;
@@ -936,8 +972,9 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
         // input gradient: the forward gather on the mirrored-Gaussian-blurred error with the
         // parameters read as [F,G,S] and negated offsets (base_dau_conv_layer.cu:299-325)
         const bool fresh = !(need_mask & param_mask);     // this call has not looked at the offsets yet
+        // (the line members' condition is counted on THIS table, whether or not the offsets have been looked at)
         launch_prepare_units(st, w, mu1, mu2, s, 0, flags, p->bucket, true, ws.table_t, fresh ? ws.status : nullptr,
-                             p->host_status, p->d.number_units_ignore);
+                             p->host_status, p->d.number_units_ignore, p->sets[0].has[kLine4] ? ws.status : nullptr);
         // DAU_FLAG_INPUT_RELU: the ReLU's backward in the store, dx = (x <= 0) ? 0 : sum, from the raw x at the store's own index
         Epilogue gate;
         if (flags & DAU_FLAG_INPUT_RELU) gate.gate = x;
@@ -995,6 +1032,17 @@ int dau_conv_gather_outlier_status(const dau_conv_plan* p, void* stream, const v
     DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
     if (outlier_units) *outlier_units = (int32_t)(h.pad[1] & ~kRingTakenBit);
     if (ring_taken) *ring_taken = (h.pad[1] & kRingTakenBit) ? 1 : 0;
+    return DAU_OK;
+}
+
+int dau_conv_gather_line_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* off_line_units,
+                                int32_t* line_radius_taken) {
+    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    Status h;
+    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
+    if (off_line_units) *off_line_units = (int32_t)h.line[0];
+    if (line_radius_taken) *line_radius_taken = (int32_t)h.line[1];
     return DAU_OK;
 }
 

@@ -88,6 +88,9 @@ DAU_DECLARE_DENSE_GATHER(r3)
 DAU_DECLARE_SPLIT_GATHER(s2)
 DAU_DECLARE_SPLIT_GATHER(s3)
 DAU_DECLARE_SPLIT_GATHER(s4)
+// the line forms (-DDAU_SPLIT_1D): one row of 2 R + 1 taps, R = 4 and 8 (DAU_FLAG_DENSE_SPLIT_LINE)
+DAU_DECLARE_SPLIT_GATHER(l4)
+DAU_DECLARE_SPLIT_GATHER(l8)
 
 // Radius 3 with outliers (DAU_FLAG_DENSE_SPLIT_OUTLIERS): a call whose offsets reach into (3, 4] in few units runs the radius-3
 // GEMM on the corners inside 7 x 7 (split_densify_kernel drops the others) plus a list-driven fp32 pass over the corners on the

@@ -79,7 +79,27 @@ namespace {
 constexpr int kDR = DAU_SPLIT_R;        // offset radius of the form
 constexpr int kDK = 2 * kDR + 1;        // taps per axis (an offset of exactly +R has fraction 0: the tap at R + 1 carries weight 0)
 constexpr int kDSpan = kDK - 1;
-constexpr int kDTaps = kDK * kDK;
+// The line forms (-DDAU_SPLIT_1D, namespaces l4 ...; DAU_FLAG_DENSE_SPLIT_LINE): the same GEMM over ONE row of taps, for calls whose
+// units all lie on the row of their pixel (oy == 0 and no weight on the row below: the call's device guard decides).  The vertical
+// radius is 0: no halo rows in the staged copy or in the LDS window, one row of the dense kernel, a tap loop over tx alone.
+#ifndef DAU_SPLIT_1D
+#define DAU_SPLIT_1D 0
+#endif
+constexpr bool kLine = DAU_SPLIT_1D != 0;
+// The kernels of the line forms are named line_*_kernel (l4::line_gather_kernel, ...): tools and the built-code tests pick the 2-D
+// forms' kernels by the name split_*_kernel.  EVERY __global__ function of this file is listed here.
+#if DAU_SPLIT_1D
+#define split_absmax_kernel line_absmax_kernel
+#define split_scales_kernel line_scales_kernel
+#define split_densify_kernel line_densify_kernel
+#define split_stage_kernel line_stage_kernel
+#define split_stage_walk_kernel line_stage_walk_kernel
+#define split_gather_kernel line_gather_kernel
+#endif
+constexpr int kDRV = kLine ? 0 : kDR;   // vertical radius, taps and span
+constexpr int kDKV = 2 * kDRV + 1;
+constexpr int kDSpanV = kDKV - 1;
+constexpr int kDTaps = kDKV * kDK;
 constexpr int kDRows = 8;               // output rows per workgroup
 constexpr int kDFB = 128;               // output channels per workgroup
 constexpr int kAhead = 2;               // taps the A stream runs ahead
@@ -88,7 +108,11 @@ constexpr int kAhead = 2;               // taps the A stream runs ahead
 #endif
 constexpr int kFlushTaps = DAU_SPLIT_FLUSH_TAPS > 0 ? DAU_SPLIT_FLUSH_TAPS : kDK;   // taps chained through `part` before it joins the running sum
 #ifndef DAU_SPLIT_FLUSH_ROWS
+#if DAU_SPLIT_1D
+#define DAU_SPLIT_FLUSH_ROWS 1          // line forms: a row of taps is a whole chunk, 27 / 51 MFMAs per chain (profiles/r17_ab_line_chain_length.txt)
+#else
 #define DAU_SPLIT_FLUSH_ROWS 4          // rows of taps per chain (> 1: the chain runs across rows and chunks, `part` is zeroed by moves)
+#endif
 #endif
 constexpr int kFlushRows = DAU_SPLIT_FLUSH_ROWS;
 // The MFMA shape of the gather-sum, chosen per radius at compile time (every form of a radius shares one tap loop):
@@ -96,7 +120,7 @@ constexpr int kFlushRows = DAU_SPLIT_FLUSH_ROWS;
 // v_mfma_f32_32x32x16_f16 over one chunk elsewhere.  -DDAU_SPLIT_MFMA32 keeps the 32x32x16 loop at every radius: the A/B partner
 // (libdau_conv_hip_mfma32.so).
 #if !defined(DAU_SPLIT_K32)
-#if !defined(DAU_SPLIT_MFMA32) && DAU_SPLIT_R == 3
+#if !defined(DAU_SPLIT_MFMA32) && DAU_SPLIT_R == 3 && !DAU_SPLIT_1D
 #define DAU_SPLIT_K32 1
 #else
 #define DAU_SPLIT_K32 0
@@ -148,7 +172,7 @@ SplitGeom split_geometry(const DenseConfig& c) {
     const int rows4 = DAU_TUNE_INT("DAU_SPLIT_ROWS4", 1);    // tuning build: 0 never, 2 always (the variant tests)
     g.nrb4 = (left >= 1 && left <= 4 && rows4 != 0 && (wgs >= 1024 || rows4 == 2)) ? 1 : 0;
     g.nrb8 = c.H / kDRows + (left && !g.nrb4 ? 1 : 0);
-    g.Hs = g.nrb8 * kDRows + g.nrb4 * 4 + kDSpan;
+    g.Hs = g.nrb8 * kDRows + g.nrb4 * 4 + kDSpanV;
     {
         // tall tiles where they compute at least 5 % fewer tile positions than the 4 x 8 ones (whose waves skip dead groups of four rows):
         // 28 x 28 with a block of four rows: 24 x 28 + 4 x 32 against 28 x 32
@@ -291,6 +315,9 @@ __global__ void __launch_bounds__(256) split_scales_kernel(const unsigned* __res
         } else {
             const float s = limb_scale(__uint_as_float(m) * (float)G);    // a dense tap sums at most G units
             out->max_w_bits = m; out->sw = s; out->inv_sw = 1.0f / s;
+            // a line form's guard has passed: this member does the pass's work (dau_conv_gather_line_status reports it).  The one
+            // write a kernel makes through its guard (dau_common.hpp, Guard): one thread, the same value in every slab of a pass
+            if constexpr (kLine) { if (guard.status) const_cast<Status*>(guard.status)->line[1] = (unsigned)kDR; }
         }
     }
 }
@@ -314,9 +341,9 @@ __global__ void __launch_bounds__(kScT) split_densify_kernel(const UnitRef* __re
     if (c < Cin && f < Cout) {
         for (int g = 0; g < G; ++g) {
             const UnitRef u = table[((long)c * G + g) * Cout + f];
-            const int ty = u.oy + kDR, tx = u.ox + kDR;
+            const int ty = u.oy + kDRV, tx = u.ox + kDR;
             // (a tap outside the kernel belongs to an offset of exactly +R, weight 0, or to a call whose guard does not pass)
-            const bool y0 = ty >= 0 && ty < kDK, y1 = ty + 1 >= 0 && ty + 1 < kDK, x0 = tx >= 0 && tx < kDK, x1 = tx + 1 >= 0 && tx + 1 < kDK;
+            const bool y0 = ty >= 0 && ty < kDKV, y1 = ty + 1 >= 0 && ty + 1 < kDKV, x0 = tx >= 0 && tx < kDK, x1 = tx + 1 >= 0 && tx + 1 < kDK;
             if (y0 && x0) acc[(ty * kDK + tx) * kScT + tid] += u.w00;
             if (y0 && x1) acc[(ty * kDK + tx + 1) * kScT + tid] += u.w01;
             if (y1 && x0) acc[((ty + 1) * kDK + tx) * kScT + tid] += u.w10;
@@ -403,8 +430,8 @@ __device__ __forceinline__ void split_stage_walk(const float* rawl, const float*
     for (int j = 0; j < K; ++j) gy[j] = py[j];
     float ring[K][NCH];
     const int nin = yb - ya + 2 * kr;                        // input rows ya - kr .. yb + kr - 1
-    char* dhi = reinterpret_cast<char*>(xhi + (long)kDR * Ws + kDR + x) + ch0 * 2;
-    char* dlo = reinterpret_cast<char*>(xlo + (long)kDR * Ws + kDR + x) + ch0 * 2;
+    char* dhi = reinterpret_cast<char*>(xhi + (long)kDRV * Ws + kDR + x) + ch0 * 2;
+    char* dlo = reinterpret_cast<char*>(xlo + (long)kDRV * Ws + kDR + x) + ch0 * 2;
     for (int s0 = 0; s0 < nin; s0 += K) {
 #pragma unroll
         for (int j = 0; j < K; ++j) {
@@ -568,14 +595,14 @@ __global__ void __launch_bounds__(kStageThreads) split_stage_kernel(const SplitS
     u32x4* xhi = reinterpret_cast<u32x4*>(a.xs) + ((((long)n * a.nchunk + chunk) * 2 + 0) * 2 + half) * splane;
     u32x4* xlo = xhi + 2 * splane;
     {
-        const int rs0 = band == 0 ? 0 : y0 + kDR, rs1 = band == a.nbands - 1 ? a.Hs : y1 + kDR;
+        const int rs0 = band == 0 ? 0 : y0 + kDRV, rs1 = band == a.nbands - 1 ? a.Hs : y1 + kDRV;
         const int cs0 = seg == 0 ? 0 : x0 + kDR, cs1 = seg == a.nsegs - 1 ? a.Ws : x1 + kDR;
         const int cw = cs1 - cs0, cnt = (rs1 - rs0) * cw;
         const float inv = 1.0f / (float)cw;
         const u32x4 z = {0u, 0u, 0u, 0u};
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
             const int rr = fast_div(i, cw, inv), r = rs0 + rr, cc = cs0 + i - rr * cw;
-            if (r >= y0 + kDR && r < y1 + kDR && cc >= x0 + kDR && cc < x1 + kDR) continue;
+            if (r >= y0 + kDRV && r < y1 + kDRV && cc >= x0 + kDR && cc < x1 + kDR) continue;
             xhi[(long)r * a.Ws + cc] = z;
             xlo[(long)r * a.Ws + cc] = z;
         }
@@ -678,7 +705,7 @@ __device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, f
 #pragma unroll
         for (int cp = 0; cp < NCH / 2; ++cp) ring[i][cp] = f32x2{0.0f, 0.0f};
     auto load_row = [&](int u, Raw* dst) {
-        const int r = b0 - kDR - kr + u, rc = r < 0 ? 0 : r < H ? r : H - 1;
+        const int r = b0 - kDRV - kr + u, rc = r < 0 ? 0 : r < H ? r : H - 1;
         const long rowbase = gbase + (long)rc * W;
 #pragma unroll
         for (int l = 0; l < 8; ++l) dst[l] = load_raw<A>(a.in, rowbase + (grp * 8 + l < a.C ? l : 0) * plane + (long)offm);
@@ -697,7 +724,7 @@ __device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, f
     auto step = [&](auto pc, int u) {
         constexpr int P = decltype(pc)::value;
         load_row(u + kAhead, rv[(P + kAhead) % K]);
-        const int r = b0 - kDR - kr + u;
+        const int r = b0 - kDRV - kr + u;
         const bool row_in = r >= 0 && r < H;
         float* buf = lds + (u & 1) * kBuf;
         if (CWL == 64 || lane < CWL) {
@@ -725,7 +752,7 @@ __device__ __forceinline__ void split_stage_walk_tile(const SplitStageArgs& a, f
         }
 #pragma unroll
         for (int cp = 0; cp < NCH / 2; ++cp) ring[P][cp] = h[cp];
-        const int rs = b0 + u - (K - 1), y = rs - kDR;
+        const int rs = b0 + u - (K - 1), y = rs - kDRV;
         f32x2 o[NCH / 2];
 #pragma unroll
         for (int cp = 0; cp < NCH / 2; ++cp) o[cp] = f32x2{0.0f, 0.0f};
@@ -833,7 +860,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
     constexpr int kRowsWG = 4 * RG;                          // output rows per workgroup
     constexpr int NT0 = (RG == 2 && !TT) ? NSUB : (NSUB + 1) / 2;      // tiles per wave
     constexpr int NT1 = TT ? NSUB / 2 : NT0;                 // ... of the second column half (tall tiles)
-    constexpr int WR = kRowsWG + kDSpan;                     // window rows
+    constexpr int WR = kRowsWG + kDSpanV;                    // window rows
     // K32: K groups 0 and 1 of a ds_read_b128 lane group read planes one `HALF` apart: a whole number of bank rows (16 positions)
     constexpr int PLANE = kK32 ? (WR * P + 15) / 16 * 16 : WR * P;   // 16-byte units of one (limb, half) plane window
     constexpr int HALF = PLANE * 16;                         // ... in bytes
@@ -1081,7 +1108,8 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
 #endif
     issue(0, 0);
     f16x8 ah[kDK], al[kDK], an[2], bn[2];                   // A fragments (hi, lo) of a row of taps; the next row's first two
-    static_assert(kAhead == 2 && kDK >= 5 && kDK <= 9, "the A ring below is written for two taps ahead");
+    // (a fragment lives from its request to its tap, two taps on: the seventeen taps of the radius-8 line form need no more registers)
+    static_assert(kAhead == 2 && kDK >= 5 && (kDK <= 9 || kLine), "the A ring below is written for two taps ahead");
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) { ah[i] = wp[i * wtap]; al[i] = wp[i * wtap + wlo]; }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1096,7 +1124,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
         // are copied into place at the row's end.  Within a row: tap tx requests the A fragments of tap tx + 2 after its first
         // MFMA group, reads its lo fragments under the hi MFMAs and the next tap's hi fragments under the lo MFMAs.
 #pragma unroll 1
-        for (int ty = 0; ty < (live ? kDK : 0); ++ty) {
+        for (int ty = 0; ty < (live ? kDKV : 0); ++ty) {
             const unsigned brow = bbase + ty * P * 16;
             f16x8 xh[NT], xl[NT];
 #pragma unroll
@@ -1219,7 +1247,7 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
 #endif
     issue(0, 0);
     f16x8 ah[kDK][2], al[kDK][2], an[2][2], bn[2][2];       // A fragments (hi, lo) x m of a row of taps; the next row's first two
-    static_assert(kAhead == 2 && kDK >= 5 && kDK <= 9, "the A ring below is written for two taps ahead");
+    static_assert(kAhead == 2 && kDK >= 5 && (kDK <= 9 || !kK32), "the A ring below is written for two taps ahead");
 #pragma unroll
     for (int i = 0; i < kAhead; ++i) {
 #pragma unroll
@@ -1240,12 +1268,12 @@ __global__ void __launch_bounds__(512) split_gather_kernel(const typename std::c
         // A fragments of tap tx + 2 after its first two MFMAs; the next row's first two are requested at the row's last taps but one and
         // have landed at its end.
 #pragma unroll 1
-        for (int ty = 0; ty < (live ? kDK : 0); ++ty) {
+        for (int ty = 0; ty < (live ? kDKV : 0); ++ty) {
             const unsigned brow = bbase + ty * P * 16;
             const long wrow = 2 * pair * wchunk + (long)ty * kDK * wtap;
             const __amdgpu_buffer_rsrc_t wcur = rows_from(wrow);
             // the next row of taps (after a pair's last row: of the next pair)
-            const __amdgpu_buffer_rsrc_t wnxt = rows_from(wrow + kDK * wtap + (ty == kDK - 1 && more ? wchunk : 0));
+            const __amdgpu_buffer_rsrc_t wnxt = rows_from(wrow + kDK * wtap + (ty == kDKV - 1 && more ? wchunk : 0));
             f16x8 xb[3][2];
             auto read = [&](int u, int limb) __attribute__((always_inline)) {
                 const int tx = u / NG, p = u % NG;
@@ -1340,7 +1368,7 @@ namespace {
 
 template <int NSUB, int RG, bool TT>
 constexpr size_t split_lds_bytes() {
-    constexpr int plane = (4 * RG + kDSpan) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB));
+    constexpr int plane = (4 * RG + kDSpanV) * (TT ? lds_pitch_narrow(NSUB) : lds_pitch(NSUB));
     return (kK32 ? 4 : 2) * (size_t)((4 * (kK32 ? (plane + 15) / 16 * 16 : plane) + 63) / 64) * 1024;
 }
 

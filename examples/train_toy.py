@@ -3,10 +3,12 @@ reference's constructor arguments) inside an ordinary PyTorch training loop.  Of
 operator's own gradients; `mu_learning_rate_factor` scales them inside the op as in the reference
 (plugins/tensorflow/src/dau_conv_grad_op.cpp:297-303).
 
-    python examples/train_toy.py [--steps 60] [--compile [--backend inductor]]
+    python examples/train_toy.py [--steps 60] [--compile [--backend inductor]] [--conv1d]
 
 --compile wraps the student in torch.compile: each DAU layer becomes one opaque op (torch.ops.dau_conv.conv) of a single graph, runs
 the same kernels on the same bits, and the losses printed are those of the eager run.
+--conv1d trains a stack of single-dimension layers (DAUConv1d: offsets along x only) twice from the same seed, without and with
+dense_line=True (calls whose units lie on a line run the 1 x 9 two-limb GEMM), and prints the two loss curves side by side.
 """
 import argparse
 import os
@@ -48,11 +50,47 @@ def run(steps=60, seed=0, verbose=True, compile=False, backend="inductor"):
     return losses
 
 
+def run_conv1d(steps=60, seed=0, dense_line=False, verbose=False):
+    """The same task on DAUConv1d layers; dense_line: the line members of the two-limb gather-sum for the student's layers."""
+    torch.manual_seed(seed)
+    dev = torch.device("cuda", 0)
+    teacher = dau_conv.DAUConv1d(filters=16, dau_units=(2, 1), max_kernel_size=9, use_bias=False, in_channels=8,
+                                 mu1_initializer=dau_conv.random_uniform_initializer(-3, 3)).to(dev)
+    for p in teacher.parameters():
+        p.requires_grad_(False)
+    student = torch.nn.Sequential(
+        dau_conv.DAUConv1d(filters=16, dau_units=(2, 1), max_kernel_size=9, in_channels=8, activation=torch.relu,
+                           mu_learning_rate_factor=10, fused_epilogue=True, dense_line=dense_line),
+        dau_conv.DAUConv1d(filters=16, dau_units=(2, 1), max_kernel_size=9, in_channels=16, use_bias=False,
+                           mu_learning_rate_factor=10, fused_epilogue=True, dense_line=dense_line),
+    ).to(dev)
+    opt = torch.optim.Adam(student.parameters(), lr=3e-3)
+    losses = []
+    for step in range(steps):
+        x = torch.rand(16, 8, 32, 32, device=dev)
+        loss = torch.nn.functional.mse_loss(student(x), teacher(x))
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+        if verbose and step % 10 == 0:
+            print("step %3d  loss %.5f" % (step, losses[-1]))
+    return losses
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--compile", action="store_true", help="wrap the student in torch.compile")
     ap.add_argument("--backend", default="inductor", help="torch.compile backend (aot_eager needs no code generation)")
+    ap.add_argument("--conv1d", action="store_true", help="DAUConv1d layers, without and with dense_line=True")
     args = ap.parse_args()
+    if args.conv1d:
+        off, on = run_conv1d(args.steps, dense_line=False), run_conv1d(args.steps, dense_line=True)
+        print("step   loss            loss (dense_line=True)")
+        for step in range(0, args.steps, 10):
+            print("%4d   %.5f         %.5f" % (step, off[step], on[step]))
+        print("loss %.5f -> %.5f   (dense_line=True: %.5f -> %.5f)" % (off[0], off[-1], on[0], on[-1]))
+        sys.exit(0)
     l = run(args.steps, compile=args.compile, backend=args.backend)
     print("loss %.5f -> %.5f" % (l[0], l[-1]))

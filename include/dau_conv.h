@@ -211,6 +211,20 @@ enum {
                                                DAU_FLAG_STATIC_BUCKET and the fused output epilogue and residual of the same call;
                                                excludes DAU_FLAG_DENSE_BF16; needs the tiled kernels (not DAU_ALGO_DIRECT, nor a shape
                                                that falls back to the direct kernels).                                          */
+    DAU_FLAG_DENSE_SPLIT_LINE = 1 << 15,    /* opt-in, single-dimension layers (needs DAU_FLAG_SINGLE_DIM_KERNEL): the gather-sum passes (y, dx)
+                                               of a call whose units all lie on the row of their pixel -- mu2 == 0, i.e. every entry of the
+                                               pass's unit table has a vertical displacement of 0 and no weight on the row below; ignored
+                                               units count -- run as the two-limb f16 GEMM over ONE row of taps: 1 x 9 for offsets within
+                                               +-4, 1 x 17 within +-8 (where max_kernel_size >= 11 allows such offsets) instead of the
+                                               9 x 9 kernel or the exact gather.  fp32 accuracy, as the 2-D two-limb members.  The device
+                                               decides per call: a call with a unit off the line (a NaN / Inf weight counts as one) runs
+                                               exactly the kernels of the plan without the flag and returns its bits.  A line member is
+                                               held where the cost model says it pays in both directions (DAU_FLAG_DENSE_SPLIT_F16: always)
+                                               and the prefilter support has a two-limb staging kernel (<= 11); dau_conv_plan_info
+                                               .gather_dense_split bits 6 / 7 report it.  Without the flag no plan changes.  Inert under
+                                               DAU_FLAG_STATIC_BUCKET and DAU_ALGO_DIRECT; excludes DAU_FLAG_NO_DENSE_SPLIT and
+                                               DAU_FLAG_DENSE_BF16; combines with every other flag.  The parameter gradients are not
+                                               affected.                                                                         */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
@@ -287,7 +301,9 @@ typedef struct dau_conv_plan_info {
                                    gradients do too (49 displacements); 0: the 9x9 members only */
     int32_t gather_dense_split; /* bit r (r = 2, 3, 4): calls whose offsets lie within +-r can run their gather-sum passes as the
                                    two-limb f16 GEMM of that radius (0: never); bit 5: calls within +-4 with few units beyond +-3
-                                   can run theirs as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS) */
+                                   can run theirs as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS); bits 6 and
+                                   7: calls whose units lie on a line, offsets within +-4 / within (4, 8], can run theirs as the 1 x 9 /
+                                   1 x 17 line member (DAU_FLAG_DENSE_SPLIT_LINE) */
 } dau_conv_plan_info;
 
 DAU_API int dau_conv_abi_version(void);
@@ -388,6 +404,13 @@ DAU_API int dau_conv_check_status(const dau_conv_plan *plan, void *stream, const
  * as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS), 0 if another member did the work.  Either may be NULL. */
 DAU_API int dau_conv_gather_outlier_status(const dau_conv_plan *plan, void *stream, const void *workspace,
                                    int32_t *outlier_units, int32_t *ring_taken);
+
+/* Waits for `stream`, then reports of the last call that used `workspace`: off_line_units = the units of its gather-sum table that
+ * do not lie on the row of their pixel (vertical displacement != 0, or a weight on the row below that is not zero -- a NaN counts;
+ * ignored units count), counted only by plans that hold a line member; line_radius_taken = 4 or 8 if the call's gather-sum pass ran
+ * as the line member of that radius (DAU_FLAG_DENSE_SPLIT_LINE), 0 if another member did the work.  Either may be NULL. */
+DAU_API int dau_conv_gather_line_status(const dau_conv_plan *plan, void *stream, const void *workspace,
+                                int32_t *off_line_units, int32_t *line_radius_taken);
 
 /* The same report without waiting, from pinned host memory.  A NaN or an out-of-range offset seen by ANY completed call of
  * this plan since the last report is STICKY: it stays until this function (or dau_conv_check_status) has returned it once,
