@@ -794,6 +794,21 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
     return DAU_OK;
 }
 
+int dau_conv_split_dot_geometry(const dau_conv_plan* plan, int32_t* region_width, int32_t* strip_items, int32_t* strip_k_steps) {
+    if (!plan) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    int rw = 0, items = 0, steps = 0;
+    for (int i = 0; i < plan->nsets && !rw; ++i) {
+        const BucketSet& bs = plan->sets[i];
+        if (!bs.has[kSplitDot]) continue;
+        rw = bs.sdot.RW;
+        split_dot_strip(bs.sdot, &items, &steps);
+    }
+    if (region_width) *region_width = rw;
+    if (strip_items) *strip_items = items;
+    if (strip_k_steps) *strip_k_steps = steps;
+    return DAU_OK;
+}
+
 int dau_conv_workspace_bytes(const dau_conv_plan* plan, int pass, size_t* bytes_out) {
     if (!plan || !bytes_out) return fail(DAU_INVALID_ARGUMENT, "null argument");
     if (pass == DAU_PASS_FORWARD) *bytes_out = carve_forward(plan, nullptr).bytes;

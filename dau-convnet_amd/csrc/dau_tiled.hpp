@@ -182,6 +182,9 @@ struct SplitDotConfig {
 };
 bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);
 size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);
+// the regions (items) of one column strip and the K steps the main kernel runs for them: RW per item, ceil(RW / 4) for a strip's
+// last item where it holds a single real row ((H + 1) % 4 == 1)
+void split_dot_strip(const SplitDotConfig& cfg, int* items, int* k_steps);
 void split_dot_init(const SplitDotConfig& cfg);
 // prepare: fp32 derivative filtering (blur4_pack), per-channel maxima, limb staging of Xk and of the error; run: the GEMM + the
 // reduction into r4 (all four kinds; x, dy fp32 or f16 NCHW; table = bare unit table [S][G][F])

@@ -30,6 +30,8 @@
 //  * Bank conflicts.  The LDS window is position-major with the 16 output channels of a position in consecutive 16-byte groups, so
 //    the bank group of a ds_read_b128 is (lane % 16) whatever the unit's displacement: every read phase of 16 lanes touches 16
 //    distinct groups.  The unit-to-lane placement (lane % 16 = f % 16) is conflict-free by construction; no placement table.
+//  * Thin items.  Where H + 1 = 4 n + 1 (every map whose height is a multiple of four) the last region of a strip holds one real
+//    row; that item takes the row's columns four at a time as its K groups: ceil(RW / 4) K steps instead of RW (sd_dot_body).
 //  * Accuracy.  Per item a tile's accumulator chains 3 x RW MFMAs (hierarchical accumulation, as in the gather-sum); the bilinear
 //    combination joins a running fp32 sum per unit, flushed every few items into the float partial sums [chunk][4][S][G][F] with a
 //    no-return atomic add (the slot belongs to one lane: the program's order), summed over the chunks in double (dot_reduce).
@@ -64,8 +66,20 @@ constexpr unsigned kVmcnt0 = 0x0F70, kVmcnt8 = 0x0F78;
 
 inline size_t rup(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// Thin items: where the H + 1 rows of q leave ONE real row in a strip's last region ((H + 1) % 4 == 1: every map whose height is a
+// multiple of four), that item takes its row's columns four at a time as the K groups of an MFMA, ceil(RW / 4) K steps instead
+// of RW (sd_dot_body).  -DDAU_SD_NO_THIN (libdau_conv_hip_no_thin.so of `make tuning`) runs every item in full: the A/B partner
+// and, for shapes without such a row, the bit-exact reference of tests/test_gpu_split_dot_thin_row.py.
+#ifdef DAU_SD_NO_THIN
+constexpr bool kSdThin = false;
+#else
+constexpr bool kSdThin = true;
+#endif
+
 struct SdGeom {
     int Hq, Wq, rq, cq, XTr, XTc, EYs, EXs, octs, nfb, nsb, ngb, items, chunks, per, NP;
+    int thin;               // the last region of every strip is a thin item
+    int strip_steps;        // K steps of a column strip of regions
 };
 
 SdGeom sd_geom(const SplitDotConfig& c) {
@@ -74,6 +88,8 @@ SdGeom sd_geom(const SplitDotConfig& c) {
     g.Hq = (s.H + 1 + kSdRH - 1) / kSdRH * kSdRH;
     g.Wq = (s.W + 1 + c.RW - 1) / c.RW * c.RW;
     g.rq = g.Hq / kSdRH; g.cq = g.Wq / c.RW;
+    g.thin = kSdThin && (s.H + 1) % kSdRH == 1 && g.rq >= 2;
+    g.strip_steps = (g.rq - g.thin) * c.RW + g.thin * ((c.RW + kSdRH - 1) / kSdRH);
     g.XTr = g.Hq + 1; g.XTc = g.Wq + 1;
     g.EYs = g.Hq + 2 * kSdR; g.EXs = g.Wq + 2 * kSdR;
     g.octs = (s.N + 7) / 8;
@@ -763,6 +779,7 @@ struct SdArgs {
     float* partial;             // [chunk][4][S][G][F]
     int S, F, G;
     int nfb, nsb, ngb, per, items, rq, cq, XTr, XTc, EYs, EXs;
+    int thin;                   // SdGeom::thin
     Guard guard;
 };
 
@@ -863,6 +880,10 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
 #pragma unroll
     for (int i = 0; i < kSdAS; ++i) shx[i] = sd_shift(a.xmax[sidx[i] * kNumK + j]);
     auto flush = [&]() {
+        // (the lane's kind goes through an empty asm statement: the slots' addresses are computed here, every kSdFlushItems items,
+        // and hold no registers while the items run -- the three kinds of item below each end with a copy of this code)
+        int jf = j;
+        asm volatile("" : "+v"(jf));
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i) {
             // undo the scales: 2^-(shift of (s, k) + shift of f), in two exact steps
@@ -871,7 +892,7 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
                 const int g = gb * kSdGT + gg;
                 if (s_ok[i] && g < a.G && f_ok) {
                     const float v = ldexpf(ldexpf(run[i][gg], -shx[i]), -she);
-                    float* dst = a.partial + ((((size_t)chunk * kNumK + j) * a.S + sidx[i]) * a.G + g) * a.F + f;
+                    float* dst = a.partial + ((((size_t)chunk * kNumK + jf) * a.S + sidx[i]) * a.G + g) * a.F + f;
                     __hip_atomic_fetch_add(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 run[i][gg] = 0.0f;
@@ -893,7 +914,8 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
             const int rr = u / kRowPieces, pc = u - rr * kRowPieces;
             const unsigned within = pc * 1024 + lane * 16;
             const unsigned slot = (unsigned)(origin + w0 + rr) & (kRing - 1);
-            if (within < RB) sd_glds16(src + (size_t)rr * a.EXs * PB + within, lds0 + slot * RB + pc * 1024);
+            // (readfirstlane: hipcc may form this wave-uniform address in vector registers, and the asm statement's m0 takes a scalar one)
+            if (within < RB) sd_glds16(src + (size_t)rr * a.EXs * PB + within, __builtin_amdgcn_readfirstlane(lds0 + slot * RB + pc * 1024));
         }
 #endif
     };
@@ -908,19 +930,58 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
     // next item into sets 0 and 1 (software pipeline).
     // -DDAU_SD_STEP_LOADS (tuning builds) keeps one load per K step, set p holding the steps of parity p: the same fragments
     // into the same MFMAs, bit for bit.
+    // Thin items (a.thin: the last region of every strip holds one real row, t = 4 ry; rows 4 ry + 1 .. + 3 are zero on both
+    // sides).  K group j of a thin item is the row's column 4 k + j instead of row j of column k: ceil(RW / 4) K steps.
+    //  * A: lane (m, j) reads X[row 4 ry + dy, column 4 k + j + dx] -- its offset aoff with the row term j * XTc replaced by the
+    //    column term j (thin_adjust below, derived where it is used: no register array of its own).  Adjacent columns sit in
+    //    different lane groups, so every K step loads its own fragment: no pair / DPP scheme.
+    //  * B: the unit's window row is that of K group 0 for all four groups, its byte offset grows by j * PB, a K step advances
+    //    4 * PB (PB is a multiple of 256 B: the bank group of a read stays lane % 16).
+    //  * RW = 10: the third K step covers columns 8 .. 11; the groups of columns 10 and 11 (the next region's) get a zero A
+    //    fragment by a select and read the B column of group 0, so no lane reads beyond the window row and nothing is counted twice.
+    //  * The counted wait.  vmcnt(8) at the top of an item names the eight A loads of the item's first two K steps, sets 0 and 1
+    //    in this order, whatever kind of item follows whatever kind: the item in front of a thin item fetches the thin item's
+    //    fragments of K steps 0 and 1 in exactly the slots where it would fetch pairs 0 and 1 (the look-ahead address gets the
+    //    lane term nadj and the stride nstep), and a thin item loads its third fragment (into the registers the odd steps'
+    //    fragments use elsewhere) BEFORE it fetches the next item's sets 0 and 1, again as its last eight loads.  A thin item is
+    //    the last of its strip and copies no window rows; it also waits for its look-ahead loads before it ends (below), which
+    //    costs part of one load's latency per strip: the loads have been in flight for one to two of its three K steps.
+    //  * A thin K step reads the B fragments of one input channel at a time (the full items read channel 1's while channel 0's
+    //    MFMAs run): 32 registers less, and 3 K steps in 180 are not where the time goes.
+    // (mod 2^32: aoff + tadj >= 0; the lane's j goes through an empty asm statement, so that the term is computed where it
+    // is used and holds no register while the full items run)
+    auto thin_adjust = [&]() {
+        int jj = j;
+        asm volatile("" : "+v"(jj));
+        return (unsigned)(jj * 2) - (unsigned)(jj * a.XTc * 2);
+    };
+    constexpr int kThinStride = 2 * kSdRH;               // 16-byte units between the A fragments of a thin item's K steps
+    constexpr int kThinSteps = (RW + kSdRH - 1) / kSdRH;
+    static_assert(kThinSteps == 3, "a thin item: sets 0 and 1, then the third fragment");
+    auto is_thin = [&](int item) { return a.thin && item % a.rq == a.rq - 1; };
     h8 ahi[2][kSdAS], alo[2][kSdAS];
     if (it0 < it1) {
+        const bool th = is_thin(it0);
+        const unsigned adj0 = th ? thin_adjust() : 0u;
+        const size_t stride0 = th ? kThinStride : kSdAStride;
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int i = 0; i < kSdAS; ++i) {
-                const h8* ap = a.xs + item_off(it0) + (size_t)p * kSdAStride + aoff[i];
+                const h8* ap = a.xs + item_off(it0) + (size_t)p * stride0 + (aoff[i] + adj0);
                 ahi[p][i] = ap[0]; alo[p][i] = ap[1];
             }
     }
     int since_flush = 0;
     int origin = 0;                                      // ring slot of the current window's row 0
-    for (int it = it0; it < it1; ++it) {
+    // One item of kind kind_c (a std::integral_constant): a full item, the full item in front of a thin one (its look-ahead loads
+    // take the thin item's addresses), a thin item.  Three instantiations of this text, and the full items run in a loop of
+    // their own (below), which is the item loop of a plan without thin items: with the kinds as the arms of a branch inside one
+    // loop, hipcc no longer keeps the look-ahead loads in the registers of sets 0 and 1 and waits for them -- and for the window
+    // copy -- at the end of every item.
+    constexpr int kItemFull = 0, kItemBeforeThin = 1, kItemThin = 2;
+    auto item = [&](const int it, auto kind_c) {
+        constexpr bool thin = decltype(kind_c)::value == kItemThin, next_thin = decltype(kind_c)::value == kItemBeforeThin;
         const int oct = it / per_oct, reg = it - oct * per_oct, rx = reg / a.rq, ry = reg - rx * a.rq;
         // This wave's rows of the window were requested one item ago, before all of that item's A fragments; the newest eight
         // vector memory operations (the A fragments of this item's first two K steps) may stay in flight.  The barrier then
@@ -938,18 +999,27 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
         }
         // the RH new rows of the next item (the region below) into the slots of the previous window's first rows
         if (it + 1 < it1 && ry + 1 < a.rq) fill(oct, ry, rx, WR, kSdRH, origin);
-        int base[kSdAS][kSdGT];                          // LDS byte address of the unit's B column at K step 0
+        // LDS byte address of the unit's B column at K step 0; in a thin item: of K group 0's window row, j columns on
+        const unsigned jt = thin ? (unsigned)j : 0u;
+        int base[kSdAS][kSdGT];
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i)
 #pragma unroll
             for (int gg = 0; gg < kSdGT; ++gg)
-                base[i][gg] = (int)((((unsigned)origin + (uw[i][gg] & 15u)) & (kRing - 1)) * RB + (uw[i][gg] >> 4));
+                base[i][gg] = (int)((((unsigned)origin + (uw[i][gg] & 15u) - jt) & (kRing - 1)) * RB + (uw[i][gg] >> 4) + jt * PB);
 #ifdef DAU_SD_DIAG_AFIXED
         const size_t ioff = item_off(it0), ioff_next = ioff;
 #else
         const size_t ioff = item_off(it);
         const size_t ioff_next = item_off(it + 1 < it1 ? it + 1 : it);
 #endif
+        // lane terms of the look-ahead loads / of a thin item's own third load (the chunk's last item looks ahead at its own
+        // region, a dead load, as it did)
+        unsigned nadj = 0u, tadj = 0u;
+        if constexpr (next_thin) nadj = thin_adjust();
+        if constexpr (thin) tadj = thin_adjust();
+        constexpr size_t nstep = next_thin ? kThinStride : kSdAStride;
+        (void)nadj; (void)tadj;
         f4s part[kSdAS][kSdGT];
 #pragma unroll
         for (int i = 0; i < kSdAS; ++i)
@@ -960,10 +1030,13 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
         // while they run (sched barriers pin it).  The item is not unrolled whole: hipcc hoists loads of later steps until it
         // spills.
 #ifdef DAU_SD_DIAG_NOA
-#define SD_LOAD_A(P, i, an)
+#define SD_LOAD_INTO(AH, AL, i, an, ladj)
 #else
-#define SD_LOAD_A(P, i, an) { const h8* ap = a.xs + (an) + aoff[i]; ahi[P][i] = ap[0]; alo[P][i] = ap[1]; }
+#define SD_LOAD_INTO(AH, AL, i, an, ladj) { const h8* ap = a.xs + (an) + (aoff[i] + (ladj)); AH[i] = ap[0]; AL[i] = ap[1]; }
 #endif
+        // set P of channel i from the uniform offset `an`; SD_LOAD_NEXT: a look-ahead load of the next item (thin or not)
+#define SD_LOAD_A(P, i, an) SD_LOAD_INTO(ahi[P], alo[P], i, an, 0u)
+#define SD_LOAD_NEXT(P, i, an) SD_LOAD_INTO(ahi[P], alo[P], i, an, nadj)
 #define SD_READ_B(i, bh, bl)                                                                                    \
     _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
         const char* bp = lds + base[i][gg] + k * PB;                                                            \
@@ -989,14 +1062,71 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
         SD_GROUP(0, AH[0], AL[0], b0h, b0l, AFTER0)                                                             \
         SD_GROUP(1, AH[1], AL[1], b1h, b1l, AFTER1)                                                             \
     }
+        // bilinear combination of the four corners (lane-local), into the running sums
+        auto combine = [&]() {
+#pragma unroll
+            for (int i = 0; i < kSdAS; ++i)
+#pragma unroll
+                for (int gg = 0; gg < kSdGT; ++gg) {
+                    const int g = gb * kSdGT + gg;
+                    const bool ok = s_ok[i] && g < a.G && f_ok;
+                    const f4s p = part[i][gg], w = wb[i][gg];
+                    float v = w[0] * p[0];
+                    v = fmaf(w[1], p[1], v);
+                    v = fmaf(w[2], p[2], v);
+                    v = fmaf(w[3], p[3], v);
+                    run[i][gg] += ok ? v : 0.0f;
+                }
+        };
         static_assert(kSdAS == 2, "two groups per K step");
+        h8 aqh[kSdAS], aql[kSdAS];                       // the odd steps' fragments; a thin item's third fragment
+        if constexpr (thin) {
+#define SD_READ_BT(kk, i, bh, bl)                                                                                 \
+    _Pragma("unroll") for (int gg = 0; gg < kSdGT; ++gg) {                                                      \
+        const char* bp = lds + base[i][gg] + 4 * (kk) * PB - dead;                                               \
+        bh[gg] = *reinterpret_cast<const h8*>(bp);                                                              \
+        if constexpr (EL == 2) bl[gg] = *reinterpret_cast<const h8*>(bp + 256);                                 \
+    }
+            // K step kk of a thin item: columns 4 kk + j; a group whose column lies in the next region reads column 4 kk
+#define SD_THIN_STEP(kk, AH, AL, AFTER0, AFTER1)                                                                \
+    {                                                                                                           \
+        const int dead = 4 * (kk) + kSdRH <= RW || 4 * (kk) + j < RW ? 0 : j * PB;                              \
+        h8 bh[kSdGT], bl[kSdGT];                                                                                \
+        SD_READ_BT(kk, 0, bh, bl)                                                                               \
+        SD_GROUP(0, AH[0], AL[0], bh, bl, AFTER0)                                                               \
+        SD_READ_BT(kk, 1, bh, bl)                                                                               \
+        SD_GROUP(1, AH[1], AL[1], bh, bl, AFTER1)                                                               \
+    }
+#define SD_LOAD_THIRD(i) SD_LOAD_INTO(aqh, aql, i, ioff + (size_t)(2 * kThinStride), tadj)
+            SD_THIN_STEP(0, ahi[0], alo[0], SD_LOAD_THIRD(0) SD_LOAD_THIRD(1) SD_LOAD_NEXT(0, 0, ioff_next), SD_LOAD_NEXT(0, 1, ioff_next))
+            SD_THIN_STEP(1, ahi[1], alo[1], SD_LOAD_NEXT(1, 0, ioff_next + nstep), SD_LOAD_NEXT(1, 1, ioff_next + nstep))
+            if constexpr (4 * kThinSteps > RW) {
+                const bool live = 4 * (kThinSteps - 1) + j < RW;
+                const h8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int i = 0; i < kSdAS; ++i) { aqh[i] = live ? aqh[i] : zero; aql[i] = live ? aql[i] : zero; }
+            }
+            SD_THIN_STEP(2, aqh, aql, , )
+            combine();
+            // The look-ahead loads complete here, with no window copy in flight behind them: the next item then finds no load
+            // of this instantiation outstanding, and hipcc's waits in the full items stay those of a kernel without thin items
+            // (a wait it added there for a register loaded here would also drain the window copy, which it does not count).
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int i = 0; i < kSdAS; ++i) asm volatile("" : "+v"(ahi[p][i]), "+v"(alo[p][i]));
+#undef SD_LOAD_THIRD
+#undef SD_THIN_STEP
+#undef SD_READ_BT
+        } else {
 #ifdef DAU_SD_STEP_LOADS
         // K step kk with the A set of its parity P; the set then fetches step kk + 2 (of the next item past the last step)
 #define SD_STEP1(P, kk)                                                                                         \
     {                                                                                                           \
-        const size_t an = (kk) + 2 < RW ? ioff + (size_t)((kk) + 2) * 2 : ioff_next + (size_t)((kk) + 2 - RW) * 2; \
-        (void)an;                                                                                               \
-        SD_STEP(kk, ahi[P], alo[P], SD_LOAD_A(P, 0, an), SD_LOAD_A(P, 1, an))                                   \
+        const size_t an = (kk) + 2 < RW ? ioff + (size_t)((kk) + 2) * 2 : ioff_next + (size_t)((kk) + 2 - RW) * nstep; \
+        const unsigned la = (kk) + 2 < RW ? 0u : nadj;                                                          \
+        (void)an; (void)la;                                                                                     \
+        SD_STEP(kk, ahi[P], alo[P], SD_LOAD_INTO(ahi[P], alo[P], 0, an, la), SD_LOAD_INTO(ahi[P], alo[P], 1, an, la)) \
     }
 #pragma unroll 1
         for (int k2 = 0; k2 < RW; k2 += 2) {
@@ -1007,7 +1137,6 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
 #else
         // Pair r = K steps 2 r, 2 r + 1, its columns in set P.  Group i of the even step builds the odd step's fragment of
         // channel i from the two sets and then reloads set P with pair r + 2 of the item (r + 2 <= RW / 2).
-        h8 aqh[kSdAS], aql[kSdAS];
 #define SD_NEXT_COL(P, i)                                                                                       \
     aqh[i] = sd_next_col(ahi[P][i], ahi[1 - (P)][i], adx);                                                      \
     aql[i] = sd_next_col(alo[P][i], alo[1 - (P)][i], adx);
@@ -1021,8 +1150,8 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
         // the item's last pair: both sets are free once the odd step's fragment is built, and fetch pairs 0 and 1 of the next item
 #define SD_PAIR_LAST(P, rr)                                                                                     \
     {                                                                                                           \
-        SD_STEP(2 * (rr), ahi[P], alo[P], SD_NEXT_COL(P, 0) SD_LOAD_A(0, 0, ioff_next), SD_NEXT_COL(P, 1) SD_LOAD_A(0, 1, ioff_next)) \
-        SD_STEP(2 * (rr) + 1, aqh, aql, SD_LOAD_A(1, 0, ioff_next + 4), SD_LOAD_A(1, 1, ioff_next + 4))         \
+        SD_STEP(2 * (rr), ahi[P], alo[P], SD_NEXT_COL(P, 0) SD_LOAD_NEXT(0, 0, ioff_next), SD_NEXT_COL(P, 1) SD_LOAD_NEXT(0, 1, ioff_next)) \
+        SD_STEP(2 * (rr) + 1, aqh, aql, SD_LOAD_NEXT(1, 0, ioff_next + nstep), SD_LOAD_NEXT(1, 1, ioff_next + nstep)) \
     }
         constexpr int kPairs = RW / 2, kLoopPairs = (kPairs - 1) / 2 * 2;   // the loop takes two pairs (one per set) at a time
 #pragma unroll 1
@@ -1040,25 +1169,24 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
 #undef SD_PAIR
 #undef SD_PAIR_LAST
 #endif
+            combine();
+        }
+#undef SD_LOAD_NEXT
+#undef SD_LOAD_INTO
 #undef SD_READ_B
 #undef SD_GROUP
 #undef SD_LOAD_A
 #undef SD_STEP
-        // bilinear combination of the four corners (lane-local), into the running sums
-#pragma unroll
-        for (int i = 0; i < kSdAS; ++i)
-#pragma unroll
-            for (int gg = 0; gg < kSdGT; ++gg) {
-                const int g = gb * kSdGT + gg;
-                const bool ok = s_ok[i] && g < a.G && f_ok;
-                const f4s p = part[i][gg], w = wb[i][gg];
-                float v = w[0] * p[0];
-                v = fmaf(w[1], p[1], v);
-                v = fmaf(w[2], p[2], v);
-                v = fmaf(w[3], p[3], v);
-                run[i][gg] += ok ? v : 0.0f;
-            }
         if (++since_flush == kSdFlushItems) { flush(); since_flush = 0; }
+    };
+    // the chunk's items: runs of full items, each up to its strip's thin item (or to the chunk's end), and that item
+    for (int it = it0; it < it1;) {
+        const int run_end = a.thin ? min(it1, it + (a.rq - 1 - it % a.rq)) : it1;   // the strip's thin item, if the chunk reaches it
+        const int full_end = run_end < it1 ? run_end - 1 : run_end;
+#pragma unroll 1
+        for (; it < full_end; ++it) item(it, std::integral_constant<int, kItemFull>{});
+        if (it < run_end) { item(it, std::integral_constant<int, kItemBeforeThin>{}); ++it; }
+        if (it < it1) { item(it, std::integral_constant<int, kItemThin>{}); ++it; }
     }
     // the last item's look-ahead (a dead load) completes before any register is reused
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1156,6 +1284,11 @@ bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* c
 }
 
 size_t split_dot_workspace_bytes(const SplitDotConfig& c) { return sd_layout(c, sd_geom(c)).total; }
+
+void split_dot_strip(const SplitDotConfig& c, int* items, int* k_steps) {
+    const SdGeom g = sd_geom(c);
+    *items = g.rq; *k_steps = g.strip_steps;
+}
 
 void split_dot_init(const SplitDotConfig& c) {
     dispatch_sd(c.RW, c.e_limbs, nullptr, nullptr, 0);
@@ -1255,6 +1388,7 @@ void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table
     a.S = s.S; a.F = s.F; a.G = s.G;
     a.nfb = g.nfb; a.nsb = g.nsb; a.ngb = g.ngb; a.per = g.per; a.items = g.items; a.rq = g.rq; a.cq = g.cq;
     a.XTr = g.XTr; a.XTc = g.XTc; a.EYs = g.EYs; a.EXs = g.EXs;
+    a.thin = g.thin;
     a.guard = guard;
     dispatch_sd(c.RW, c.e_limbs, st, &a, g.chunks * g.nfb * g.nsb * g.ngb);
     launch_dot_reduce(st, a.partial, 1, (long)kNumK * s.S * s.G * s.F, s.G, s.F, s.G, g.chunks, g.chunks, s.G, false, r4, guard);

@@ -94,6 +94,8 @@ def _load():
         lib.dau_conv_gather_outlier_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "dau_conv_gather_line_status"):      # (likewise: the line members' query)
         lib.dau_conv_gather_line_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "dau_conv_split_dot_geometry"):      # (likewise: the split gather-dot's strip geometry)
+        lib.dau_conv_split_dot_geometry.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 3
     if hasattr(lib, "dau_conv_forward_epilogue"):        # (likewise: the fused epilogue and its backward pass)
         lib.dau_conv_epilogue_supported.argtypes = [vp, ctypes.c_int]
         lib.dau_conv_forward_epilogue.argtypes = [vp, vp, fp, fp, fp, fp, fp, fp, ctypes.c_int, fp, vp, ctypes.c_size_t]
@@ -375,6 +377,14 @@ class Plan(object):
         with torch.cuda.device(dev):
             _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, bool(taken.value)
+
+    def split_dot_geometry(self):
+        """-> (region_width, strip_items, strip_k_steps) of the two-limb f16 parameter-gradient kernel: the K steps of a full item,
+        the items of one column strip and the K steps the kernel runs for a strip (a strip's last item takes ceil(region_width / 4)
+        where (H + 1) % 4 == 1); zeros for a plan without that kernel.  No device needed."""
+        v = [ctypes.c_int32() for _ in range(3)]
+        _check(lib.dau_conv_split_dot_geometry(self._h, *[ctypes.byref(c) for c in v]))
+        return tuple(c.value for c in v)
 
     def line_status(self):
         """Sync; -> (off_line_units, line_radius_taken) of the last call: the units of its gather-sum table that do not lie on the row

@@ -320,6 +320,11 @@ DAU_API int dau_conv_plan_create(const dau_conv_desc *desc, dau_conv_plan **plan
 DAU_API int dau_conv_plan_destroy(dau_conv_plan *plan);
 DAU_API int dau_conv_plan_get_info(const dau_conv_plan *plan, dau_conv_plan_info *info);
 DAU_API int dau_conv_workspace_bytes(const dau_conv_plan *plan, int pass, size_t *bytes_out);
+/* Geometry of the two-limb f16 parameter-gradient kernel (k_split_dot.hip) of a plan that holds it: the region width (columns of a
+ * region = K steps of a full item: 10 or 12), the regions (items) of one column strip and the K steps the kernel runs for a strip --
+ * region_width per item, ceil(region_width / 4) for a strip's last item where (H + 1) % 4 == 1 leaves it one real row.  All three are 0
+ * for a plan without that kernel.  Needs no device.  Any pointer may be NULL. */
+DAU_API int dau_conv_split_dot_geometry(const dau_conv_plan *plan, int32_t *region_width, int32_t *strip_items, int32_t *strip_k_steps);
 
 /* stream is a hipStream_t (NULL = default stream).  All pointers are device pointers. */
 DAU_API int dau_conv_forward(const dau_conv_plan *plan, void *stream, const float *x, const float *w,
