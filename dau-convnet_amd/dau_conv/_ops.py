@@ -1,7 +1,12 @@
 """The DAU operator as two opaque PyTorch ops, `dau_conv::conv` and `dau_conv::conv_backward` (torch.library.custom_op), so that a
 layer can sit inside `torch.compile`: Dynamo sees one op with a shape function, and everything that depends on the plan -- the plan
 cache, the library's refusals and the fallbacks they select, the offset status, the host copy of sigma -- happens at run time inside
-the op's implementation, where the tensors are real.  The eager layer does not come through here (dau_conv.py: _DAUConvFunction).
+the op's implementation, where the tensors are real.  The forward and the backward over a plan are dau_conv.py's _forward / _backward,
+the core the eager layer's _DAUConvFunction runs as well (eager calls it directly, never through these ops: no dispatcher cost, and the
+two promise rules below are the ops' alone).  What the implementations here add around that core: sigma tiled and its host copy kept
+(_tiled, _sigma_hint); what a plan does not fuse -- `+ bias`, `+ residual`, ReLU, the ReLU in front -- applied in torch inside the op,
+forward and backward, where eager leaves it to torch's autograd outside its function; the result brought to the shape function's
+promise (_promised); grad cast to x's dtype; 0-element tensors for the gradients not asked for.
 
     conv(x, w, mu1, mu2, sigma, bias?, residual?, relu, input_relu, ...settings...) -> y
         y = act((DAU(relu?(x)) + bias[f]) + residual): what dau_conv() computes for these arguments.  w, mu1, mu2 [1,S,G,F]; sigma
@@ -149,34 +154,23 @@ def conv(x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, bias: Op
     nhwc = _impl._wants_nhwc(x, st)
     w, mu1, mu2 = (_impl._c(_impl._f32(t)) for t in (w, mu1, mu2))
     sigma = _tiled(sigma, w)
-    if bias is not None and tuple(bias.shape) != (w.shape[-1],):
-        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), w.shape[-1]))
-    if residual is not None and tuple(residual.shape) != (x.shape[0], w.shape[-1]) + tuple(x.shape[2:]):
+    _impl._check_bias(bias, w)
+    if residual is not None and not _impl._residual_fusable(residual, x, w):
         raise _capi.InvalidArgumentError("dau_conv::conv: the residual must have the input's dtype and the output's shape")
     plan = _impl._get_plan(x, w, st, nhwc)
     if input_relu and not plan.input_relu:
         x = torch.relu(x)                    # the plan cannot take the flag (direct kernels, dense_bf16): the ReLU in front
-    xin = _impl._act(x, plan)
-    _impl._check_before(plan, st["check_offsets"])
-    epilogue = bias is not None or relu or residual is not None
-    if not epilogue:
-        y = plan.forward(xin, w, mu1, mu2, sigma)
-    elif _impl._epilogue_ok(plan):
-        fbias = None if bias is None else _impl._c(_impl._f32(bias))
-        if residual is not None:
-            y = plan.forward(xin, w, mu1, mu2, sigma, bias=fbias, relu=relu, residual=_impl._act(residual, plan))
-        else:
-            y = plan.forward(xin, w, mu1, mu2, sigma, bias=fbias, relu=relu)
+    if not (bias is not None or relu or residual is not None) or _impl._epilogue_ok(plan):
+        y = _impl._forward(plan, st, x, w, mu1, mu2, sigma, None if bias is None else _impl._c(_impl._f32(bias)), relu, residual)[0]
     else:
         # no fused epilogue: the op, then `+ bias`, `+ residual` and relu in torch, in dau_conv()'s order
-        y = plan.forward(xin, w, mu1, mu2, sigma)
+        y = _impl._forward(plan, st, x, w, mu1, mu2, sigma)[0]
         if bias is not None:
             y = y + bias.reshape(1, -1, 1, 1)
         if residual is not None:
             y = y + residual
         if relu:
             y = torch.relu(y)
-    _impl._check_after(plan, st["check_offsets"])
     return _promised(y, nhwc, x.dtype)
 
 
@@ -211,29 +205,19 @@ def conv_backward(grad: Tensor, x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, 
     relu_in_front = input_relu and not plan.input_relu
     if relu_in_front:
         x = torch.relu(x)
-    xin = _impl._act(x, plan)
     none = lambda like, dtype=torch.float32: torch.empty((0,), dtype=dtype, device=like.device)
     need = int(need_mask) & _capi.NEED_ALL
     if need == 0 and not need_dbias:
         return (none(x, x.dtype),) + (none(x),) * 5
-    _impl._check_before(plan, st["check_offsets"])
     grad = _impl._act(grad if grad.dtype == x.dtype else grad.to(x.dtype), plan)
-    dbias = None
-    if need_dbias or (relu and need):
-        if _impl._epilogue_ok(plan):
-            # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient
-            dz, dbias = plan.epilogue_backward(grad, _impl._act(y, plan) if relu else None, relu=relu, need_dbias=need_dbias)
-            if dz is not None:
-                grad = dz
-        else:
-            if relu:
-                grad = torch.where(_impl._act(y, plan) <= 0, torch.zeros((), dtype=grad.dtype, device=grad.device), grad)
-            if need_dbias:
-                dbias = grad.sum_to_size(1, grad.shape[1], 1, 1).reshape(-1).float()
-    out = (None,) * 5
-    if need:
-        out = plan.backward(xin, grad, w, mu1, mu2, sigma, need)
-        _impl._check_after(plan, st["check_offsets"])
+    if (need_dbias or relu) and not _impl._epilogue_ok(plan):
+        # no fused epilogue: its backward in torch -- the select threshold_backward makes, the sum `+ bias`'s autograd makes
+        if relu:
+            grad = torch.where(_impl._act(y, plan) <= 0, torch.zeros((), dtype=grad.dtype, device=grad.device), grad)
+        dbias = grad.sum_to_size(1, grad.shape[1], 1, 1).reshape(-1).float() if need_dbias else None
+        out = _impl._backward(plan, st, _impl._act(x, plan), grad, w, mu1, mu2, sigma, need)[2]
+    else:
+        _, dbias, out = _impl._backward(plan, st, _impl._act(x, plan), grad, w, mu1, mu2, sigma, need, y, relu, need_dbias)
     dx = out[0]
     if dx is not None:
         if relu_in_front:
@@ -269,11 +253,7 @@ def _setup_context(ctx, inputs, output):
     # the raw input (an input_relu call's ReLU output is never materialised, nor saved) and y only for the ReLU mask
     ctx.save_for_backward(*((x, w, mu1, mu2, sigma) + ((output,) if relu else ())))
     ctx.relu, ctx.input_relu, ctx.settings = bool(relu), bool(input_relu), tuple(inputs[9:])
-    need = 0
-    for i, bit in enumerate((_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
-        if ctx.needs_input_grad[i]:
-            need |= bit
-    ctx.need = need
+    ctx.need = _impl._need_mask(ctx.needs_input_grad)
     ctx.need_dbias = bias is not None and bool(ctx.needs_input_grad[5])
     ctx.need_dres = residual is not None and bool(ctx.needs_input_grad[6])
     ctx.param_dtypes = tuple(t.dtype for t in (w, mu1, mu2, sigma))

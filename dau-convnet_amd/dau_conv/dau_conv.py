@@ -8,7 +8,10 @@ argument / variable names and defaults) on top of the C ABI in include/dau_conv.
     dau_conv_op_module.dau_conv  (:212-219)     dau_conv(...)        raw op, TF attr names
     dau_conv_grad_module.dau_conv_grad          dau_conv_grad(...)   raw grad op
       (_dau_conv_grad_op.py:40-60)
-    @ops.RegisterGradient("DAUConv") (:14)      _DAUConvFunction (torch.autograd.Function)
+    @ops.RegisterGradient("DAUConv") (:14)      _DAUConvFunction (torch.autograd.Function); under torch.compile the op
+                                                torch.ops.dau_conv.conv (_ops.py).  Both run the one core, _forward / _backward
+                                                below (layouts, offset checks, the plan's passes); what a plan does not fuse,
+                                                eager applies in torch around the function, the op inside itself
     DAUGridMean (:24-74), ZeroNLast (:76-110)   same names (initializers)
     _DAUConvolution2d (:113-219)                same name
     DAUConv2d (:221-555), DAUConv1d (:557-570)  same names (torch.nn.Module)
@@ -90,16 +93,36 @@ def _get_plan(x, w, settings, nhwc=False):
     return _get_plan_with(x, w, settings, nhwc, 0)
 
 
-def _get_plan_with(x, w, settings, nhwc, extra_flags):
-    N, S, H, W = x.shape
-    _, S2, G, F = w.shape
-    if S2 != S:
-        raise _capi.InvalidArgumentError("weights dim 1 (%d) must equal the input channels (%d)" % (S2, S))
-    if F != settings["num_output"]:
+def _check_activations(activation, input_activation):
+    for prefix, value in (("", activation), ("input_", input_activation)):
+        if value not in (None, "relu"):
+            raise _capi.InvalidArgumentError(prefix + "activation must be None or \"relu\"")
+
+
+def _check_weights(x, w, settings):
+    if w.shape[1] != x.shape[1]:
+        raise _capi.InvalidArgumentError("weights dim 1 (%d) must equal the input channels (%d)" % (w.shape[1], x.shape[1]))
+    if w.shape[-1] != settings["num_output"]:
         # shape function of the op: last dim of every parameter == num_output (dau_conv_op.cpp:62-76)
-        raise _capi.InvalidArgumentError("last dim of weights (%d) must equal num_output (%d)" % (F, settings["num_output"]))
+        raise _capi.InvalidArgumentError("last dim of weights (%d) must equal num_output (%d)" % (w.shape[-1], settings["num_output"]))
     if settings["stride"] != 1:
         raise _capi.InvalidArgumentError("DAUConv: only stride=1 is supported")  # base_dau_conv_layer.cpp:68-69
+
+
+def _check_bias(bias, w):
+    if bias is not None and tuple(bias.shape) != (w.shape[-1],):
+        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), w.shape[-1]))
+
+
+def _residual_fusable(residual, x, w):
+    """A residual the store can add: the input's dtype and exactly the output's shape (any other is added in torch)."""
+    return residual.dtype == x.dtype and tuple(residual.shape) == (x.shape[0], w.shape[-1]) + tuple(x.shape[2:])
+
+
+def _get_plan_with(x, w, settings, nhwc, extra_flags):
+    N, S, H, W = x.shape
+    _, _, G, F = w.shape
+    _check_weights(x, w, settings)
     flags = extra_flags
     if settings["use_interpolation"]:
         flags |= _capi.FLAG_USE_INTERPOLATION
@@ -248,31 +271,63 @@ def dau_conv_grad(grad, input, weights, mu1, mu2, sigma, need_mask=_capi.NEED_AL
     """DAUConvGrad op -> (grad_input, grad_weights, grad_mu1, grad_mu2, grad_sigma).  The parameter gradients are float32."""
     attrs.setdefault("component_border_bound", 0.0)  # the only default that differs (dau_conv_grad_op.cpp:37)
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
-    st = _settings(sigma, **attrs)
+    st = dict(_settings(sigma, **attrs), process_group=None)     # (the raw grad op is local: process_group= is the layer's)
     plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
+    return _backward(plan, st, _act(input, plan), grad, _c(weights), _c(mu1), _c(mu2), _c(sigma), need_mask)[2]
+
+
+# The one forward / backward over a plan: eager (_DAUConvFunction, dau_conv_grad) and the torch.compile ops (_ops.conv,
+# _ops.conv_backward) both run these two; what a caller adds is what its side alone needs (see each).
+def _forward(plan, st, input, weights, mu1, mu2, sigma, bias=None, relu=False, residual=None):
+    """-> (y, the input as the plan took it: what backward wants back).  bias / relu / residual: the epilogue fused into the store
+    -- the caller has asked _epilogue_ok(plan); the parameters and the bias contiguous float32."""
+    # a channels_last input runs the NHWC plan where there is one: no copy of x, y channels_last
+    input = _act(input, plan)
+    if residual is not None:
+        residual = _act(residual, plan)
     _check_before(plan, st["check_offsets"])
-    out = plan.backward(_act(input, plan), _act(grad, plan), _c(weights), _c(mu1), _c(mu2), _c(sigma), need_mask)
+    y = plan.forward(input, weights, mu1, mu2, sigma, bias=bias, relu=relu, residual=residual)
     _check_after(plan, st["check_offsets"])
-    return out
+    return y, input
+
+
+def _need_mask(needs_input_grad):
+    """The _capi.NEED_* bits of an autograd context whose first five inputs are (input, weights, mu1, mu2, sigma)."""
+    bits = (_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)
+    return sum(bit for bit, wanted in zip(bits, needs_input_grad) if wanted)
+
+
+def _backward(plan, st, input, grad, weights, mu1, mu2, sigma, need, y=None, relu=False, need_dbias=False):
+    """-> (the gradient of the sum, dbias, (dx, dw, dmu1, dmu2, dsigma)), for a caller that wants at least one of them.  input as
+    _forward returned it; relu / need_dbias: backward of the fused epilogue, from the forward's y.  The residual joins the sum
+    before the activation, so its gradient IS the first result (dz, or grad in the plan's layout without a ReLU)."""
+    _check_before(plan, st["check_offsets"])
+    grad = _act(grad, plan)
+    dbias = None
+    if need_dbias or relu:
+        # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient (local: it is not exchanged)
+        dz, dbias = plan.epilogue_backward(grad, _act(y, plan) if relu else None, relu=relu, need_dbias=need_dbias)
+        if dz is not None:
+            grad = dz
+    if need == 0:
+        return grad, dbias, (None,) * 5
+    group = st["process_group"]
+    if group is not None and need & ~_capi.NEED_DX and _group_size(group) > 1:
+        out = _data_parallel_backward(plan, input, grad, weights, mu1, mu2, sigma, need, group, st["grad_reduce"])
+    else:
+        out = plan.backward(input, grad, weights, mu1, mu2, sigma, need)
+    _check_after(plan, st["check_offsets"])
+    return grad, dbias, out
 
 
 class _DAUConvFunction(torch.autograd.Function):
+    """Eager's caller of _forward / _backward; what the plan does not fuse, dau_conv() applies in torch around this function."""
     @staticmethod
     def forward(ctx, input, weights, mu1, mu2, sigma, st, bias=None, relu=False, residual=None):
         weights, mu1, mu2, sigma = _c(weights), _c(mu1), _c(mu2), _c(sigma)
-        # a channels_last input runs the NHWC plan where there is one: no copy of x (it is saved as it is), y channels_last
         plan = _get_plan(input, weights, st, _wants_nhwc(input, st))
-        input = _act(input, plan)
-        _check_before(plan, st["check_offsets"])
-        # bias / residual / relu: the epilogue fused into the store (dau_conv() asks the plan first); y is then saved for the ReLU mask
-        if residual is not None:
-            y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu,
-                             residual=_act(residual, plan))
-        else:
-            y = plan.forward(input, weights, mu1, mu2, sigma, bias=None if bias is None else _c(bias), relu=relu) \
-                if (bias is not None or relu) else plan.forward(input, weights, mu1, mu2, sigma)
-        _check_after(plan, st["check_offsets"])
-        # (an input_relu plan: `input` is the raw tensor -- the ReLU's output is never materialised, nor saved)
+        y, input = _forward(plan, st, input, weights, mu1, mu2, sigma, None if bias is None else _c(bias), relu, residual)
+        # (an input_relu plan: `input` is the raw tensor -- the ReLU's output is never materialised, nor saved); y for the ReLU mask
         ctx.save_for_backward(*((input, weights, mu1, mu2, sigma) + ((y,) if relu else ())))
         ctx.plan, ctx.st, ctx.relu = plan, st, bool(relu)
         return y
@@ -281,36 +336,14 @@ class _DAUConvFunction(torch.autograd.Function):
     def backward(ctx, grad):
         input, weights, mu1, mu2, sigma = ctx.saved_tensors[:5]
         y = ctx.saved_tensors[5] if ctx.relu else None
-        need = 0
-        for i, bit in enumerate((_capi.NEED_DX, _capi.NEED_DW, _capi.NEED_DMU1, _capi.NEED_DMU2, _capi.NEED_DSIGMA)):
-            if ctx.needs_input_grad[i]:
-                need |= bit
+        need = _need_mask(ctx.needs_input_grad)
         n_in = len(ctx.needs_input_grad)             # 6, 8 with (bias, relu), 9 with the residual
         need_dbias = n_in > 6 and ctx.needs_input_grad[6]
         need_dres = n_in > 8 and ctx.needs_input_grad[8]
         if need == 0 and not need_dbias and not need_dres:
             return (None,) * n_in
-        _check_before(ctx.plan, ctx.st["check_offsets"])
-        grad = _act(grad, ctx.plan)
-        dbias = None
-        if need_dbias or (ctx.relu and (need or need_dres)):
-            # one pass: the gradient of the sum, dz = (y <= 0) ? 0 : grad, and the bias gradient (local: it is not exchanged)
-            dz, dbias = ctx.plan.epilogue_backward(grad, y, relu=ctx.relu, need_dbias=need_dbias)
-            if dz is not None:
-                grad = dz
-        # the residual joins the sum before the activation: its gradient IS the gradient of the sum (dz, or grad without a ReLU)
-        dres = grad if need_dres else None
-        if need == 0:
-            return ((None,) * 6 + (dbias, None, dres))[:n_in]
-        group = ctx.st["process_group"]
-        param_need = need & ~_capi.NEED_DX
-        if group is not None and param_need and _group_size(group) > 1:
-            out = _data_parallel_backward(ctx.plan, input, grad, weights, mu1, mu2, sigma, need, group,
-                                          ctx.st["grad_reduce"])
-        else:
-            out = ctx.plan.backward(input, grad, weights, mu1, mu2, sigma, need)
-        _check_after(ctx.plan, ctx.st["check_offsets"])
-        return (out + (None, dbias, None, dres))[:n_in]
+        dsum, dbias, out = _backward(ctx.plan, ctx.st, input, grad, weights, mu1, mu2, sigma, need, y, ctx.relu, need_dbias)
+        return (out + (None, dbias, None, dsum if need_dres else None))[:n_in]
 
 
 def _group_size(group):
@@ -380,34 +413,30 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
     makes these decisions at run time and reads sigma itself (a sigma_hint= is ignored there); process_group= calls leave the graph."""
     if torch.compiler.is_compiling():
         return _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, activation, residual, input_activation, attrs)
-    if activation not in (None, "relu"):
-        raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
-    if input_activation not in (None, "relu"):
-        raise _capi.InvalidArgumentError("input_activation must be None or \"relu\"")
+    _check_activations(activation, input_activation)
     if input_activation == "relu":
         ok, hint = _input_relu_ok(input, weights, sigma, attrs)
         attrs = dict(attrs, sigma_hint=hint)
         if not ok:
             return dau_conv(torch.relu(input), weights, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual, **attrs)
-    if residual is not None:
-        out_shape = (input.shape[0], weights.shape[-1]) + tuple(input.shape[2:])
-        if not (residual.dtype == input.dtype and tuple(residual.shape) == out_shape):
-            out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, input_activation=input_activation, **attrs) + residual
-            return torch.relu(out) if activation == "relu" else out
+
+    def residual_in_torch():
+        out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, input_activation=input_activation, **attrs) + residual
+        return torch.relu(out) if activation == "relu" else out
+    if residual is not None and not _residual_fusable(residual, input, weights):
+        return residual_in_torch()
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
     if input_activation == "relu":
         st["input_relu"] = True          # part of the plan key (_get_plan): the plan takes the raw input
     if bias is None and activation is None and residual is None:
         return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
-    if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
-        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), weights.shape[-1]))
+    _check_bias(bias, weights)
     if _epilogue_ok(_get_plan(input, weights, st, _wants_nhwc(input, st))):
         args = (input, weights, mu1, mu2, sigma, st, None if bias is None else _f32(bias), activation == "relu")
         return _DAUConvFunction.apply(*(args if residual is None else args + (residual,)))
     if residual is not None:
-        out = dau_conv(input, weights, mu1, mu2, sigma, bias=bias, input_activation=input_activation, **attrs) + residual
-        return torch.relu(out) if activation == "relu" else out
+        return residual_in_torch()
     out = _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     if bias is not None:
         out = out + bias.reshape(1, -1, 1, 1)
@@ -420,24 +449,13 @@ def _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, activation, residu
         # the overlapped all-reduce of _data_parallel_backward is not an op: today's function, outside the graph (one graph break)
         return _ops.process_group_eager()(dau_conv, input, weights, mu1, mu2, sigma, bias=bias, activation=activation,
                                           residual=residual, input_activation=input_activation, **attrs)
-    if activation not in (None, "relu"):
-        raise _capi.InvalidArgumentError("activation must be None or \"relu\"")
-    if input_activation not in (None, "relu"):
-        raise _capi.InvalidArgumentError("input_activation must be None or \"relu\"")
-    if residual is not None:
-        out_shape = (input.shape[0], weights.shape[-1]) + tuple(input.shape[2:])
-        if not (residual.dtype == input.dtype and tuple(residual.shape) == out_shape):
-            out = _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, None, None, input_activation, attrs) + residual
-            return torch.relu(out) if activation == "relu" else out
+    _check_activations(activation, input_activation)
+    if residual is not None and not _residual_fusable(residual, input, weights):
+        out = _dau_conv_compiled(input, weights, mu1, mu2, sigma, bias, None, None, input_activation, attrs) + residual
+        return torch.relu(out) if activation == "relu" else out
     st = _settings(sigma, **dict(attrs, sigma_hint=0.0))     # (a placeholder: sigma is not read while tracing)
-    if weights.shape[1] != input.shape[1]:
-        raise _capi.InvalidArgumentError("weights dim 1 (%d) must equal the input channels (%d)" % (weights.shape[1], input.shape[1]))
-    if weights.shape[-1] != st["num_output"]:
-        raise _capi.InvalidArgumentError("last dim of weights (%d) must equal num_output (%d)" % (weights.shape[-1], st["num_output"]))
-    if st["stride"] != 1:
-        raise _capi.InvalidArgumentError("DAUConv: only stride=1 is supported")
-    if bias is not None and tuple(bias.shape) != (weights.shape[-1],):
-        raise _capi.InvalidArgumentError("bias has shape %s, expected (%d,)" % (tuple(bias.shape), weights.shape[-1]))
+    _check_weights(input, weights, st)
+    _check_bias(bias, weights)
     return torch.ops.dau_conv.conv(input, weights, mu1, mu2, sigma, bias, residual, activation == "relu", input_activation == "relu",
                                    *_ops.encode_settings(st))
 

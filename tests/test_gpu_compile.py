@@ -51,13 +51,13 @@ def _data(seed=3, S=S, F=F, H=H, W=W, out_hw=None, dtype=torch.float32, channels
     return x, dy, r
 
 
-def _step(fn, layer, x, dy, residual=None, autocast=None):
+def _step(fn, layer, x, dy, residual=None, autocast=None, x_grad=True, residual_grad=True):
     for p in layer.parameters():
         p.grad = None
-    x = x.detach().clone(memory_format=torch.preserve_format).requires_grad_(True)
+    x = x.detach().clone(memory_format=torch.preserve_format).requires_grad_(x_grad)
     args = (x,)
     if residual is not None:
-        residual = residual.detach().clone(memory_format=torch.preserve_format).requires_grad_(True)
+        residual = residual.detach().clone(memory_format=torch.preserve_format).requires_grad_(residual_grad)
         args = (x, residual)
     with torch.autocast("cuda", dtype=autocast, enabled=autocast is not None):
         y = fn(*args)
@@ -311,6 +311,67 @@ def test_dense_bf16_fallbacks_inside_the_op():
     # exactly what the shape function promised: bfloat16, contiguous (DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16)
     assert y1.dtype == torch.bfloat16 and y1.stride() == (32 * 256, 256, 16, 1)
     assert dx1.dtype == torch.bfloat16 and dx1.shape == x.shape
+
+
+@pytest.mark.parametrize("with_residual", [False, True], ids=["bias_relu", "bias_relu_residual"])
+def test_direct_kernel_fallbacks_inside_the_op(with_residual):
+    """algo=ALGO_DIRECT on a float32 channels_last input: the direct kernels have no fused epilogue, no NHWC plan and no input-ReLU
+    flag -- the op applies all three in torch, on eager's bits (float32: torch's promotion changes nothing).  The one difference is
+    the documented one: eager's output is contiguous, the op's output and input gradient are channels_last, as its shape function
+    promised."""
+    import importlib
+    from dau_conv import _capi
+    impl = importlib.import_module("dau_conv.dau_conv")
+    before = set(impl._PLANS)
+    eager, twin, compiled = _pair(algo=_capi.ALGO_DIRECT, fused_epilogue=True, activation=torch.relu, input_activation="relu",
+                                  use_bias=True)
+    x, dy, r = _data(channels_last=True)
+    assert 0.2 < float((x <= 0).float().mean()) < 0.8
+    call = (lambda m: lambda a, b: m(a, residual=b)) if with_residual else (lambda m: m)
+    y0, dx0, g0, dr0 = _step(call(eager), eager, x, dy, r if with_residual else None)
+    y1, dx1, g1, dr1 = _step(call(compiled), twin, x, dy, r if with_residual else None)
+    plans = [p for k, p in impl._PLANS.items() if k not in before]
+    assert plans and all(p.info["algo_forward"] == _capi.ALGO_DIRECT and p.info["algo_backward"] == _capi.ALGO_DIRECT
+                         and p.io_layout == "NCHW" and not p.input_relu and not impl._epilogue_ok(p) for p in plans)
+    _same(y1.contiguous(), y0.contiguous(), "y")
+    assert 0.1 < float((y1 == 0).float().mean()) < 0.9
+    _same(dx1.contiguous(), dx0.contiguous(), "x.grad")
+    assert set(g0) == set(g1) == {"weights", "mu1", "mu2", "sigma", "bias"}
+    for name in ("weights", "mu1", "mu2", "bias"):
+        _same(g1[name], g0[name], name + ".grad")
+        assert bool((g1[name] != 0).any()), name
+    assert g0["sigma"] is None and g1["sigma"] is None
+    if with_residual:
+        _same(dr1.contiguous(), dr0.contiguous(), "residual.grad")
+    # the two promises: eager lets the NCHW plan's layout through, the op keeps what its shape function said of a channels_last x
+    assert y0.is_contiguous()
+    for t in (y1, dx1):
+        assert t.is_contiguous(memory_format=torch.channels_last) and not t.is_contiguous()
+
+
+@pytest.mark.parametrize("wanted", ["bias_and_residual", "residual", "x"])
+def test_gradient_subsets_of_the_fused_epilogue(wanted):
+    """backward's branches when only some gradients are asked for, fused bias + residual + ReLU: (a) need == 0 with the bias and the
+    residual gradient wanted, (b) the residual's gradient alone (the masked grad, no DAU pass), (c) the input gradient alone"""
+    eager, twin, compiled = _pair(fused_epilogue=True, activation=torch.relu)
+    for layer in (eager, twin):
+        for name, p in layer.named_parameters():
+            p.requires_grad_(name == "bias" and wanted == "bias_and_residual")
+    x, dy, r = _data()
+    kw = dict(x_grad=wanted == "x", residual_grad=wanted != "x")
+    y0, dx0, g0, dr0 = _step(lambda a, b: eager(a, residual=b), eager, x, dy, r, **kw)
+    y1, dx1, g1, dr1 = _step(lambda a, b: compiled(a, residual=b), twin, x, dy, r, **kw)
+    _same(y1, y0, "y")
+    assert y1.stride() == y0.stride()
+    assert 0.1 < float((y1 == 0).float().mean()) < 0.9
+    got = dict(g1, x=dx1, residual=dr1)
+    want = dict(g0, x=dx0, residual=dr0)
+    asked = {"bias_and_residual": {"bias", "residual"}, "residual": {"residual"}, "x": {"x"}}[wanted]
+    assert {n for n, t in got.items() if t is not None} == {n for n, t in want.items() if t is not None} == asked
+    for name in asked:
+        _same(got[name], want[name], name + ".grad")
+        assert got[name].stride() == want[name].stride(), name
+        assert bool((got[name] != 0).any()), name
 
 
 # ----------------------------------------------------------------------------------------------
