@@ -216,6 +216,11 @@ struct Status {
     // (oy != 0 or a weight on the row below that is not zero -- a NaN counts; ignored units count too), counted by
     // prepare_units_kernel.  line[1]: the radius of the line member that ran the pass (written by its scales kernel), 0 if none did.
     unsigned int line[2];
+    // DAU_FLAG_SPLIT_DOT_LINE (dau_conv_dot_line_status).  pad2[0]: the units of the call's bare parameter-gradient table that do
+    // not lie on the row of their pixel, counted by the prepare_units_kernel of that pass -- which counts them into line[0] too,
+    // where the guards read the count; the pass puts line[0] back to zero behind itself, so that after a backward call line[0] is
+    // the count of the input-gradient table alone.  pad2[1]: the radius of the line member of the gather-dot that ran the pass
+    // (written by its dy maxima kernel), 0 if none did.
     unsigned int pad2[2];
 };
 constexpr unsigned kRingTakenBit = 0x80000000u;
@@ -240,7 +245,7 @@ struct Guard {
     float lo, hi;
     unsigned cnt_lo = 0u, cnt_hi = 0xffffffffu;
     float cnt_upto = INFINITY;
-    // DAU_FLAG_DENSE_SPLIT_LINE (Status.line[0], the units off the line).  +R: a line member, runs only where that count is 0.
+    // DAU_FLAG_DENSE_SPLIT_LINE, DAU_FLAG_SPLIT_DOT_LINE (Status.line[0], the units off the line of the pass's table).  +R: a line member, runs only where that count is 0.
     // -R: a member that shares offsets within +-R with a line member, runs there only where the count is not 0.  0: any.
     // Kernels only READ the status block through their guard, with one exception: the scales kernel of a line member whose guard
     // has passed writes its radius to Status::line[1] (k_dense_split.hip, split_scales_kernel under DAU_SPLIT_1D).
@@ -274,10 +279,12 @@ void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k,
 // k_units.hip
 // host_status (may be null): pinned host copy of the status block, written by the last workgroup to finish
 // count_ignore: the units left out of the status block's outlier count (-1: `ignore`; the input-gradient table ignores no unit)
-// line_status (may be null; DAU_FLAG_DENSE_SPLIT_LINE): the status block whose line[0] takes the count of this table's units off the line
+// line_status (may be null; DAU_FLAG_DENSE_SPLIT_LINE / DAU_FLAG_SPLIT_DOT_LINE): the status block whose line[0] takes the count of this
+// table's units off the line; line_dot: the table of the parameter-gradient pass, whose count goes to pad2[0] as well
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
-                          Status* status, HostStatus* host_status, int count_ignore = -1, Status* line_status = nullptr);
+                          Status* status, HostStatus* host_status, int count_ignore = -1, Status* line_status = nullptr,
+                          bool line_dot = false);
 void launch_finalize_grads(hipStream_t st, const float* r4, const float* w, Shape sh, int ignore, float lr,
                            int need_mask, bool single_dim, float* dw, float* dmu1, float* dmu2, float* dsigma);
 // k_direct.hip  (DAU_ALGO_DIRECT: plain kernels, any shape)

@@ -84,19 +84,21 @@ enum Member {
     kLine4, kLine8,              // ... its line forms, one row of 9 / 17 taps (DAU_FLAG_DENSE_SPLIT_LINE: calls whose units lie on a line)
     kBf16R3, kBf16R4,            // ... the densified bf16 implicit GEMM of radius 3 / 4 (k_dense_bf16.hip; DAU_FLAG_DENSE_BF16)
     kTiledDot,                   // parameter gradients: the exact tiled gather-dot
+    kDotLine4, kDotLine8,        // ... the line forms of the next, horizontal radius 4 / 8 (DAU_FLAG_SPLIT_DOT_LINE: calls whose units lie on a line)
     kSplitDot,                   // ... the two-limb f16 GEMM with the bilinear corners as rows (k_split_dot.hip: fp32 accuracy)
     kWgradR3, kWgradR4,          // ... the bf16 dense correlations of radius 3 / 4 (k_dense_wgrad.hip; DAU_FLAG_DENSE_BF16)
     kNumMembers
 };
 enum PassKind { kGatherSum, kGatherDot };
 // the offsets a bucket-4 member covers (its device guard's upper end)
-constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 4, 8, 3, 4, 0, 4, 3, 4};
+constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 4, 8, 3, 4, 0, 4, 8, 4, 3, 4};
 constexpr int kFirst[2] = {kTiledGather, kTiledDot}, kEnd[2] = {kTiledDot, kNumMembers};   // the members of a pass kind
 // The radius-4 bf16 member runs in place of its set's exact kernels; every other non-exact member has an arithmetic of its own
 // and goes ahead of the bucket sets under its own guard.
 constexpr int kDense4[2] = {kBf16R4, kWgradR4};
 constexpr bool goes_ahead(int m) { return m != kTiledGather && m != kTiledDot && m != kBf16R4 && m != kWgradR4; }
-constexpr bool is_line(int m) { return m == kLine4 || m == kLine8; }
+constexpr bool is_line(int m) { return m == kLine4 || m == kLine8 || m == kDotLine4 || m == kDotLine8; }
+constexpr int kFirstLine[2] = {kLine4, kDotLine4};         // the two line members of a pass kind, radius 4 and 8
 
 // gather-sum directions, which are also their profile slots: y from x (S -> F) and dx from the error (F -> S)
 enum Dir { kFwd, kDx };
@@ -135,6 +137,19 @@ const WgradFns kWgrad[] = {
     {r4::dense_wgrad_configure, r4::dense_wgrad_workspace_bytes, r4::dense_wgrad_init, r4::dense_wgrad_run},
 };
 
+// the line members of the two-limb gather-dot kDotLine4, kDotLine8 (index m - kDotLine4)
+struct DotLineFns {
+    bool (*configure)(const Shape&, int, int, SplitDotConfig*);
+    size_t (*workspace_bytes)(const SplitDotConfig&);
+    void (*init)(const SplitDotConfig&);
+    void (*prepare)(hipStream_t, const SplitDotConfig&, const float*, const float*, const float*, int, int, void*, const Guard&);
+    void (*run)(hipStream_t, const SplitDotConfig&, const UnitRef*, float*, void*, const Guard&);
+};
+const DotLineFns kDotLine[] = {
+    {d4::split_dot_configure, d4::split_dot_workspace_bytes, d4::split_dot_init, d4::split_dot_prepare, d4::split_dot_run},
+    {d8::split_dot_configure, d8::split_dot_workspace_bytes, d8::split_dot_init, d8::split_dot_prepare, d8::split_dot_run},
+};
+
 // The kernels of one offset bucket.  A plan holds one set per bucket up to the static one (the bucket max_kernel_size allows);
 // which set and member run is decided per call from the actual max|mu| (pick_candidates below).
 struct BucketSet {
@@ -144,6 +159,7 @@ struct BucketSet {
     DenseConfig dense[kNumDense][2];
     TiledDotConfig tiled_dot;
     SplitDotConfig sdot;
+    SplitDotConfig sdline[2];     // kDotLine4, kDotLine8
     WgradConfig wgrad[2];
     // Batch slabs.  Every pass stages its whole input before it gathers; where that staged copy would exceed the workspace
     // budget (DAU_WORKSPACE_BUDGET_GB at plan creation, default 12: only the 512 x 512 configurations get there) the pass
@@ -176,6 +192,8 @@ size_t gather_bytes(const BucketSet& bs, int dir) {
 size_t dot_bytes(const BucketSet& bs) {
     size_t need = bs.has[kTiledDot] ? tiled_dot_workspace_bytes(bs.tiled_dot) : 0;
     if (bs.has[kSplitDot]) need = std::max(need, split_dot_workspace_bytes(bs.sdot));
+    for (int m = kDotLine4; m <= kDotLine8; ++m)
+        if (bs.has[m]) need = std::max(need, kDotLine[m - kDotLine4].workspace_bytes(bs.sdline[m - kDotLine4]));
     for (int m = kWgradR3; m <= kWgradR4; ++m)
         if (bs.has[m]) need = std::max(need, kWgrad[m - kWgradR3].workspace_bytes(bs.wgrad[m - kWgradR3]));
     return need;
@@ -299,6 +317,7 @@ int status_error(const dau_conv_plan* p, float mx, bool nan_seen) {
 // set -- and the call's outlier-unit count tells them apart: the ring member at most ring_limit, the others more (or offsets beyond 4).
 // With line members (DAU_FLAG_DENSE_SPLIT_LINE): they go first, under (-1, 4] and (4, 8], and run where the call's table has no unit
 // off the line; every member that follows and shares offsets with them runs there only where it has one -- the flag-off plan's kernels.
+// The line members of the gather-dot (DAU_FLAG_SPLIT_DOT_LINE) likewise, on the count of the pass's own bare table (run_param_sums).
 constexpr int kMaxCandidates = 9;
 int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
@@ -322,7 +341,7 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
     float lo = -1.0f;
     bool with_ring = false;
     int line_r = 0;                                          // the offsets the line members cover
-    for (int m = kLine4; m <= kLine8 && kind == kGatherSum; ++m) {
+    for (int m = kFirstLine[kind]; m <= kFirstLine[kind] + 1; ++m) {
         if (!s0->has[m]) continue;
         Guard g{dev_status, (float)line_r - (line_r ? 0.0f : 1.0f), (float)kRadius[m]};
         g.line = kRadius[m];
@@ -372,6 +391,7 @@ int ensure_attrs(const dau_conv_plan* p) {
             else if (m <= kBf16R4) for (int dir : {kFwd, kDx}) kDense[m - kSplit2].init(bs.dense[m - kSplit2][dir]);
             else if (m == kTiledDot) tiled_dot_init(bs.tiled_dot);
             else if (m == kSplitDot) split_dot_init(bs.sdot);
+            else if (m == kDotLine4 || m == kDotLine8) kDotLine[m - kDotLine4].init(bs.sdline[m - kDotLine4]);
             else kWgrad[m - kWgradR3].init(bs.wgrad[m - kWgradR3]);
         }
         if (bs.ring) ring_init();
@@ -563,6 +583,12 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL");
     if ((flags & DAU_FLAG_DENSE_SPLIT_LINE) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
+    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL");
+    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && !(flags & DAU_FLAG_USE_INTERPOLATION))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_USE_INTERPOLATION");
+    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
     if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
         (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
         return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
@@ -688,6 +714,17 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
                                 split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
             bs.sdot.nhwc = nhwc;
             bs.sdot.in_relu = in_relu;
+            // its line members (DAU_FLAG_SPLIT_DOT_LINE, single-dimension layers): held where the 2-D member would be; radius 8 where
+            // the plan's offsets reach it and radius 4 is held (DAU_FLAG_STATIC_BUCKET: no per-call selection, the flag is inert)
+            for (int m = kDotLine4; m <= kDotLine8; ++m) {
+                SplitDotConfig& cfg = bs.sdline[m - kDotLine4];
+                const DotLineFns& fn = kDotLine[m - kDotLine4];
+                const bool want = (flags & DAU_FLAG_SPLIT_DOT_LINE) && split_allowed && whole_dot && !(flags & DAU_FLAG_STATIC_BUCKET) &&
+                                  (split_forced || fill) && (m == kDotLine4 || (bucket >= 8 && bs.has[kDotLine4]));
+                bs.has[m] = want && fn.configure(s, blur_k, act, &cfg) && (double)fn.workspace_bytes(cfg) <= budget_bytes;
+                cfg.nhwc = nhwc;
+                cfg.in_relu = in_relu;
+            }
         }
     }
     const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
@@ -791,6 +828,9 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
     if (plan->sets[0].ring) info->gather_dense_split |= 1 << 5;
     if (plan->dynamic && tiled_fwd && s0[kLine4]) info->gather_dense_split |= 1 << 6;
     if (plan->dynamic && tiled_fwd && s0[kLine8]) info->gather_dense_split |= 1 << 7;
+    const bool tiled_bwd = plan->algo_bwd == DAU_ALGO_TILED;
+    if (plan->dynamic && tiled_bwd && s0[kDotLine4]) info->gather_dense_split |= 1 << 8;
+    if (plan->dynamic && tiled_bwd && s0[kDotLine8]) info->gather_dense_split |= 1 << 9;
     return DAU_OK;
 }
 
@@ -909,11 +949,16 @@ namespace {
 
 // raw parameter-gradient sums r4[k][s][g][f] = offset_and_dot(x * D_k, dy') with bare bilinear factors
 // kinds: 4, or 3 when the caller does not want dsigma (only the dense form computes fewer: its GEMMs are per kind)
+// w: the weights where the caller has them (dau_conv_backward), for the line members' count alone; the table is bare either way
 int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const float* dy, const float* mu1,
-                   const float* mu2, const BwdWs& ws, float* r4, int kinds) {
+                   const float* mu2, const BwdWs& ws, float* r4, int kinds, const float* w = nullptr) {
     const Shape& s = p->sh;
-    launch_prepare_units(st, nullptr, mu1, mu2, s, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table_bare,
-                         ws.status, p->host_status);
+    // (the gather-dot's line members: their condition is counted on THIS table, into Status::pad2[0] for the report and into
+    // line[0], which the guards read; line[0] goes back to zero behind the pass, for the count of the input-gradient table;
+    // a NaN / Inf weight counts where the caller has the weights)
+    const bool dot_line = p->algo_bwd == DAU_ALGO_TILED && p->dynamic && p->sets[0].has[kDotLine4];
+    launch_prepare_units(st, dot_line ? w : nullptr, mu1, mu2, s, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table_bare,
+                         ws.status, p->host_status, -1, dot_line ? ws.status : nullptr, true);
     if (p->profiling) ++p->prof_passes[2];
     if (p->algo_bwd == DAU_ALGO_TILED) {
         Candidate cand[kMaxCandidates];
@@ -922,7 +967,12 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
             const BucketSet& bs = *cand[ci].set;
             const Guard& g = cand[ci].guard;
             const int m = cand[ci].member;
-            if (m == kSplitDot) {                                              // the whole batch in one pass
+            if (m == kDotLine4 || m == kDotLine8) {                            // the whole batch in one pass
+                const DotLineFns& fn = kDotLine[m - kDotLine4];
+                fn.prepare(st, bs.sdline[m - kDotLine4], x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
+                ProfScope prof(p, 2, st);
+                fn.run(st, bs.sdline[m - kDotLine4], ws.table_bare, r4, ws.tiled_dot, g);
+            } else if (m == kSplitDot) {                                       // likewise
                 split_dot_prepare(st, bs.sdot, x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
                 ProfScope prof(p, 2, st);
                 split_dot_run(st, bs.sdot, ws.table_bare, r4, ws.tiled_dot, g);
@@ -940,6 +990,7 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
                 }
             }
         }
+        if (dot_line) (void)hipMemsetAsync(&ws.status->line[0], 0, sizeof(unsigned), st);
     } else {
         launch_blur_direct(st, x, (long)s.N * s.S, s.H, s.W, ws.filters + 1 * kFilterPlane, kNumK, p->blur_k, ws.xk4);
         ProfScope prof(p, 2, st);
@@ -979,7 +1030,7 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
 
     const int param_mask = DAU_NEED_DW | DAU_NEED_DMU1 | DAU_NEED_DMU2 | DAU_NEED_DSIGMA;
     if (need_mask & param_mask) {
-        run_param_sums(p, st, x, dy, mu1, mu2, ws, ws.r4, (need_mask & DAU_NEED_DSIGMA) ? 4 : 3);
+        run_param_sums(p, st, x, dy, mu1, mu2, ws, ws.r4, (need_mask & DAU_NEED_DSIGMA) ? 4 : 3, w);
         launch_finalize_grads(st, ws.r4, w, s, p->d.number_units_ignore, p->d.mu_learning_rate_factor, need_mask,
                               flags & DAU_FLAG_SINGLE_DIM_KERNEL, dw, dmu1, dmu2, dsigma);
     }
@@ -1058,6 +1109,17 @@ int dau_conv_gather_line_status(const dau_conv_plan* p, void* stream, const void
     DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
     if (off_line_units) *off_line_units = (int32_t)h.line[0];
     if (line_radius_taken) *line_radius_taken = (int32_t)h.line[1];
+    return DAU_OK;
+}
+
+int dau_conv_dot_line_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* off_line_units,
+                             int32_t* line_radius_taken) {
+    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    Status h;
+    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
+    if (off_line_units) *off_line_units = (int32_t)h.pad2[0];
+    if (line_radius_taken) *line_radius_taken = (int32_t)h.pad2[1];
     return DAU_OK;
 }
 

@@ -191,6 +191,23 @@ void split_dot_init(const SplitDotConfig& cfg);
 void split_dot_prepare(hipStream_t st, const SplitDotConfig& cfg, const float* x, const float* dy, const float* filters,
                        int drop_col, int drop_row, void* workspace, const Guard& guard);
 void split_dot_run(hipStream_t st, const SplitDotConfig& cfg, const UnitRef* table, float* r4, void* workspace, const Guard& guard);
+// The line forms (-DDAU_SD_1D: namespaces d4 and d8; DAU_FLAG_SPLIT_DOT_LINE): the same source compiled with a horizontal radius
+// of 4 / 8 and a vertical radius of 0, for calls whose units all lie on the row of their pixel -- the parameter gradients of
+// single-dimension layers.  The kind mu2 is computed and discarded.  The dy maxima kernel of a form whose guard has passed writes
+// the form's radius to Status::pad2[1].
+#define DAU_DECLARE_SPLIT_DOT_LINE(NS)                                                                                         \
+    namespace NS {                                                                                                            \
+    bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);                                      \
+    size_t split_dot_workspace_bytes(const SplitDotConfig& cfg);                                                              \
+    void split_dot_strip(const SplitDotConfig& cfg, int* items, int* k_steps);                                                \
+    void split_dot_init(const SplitDotConfig& cfg);                                                                           \
+    void split_dot_prepare(hipStream_t st, const SplitDotConfig& cfg, const float* x, const float* dy, const float* filters,  \
+                           int drop_col, int drop_row, void* workspace, const Guard& guard);                                  \
+    void split_dot_run(hipStream_t st, const SplitDotConfig& cfg, const UnitRef* table, float* r4, void* workspace,           \
+                       const Guard& guard);                                                                                   \
+    }
+DAU_DECLARE_SPLIT_DOT_LINE(d4)
+DAU_DECLARE_SPLIT_DOT_LINE(d8)
 
 // Densified parameter gradients on the bf16 matrix cores (k_dense_wgrad.hip; DAU_FLAG_DENSE_BF16, bucket 4, bfloat16
 // activations, three or more units): C_k[d][s][f] = sum_{n,q} Xk[n,s,q+d] * E'[n,f,q] for the 9 x 9 displacements d as a GEMM

@@ -46,7 +46,37 @@
 
 #include "dau_tiled.hpp"
 
+// The line forms (-DDAU_SD_1D with -DDAU_SD_RX=4 / 8 and -DDAU_SD_NS=d4 / d8; DAU_FLAG_SPLIT_DOT_LINE): the same GEMM for calls whose
+// units all lie on the row of their pixel (oy == 0 and no factor on the row below: the call's device guard decides), i.e. the
+// parameter gradients of single-dimension layers.  The horizontal radius of the error window is RX, the vertical one 0: no halo
+// rows in ES or in the LDS ring (2 RH = 8 slots, every row of an item new), which leaves room for RX = 8.  The corners dy = 1
+// are left out of the bilinear combination (their A rows repeat the dy = 0 rows): half of a tile's rows carry no result.
+// The plain object is the 2-D member (radius 4 both ways), its kernels the bytes they were.
+#ifndef DAU_SD_RX
+#define DAU_SD_RX 4
+#endif
+#ifndef DAU_SD_1D
+#define DAU_SD_1D 0
+#endif
+// The kernels of the line forms are named ld_*_kernel / line_dot_kernel (d4::line_dot_kernel, ...): tools and the built-code
+// tests pick the 2-D member's kernels by the names below.  EVERY __global__ function of this file is listed here.
+#if DAU_SD_1D
+#define sd_absmax_x_kernel ld_absmax_x_kernel
+#define sd_absmax_e_kernel ld_absmax_e_kernel
+#define sd_absmax_nhwc_e_kernel ld_absmax_nhwc_e_kernel
+#define sd_stage_x_kernel ld_stage_x_kernel
+#define sd_xk_walk_kernel ld_xk_walk_kernel
+#define sd_stage_e_kernel ld_stage_e_kernel
+#define sd_stage_e1_kernel ld_stage_e1_kernel
+#define sd_stage_nhwc_e_kernel ld_stage_nhwc_e_kernel
+#define split_gather_dot_kernel line_dot_kernel
+#define sd_e1_dot_kernel line_e1_dot_kernel
+#endif
+
 namespace dau {
+#ifdef DAU_SD_NS
+namespace DAU_SD_NS {
+#endif
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4s __attribute__((ext_vector_type(4)));
@@ -58,7 +88,9 @@ constexpr int kSdAS = 2;                // input channels per wave (four spill t
 constexpr int kSdGT = 4;                // units per (input channel, output channel) in one workgroup
 constexpr int kSdSB = kSdWaves * kSdAS; // input channels per workgroup
 constexpr int kSdFB = 16;               // output channels per workgroup = B columns of a tile
-constexpr int kSdR = 4;                 // offset radius of the error window
+constexpr bool kSdLine = DAU_SD_1D != 0;
+constexpr int kSdRX = DAU_SD_RX;        // offset radius of the error window: horizontal,
+constexpr int kSdRY = kSdLine ? 0 : kSdRX;   // vertical (a line form has no rows above or below)
 constexpr int kSdRH = 4;                // region rows = K groups of one MFMA
 constexpr int kSdFlushItems = 16;       // items per flush of the running sums (at most 16 float additions per slot and chunk)
 // s_waitcnt immediates (gfx9 encoding: vmcnt in bits 3:0, expcnt 6:4 and lgkmcnt 11:8 left at their maxima)
@@ -91,7 +123,7 @@ SdGeom sd_geom(const SplitDotConfig& c) {
     g.thin = kSdThin && (s.H + 1) % kSdRH == 1 && g.rq >= 2;
     g.strip_steps = (g.rq - g.thin) * c.RW + g.thin * ((c.RW + kSdRH - 1) / kSdRH);
     g.XTr = g.Hq + 1; g.XTc = g.Wq + 1;
-    g.EYs = g.Hq + 2 * kSdR; g.EXs = g.Wq + 2 * kSdR;
+    g.EYs = g.Hq + 2 * kSdRY; g.EXs = g.Wq + 2 * kSdRX;
     g.octs = (s.N + 7) / 8;
     g.NP = (s.N + 1) / 2;
     g.nfb = (s.F + kSdFB - 1) / kSdFB;
@@ -172,10 +204,19 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
 }
 #endif
 
+// A line form's guard has passed: this member does the pass's work (dau_conv_dot_line_status reports it).  The one write a kernel
+// of this file makes through its guard (dau_common.hpp, Guard): one thread of the pass's dy maxima kernel.
+__device__ __forceinline__ void sd_mark_taken(const Guard& guard) {
+    if constexpr (kSdLine) {
+        if (guard.status && blockIdx.x == 0 && threadIdx.x == 0) const_cast<Status*>(guard.status)->pad2[1] = (unsigned)kSdRX;
+    }
+}
+
 // max |dy| per output channel: grid (F, split); dy is fp32, f16 or bf16 (act)
 __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
                                                           unsigned* __restrict__ emax, const Guard guard) {
     if (!guard_pass(guard)) return;
+    sd_mark_taken(guard);
     const int f = blockIdx.x % F, part = blockIdx.x / F;
     float m = 0.0f;
     const long total = (long)N * HW;
@@ -193,6 +234,7 @@ __global__ void __launch_bounds__(256) sd_absmax_e_kernel(const float* __restric
 __global__ void __launch_bounds__(256) sd_absmax_nhwc_e_kernel(const float* __restrict__ dy, int N, int F, int HW, int split, int act,
                                                                unsigned* __restrict__ emax, const Guard guard) {
     if (!guard_pass(guard)) return;
+    sd_mark_taken(guard);
     const int nfb = (F + 63) / 64;
     const int f = (blockIdx.x % nfb) * 64 + (threadIdx.x & 63), part = blockIdx.x / nfb;
     if (f >= F) return;
@@ -508,7 +550,7 @@ __device__ __forceinline__ void sd_stage_e_walk(const SeWalkArgs& a, h8* lds) {
     const int lane = threadIdx.x, c = lane & (kSeCols - 1), j = lane >> 4;
     const int H = a.H, W = a.W;
     const long plane = (long)H * W;
-    const int vx0 = ct * kSeCols, x = vx0 + c - (kSdR + 1);
+    const int vx0 = ct * kSeCols, x = vx0 + c - (kSdRX + 1);
     const bool col_in = x >= 0 && x < a.wlim;
     long off[4];                                         // elements from (image, first channel of the block, row)
     float sc[4];
@@ -526,7 +568,7 @@ __device__ __forceinline__ void sd_stage_e_walk(const SeWalkArgs& a, h8* lds) {
     const int steps = (b1 - b0 + kRing - 1) / kRing * kRing;
     Raw rv[kRing][32];
     auto load_row = [&](int vy, Raw* dst) {
-        const int y = vy - (kSdR + 1), yc = y < 0 ? 0 : y < H ? y : H - 1;
+        const int y = vy - (kSdRY + 1), yc = y < 0 ? 0 : y < H ? y : H - 1;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int n = oct * 8 + i;
@@ -540,7 +582,7 @@ __device__ __forceinline__ void sd_stage_e_walk(const SeWalkArgs& a, h8* lds) {
     h8* const out = a.es + (((size_t)oct * a.nfb + fb) * a.EYs * a.EXs + vx0) * 32 + lane;
     auto step = [&](auto pc, int u) {
         constexpr int P = decltype(pc)::value;
-        const int vy = b0 + u, y = vy - (kSdR + 1);
+        const int vy = b0 + u, y = vy - (kSdRY + 1);
         load_row(vy + kSeAhead, rv[(P + kSeAhead) % kRing]);
         const bool row_in = y >= 0 && y < a.hlim;
         h8* buf = lds + (u & 1) * kRow;
@@ -603,12 +645,12 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
     const int oct = t / nfb;
     const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
     const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
-    const int y = vy - (kSdR + 1);
+    const int y = vy - (kSdRY + 1);
     // its columns inside the image: [c0, c1)
-    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    const int c0 = max(vx0, kSdRX + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdRX + 1 + wlim) : c0;
     const int nd = max(c1 - c0, 0);
     for (int i = threadIdx.x; i < kSdFB * nd; i += 256) {
-        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdR + 1), lx = vx - vx0;
+        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdRX + 1), lx = vx - vx0;
         const int f = fb * kSdFB + fl;
         const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
         float v[8];
@@ -650,7 +692,7 @@ __global__ void __launch_bounds__(256) sd_stage_e_kernel(const float* __restrict
         const int vy = (int)(t % EYs); t /= EYs;
         const int fb = (int)(t % nfb);
         const int oct = (int)(t / nfb);
-        const int y = vy - (kSdR + 1), x = vx - (kSdR + 1);
+        const int y = vy - (kSdRY + 1), x = vx - (kSdRX + 1);
         const bool in = y >= 0 && y < hlim && x >= 0 && x < wlim;
         h8* dst = es + (size_t)idx * 32;
         for (int fl = 0; fl < kSdFB; ++fl) {
@@ -691,12 +733,12 @@ __global__ void __launch_bounds__(256) sd_stage_e1_kernel(const float* __restric
     const int oct = t / nfb;
     const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
     const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
-    const int y = vy - (kSdR + 1);
+    const int y = vy - (kSdRY + 1);
     // its columns inside the image: [c0, c1)
-    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    const int c0 = max(vx0, kSdRX + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdRX + 1 + wlim) : c0;
     const int nd = max(c1 - c0, 0);
     for (int i = threadIdx.x; i < kSdFB * nd; i += 256) {
-        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdR + 1), lx = vx - vx0;
+        const int fl = i / nd, vx = c0 + (i - fl * nd), x = vx - (kSdRX + 1), lx = vx - vx0;
         const int f = fb * kSdFB + fl;
         const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
         float v[8];
@@ -738,12 +780,12 @@ __global__ void __launch_bounds__(256) sd_stage_nhwc_e_kernel(const float* __res
     const int oct = t / nfb;
     const int wlim = drop_col ? W - 1 : W, hlim = drop_row ? H - 1 : H;
     const int vx0 = ct * TX, nvx = min(TX, EXs - vx0);   // this tile's window columns [vx0, vx0 + nvx)
-    const int y = vy - (kSdR + 1);
+    const int y = vy - (kSdRY + 1);
     // its columns inside the image: [c0, c1)
-    const int c0 = max(vx0, kSdR + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdR + 1 + wlim) : c0;
+    const int c0 = max(vx0, kSdRX + 1), c1 = (y >= 0 && y < hlim) ? min(vx0 + nvx, kSdRX + 1 + wlim) : c0;
     h8* dst = es + ((((size_t)oct * nfb + fb) * EYs + vy) * EXs + vx0) * (kSdFB * LIMBS);
     for (int i = threadIdx.x; i < nvx * kSdFB; i += 256) {
-        const int lx = i / kSdFB, fl = i - lx * kSdFB, vx = vx0 + lx, x = vx - (kSdR + 1);
+        const int lx = i / kSdFB, fl = i - lx * kSdFB, vx = vx0 + lx, x = vx - (kSdRX + 1);
         const int f = fb * kSdFB + fl;
         const bool in = vx >= c0 && vx < c1 && f < F;
         const float sc = f < F ? ldexpf(1.0f, sd_shift(emax[f])) : 0.0f;
@@ -821,7 +863,7 @@ template <int RW, int EL>
 __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     if (!guard_pass(a.guard)) return;
-    constexpr int WL = RW + 2 * kSdR, WR = kSdRH + 2 * kSdR;
+    constexpr int WL = RW + 2 * kSdRX, WR = kSdRH + 2 * kSdRY;
     constexpr int kRing = WR + kSdRH;                    // ring slots (rows)
     constexpr int PB = EL * 256;                         // bytes per window position: 16 channels x 8 images x EL limbs
     constexpr unsigned RB = WL * PB;                     // bytes per window row
@@ -862,13 +904,13 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
         const int s = sb * kSdSB + wave * kSdAS + i;
         s_ok[i] = s < a.S;
         sidx[i] = s_ok[i] ? s : a.S - 1;
-        aoff[i] = (unsigned)((((size_t)sidx[i] * kNumK + ak) * xplane + (size_t)(j + ady) * a.XTc + adx) * 2);
+        aoff[i] = (unsigned)((((size_t)sidx[i] * kNumK + ak) * xplane + (size_t)(j + (kSdLine ? 0 : ady)) * a.XTc + adx) * 2);
 #pragma unroll
         for (int gg = 0; gg < kSdGT; ++gg) {
             const int g = gb * kSdGT + gg;
             UnitRef u{0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
             if (s_ok[i] && g < a.G && f_ok) u = a.table[((size_t)sidx[i] * a.G + g) * a.F + f];
-            uw[i][gg] = (unsigned)(j - u.oy + kSdR) | (unsigned)((kSdR - u.ox) * PB + fl * 16) << 4;
+            uw[i][gg] = (unsigned)(j - u.oy + kSdRY) | (unsigned)((kSdRX - u.ox) * PB + fl * 16) << 4;
             wb[i][gg] = f4s{u.w00, u.w01, u.w10, u.w11};
             run[i][gg] = 0.0f;
         }
@@ -1073,8 +1115,11 @@ __device__ __forceinline__ void sd_dot_body(const SdArgs& a) {
                     const f4s p = part[i][gg], w = wb[i][gg];
                     float v = w[0] * p[0];
                     v = fmaf(w[1], p[1], v);
-                    v = fmaf(w[2], p[2], v);
-                    v = fmaf(w[3], p[3], v);
+                    // (a line form: the corners on the row below are no terms at all -- a zero factor times a non-finite sum would be a NaN)
+                    if constexpr (!kSdLine) {
+                        v = fmaf(w[2], p[2], v);
+                        v = fmaf(w[3], p[3], v);
+                    }
                     run[i][gg] += ok ? v : 0.0f;
                 }
         };
@@ -1207,7 +1252,7 @@ __global__ void __launch_bounds__(kSdWaves * 64) __attribute__((amdgpu_waves_per
 template <int RW, int EL>
 void launch_sd(hipStream_t st, const SdArgs* a, int grid) {
     auto kern = [] { if constexpr (EL == 2) return split_gather_dot_kernel<RW>; else return sd_e1_dot_kernel<RW>; }();
-    const size_t lds = (size_t)(2 * kSdRH + 2 * kSdR) * (RW + 2 * kSdR) * 256 * EL;
+    const size_t lds = (size_t)(2 * kSdRH + 2 * kSdRY) * (RW + 2 * kSdRX) * 256 * EL;
     if (!a) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); return; }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kSdWaves * 64), lds, st, *a);
 }
@@ -1264,7 +1309,7 @@ bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* c
         const long cost = wq * (rw + 2) * (60 / rw);                // wq * (rw + 2) / rw, scaled to an integer
         if (cost < best_cost) { best_cost = cost; best = rw; }
     }
-    if ((size_t)(2 * kSdRH + 2 * kSdR) * (best + 2 * kSdR) * 512 > 160 * 1024) return false;
+    if ((size_t)(2 * kSdRH + 2 * kSdRY) * (best + 2 * kSdRX) * 512 > 160 * 1024) return false;
     if (!blur4_pack_fits(blur_k, sh.H, sh.W)) return false;
     SplitDotConfig c{};
     c.sh = sh; c.blur_k = blur_k; c.RW = best; c.act = act;
@@ -1394,4 +1439,7 @@ void split_dot_run(hipStream_t st, const SplitDotConfig& c, const UnitRef* table
     launch_dot_reduce(st, a.partial, 1, (long)kNumK * s.S * s.G * s.F, s.G, s.F, s.G, g.chunks, g.chunks, s.G, false, r4, guard);
 }
 
+#ifdef DAU_SD_NS
+}  // namespace DAU_SD_NS
+#endif
 }  // namespace dau

@@ -26,7 +26,7 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
                                      const float* __restrict__ mu2, int S, int G, int F, int ignore,
                                      int flags, int bucket, int transposed_negated, int weight_mode,
                                      UnitRef* __restrict__ table, Status* __restrict__ status,
-                                     HostStatus* __restrict__ host_status, int count_ignore, Status* line_status) {
+                                     HostStatus* __restrict__ host_status, int count_ignore, Status* line_status, int line_dot) {
     const long units = (long)S * G * F;
     unsigned int local_max = 0, local_nan = 0, local_out = 0;   // local_out: live units beyond +-3 (Status.pad[1])
     unsigned int local_off = 0;                                 // units of this table off the line (Status.line[0])
@@ -58,10 +58,16 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
         table[dst] = r;
         // on the line: the row of the pixel alone (a NaN / Inf weight makes w10 a NaN: off the line, the 2-D kernels propagate it)
         local_off += (r.oy == 0 && r.w10 == 0.0f && r.w11 == 0.0f) ? 0u : 1u;
+        // the bare table of the parameter-gradient pass knows no weight: where the caller has them (dau_conv_backward), a NaN / Inf
+        // weight counts as a unit off the line here too, so that such a call runs the flag-off plan in all of its passes
+        if (line_dot && w) local_off += (fabsf(w[u]) <= 3.402823466e+38f) ? 0u : 1u;
     }
     if (line_status) {
         for (int m = 32; m >= 1; m >>= 1) local_off += (unsigned int)__shfl_xor((int)local_off, m);
-        if ((threadIdx.x & 63) == 0 && local_off) atomicAdd(&line_status->line[0], local_off);
+        if ((threadIdx.x & 63) == 0 && local_off) {
+            atomicAdd(&line_status->line[0], local_off);
+            if (line_dot) atomicAdd(&line_status->pad2[0], local_off);     // the parameter-gradient pass: the count it reports
+        }
     }
     if (status) {
         // one atomic per workgroup: thousands of same-address atomics serialise in L2 and were most of this kernel's time
@@ -102,13 +108,13 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
 
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
-                          Status* status, HostStatus* host_status, int count_ignore, Status* line_status) {
+                          Status* status, HostStatus* host_status, int count_ignore, Status* line_status, bool line_dot) {
     const long units = (long)sh.S * sh.G * sh.F;
     const int block = 256;
     const int grid = (int)((units + block - 1) / block < 512 ? (units + block - 1) / block : 512);
     hipLaunchKernelGGL(prepare_units_kernel, dim3(grid), dim3(block), 0, st, w, mu1, mu2, sh.S, sh.G, sh.F,
-                       ignore, flags, bucket, transposed_negated ? 1 : 0, w == nullptr ? 1 : 0, table, status,
-                       status ? host_status : nullptr, count_ignore < 0 ? ignore : count_ignore, line_status);
+                       ignore, flags, bucket, transposed_negated ? 1 : 0, (w == nullptr || line_dot) ? 1 : 0, table, status,
+                       status ? host_status : nullptr, count_ignore < 0 ? ignore : count_ignore, line_status, line_dot ? 1 : 0);
 }
 
 // dw = r0 ; dmu1 = w*r1*lr ; dmu2 = w*r2*lr ; dsigma = w*r3 ; ignored units -> 0 ; NaN in dmu -> 0.

@@ -27,6 +27,7 @@ FLAG_DENSE_WGRAD_ALWAYS = 1 << 8   # with FLAG_DENSE_BF16: dense parameter gradi
 FLAG_DENSE_SPLIT_F16 = 1 << 9      # gather-sum passes of calls with |mu| <= 2 / 3 / 4 as a densified two-limb f16 MFMA GEMM at fp32 accuracy, whatever G
 FLAG_NO_DENSE_SPLIT = 1 << 10      # never (default: the radii that pay for the plan's unit count)
 FLAG_DENSE_SPLIT_LINE = 1 << 15       # opt-in, with FLAG_SINGLE_DIM_KERNEL: calls whose units lie on a line run the 1 x 9 / 1 x 17 two-limb GEMM
+FLAG_SPLIT_DOT_LINE = 1 << 16         # opt-in, with FLAG_SINGLE_DIM_KERNEL: parameter gradients of calls whose units lie on a line run the line member of the two-limb gather-dot
 FLAG_DENSE_SPLIT_OUTLIERS = 1 << 12   # opt-in: calls within +-4 with few units beyond +-3 run the radius-3 two-limb GEMM plus a sparse ring pass
 FLAG_IO_F16 = 1 << 11   # x, y, dy, dx are torch.float16; the fp32 plan's kernels and arithmetic, parameters and their gradients float32
 FLAG_IO_NHWC = 1 << 13  # x, y, dy, dx are channels_last: [N][H][W][C] in memory; the NCHW plan of the same desc in everything but addresses
@@ -94,6 +95,8 @@ def _load():
         lib.dau_conv_gather_outlier_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "dau_conv_gather_line_status"):      # (likewise: the line members' query)
         lib.dau_conv_gather_line_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
+    if hasattr(lib, "dau_conv_dot_line_status"):         # (likewise: the gather-dot's line members' query)
+        lib.dau_conv_dot_line_status.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     if hasattr(lib, "dau_conv_split_dot_geometry"):      # (likewise: the split gather-dot's strip geometry)
         lib.dau_conv_split_dot_geometry.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 3
     if hasattr(lib, "dau_conv_forward_epilogue"):        # (likewise: the fused epilogue and its backward pass)
@@ -394,6 +397,16 @@ class Plan(object):
         dev = self._last_ws.device
         with torch.cuda.device(dev):
             _check(lib.dau_conv_gather_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
+        return units.value, taken.value
+
+    def dot_line_status(self):
+        """Sync; -> (off_line_units, line_radius_taken) of the last backward call: the units of its bare parameter-gradient table that
+        do not lie on the row of their pixel (counted by plans that hold a line member of the gather-dot, FLAG_SPLIT_DOT_LINE), and
+        4 or 8 if its parameter gradients ran as the line member of that radius, 0 if another member did the work."""
+        units, taken = ctypes.c_int32(), ctypes.c_int32()
+        dev = self._last_ws.device
+        with torch.cuda.device(dev):
+            _check(lib.dau_conv_dot_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, taken.value
 
     def last_status(self):

@@ -16,7 +16,8 @@ promise (_promised); grad cast to x's dtype; 0-element tensors for the gradients
         -> (dx, dw, dmu1, dmu2, dsigma, dbias): need_mask holds the _capi.NEED_* bits; a gradient that is not asked for comes back as
         a 0-element tensor.  x is the raw input (of an input_relu call too), y the forward's output, needed with relu only.
     settings: number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1,
-        use_interpolation, algo, dense_bf16, dense_split (-1: the library's choice, 0: never, 1: always; 2: the library's choice plus
+        use_interpolation, algo (the _capi.ALGO_* value, plus 16 with dense_line_grads=True: the line members of the two-limb gather-dot
+        -- the schema has no argument of its own for it either), dense_bf16, dense_split (-1: the library's choice, 0: never, 1: always; 2: the library's choice plus
         the line members of dense_line=True, 3: always plus the line members -- the schema has no argument of its own for it), dense_outliers,
         channels_last (-1: by dtype, 0, 1) and check_offsets ("async", "on", "off") -- what _settings() normalises, as schema types.
 
@@ -45,6 +46,7 @@ _UNTRI = {-1: None, 0: False, 1: True}
 # the op's integer dense_split carries dense_line too: (dense_split, dense_line) <-> -1, 0, 1 as above, 2, 3 with the line members
 _SPLIT = {(None, False): -1, (False, False): 0, (True, False): 1, (None, True): 2, (True, True): 3}
 _UNSPLIT = {v: k for k, v in _SPLIT.items()}
+_LINE_GRADS = 16                     # the op's integer algo carries dense_line_grads: algo + 16
 _CHECK = {"async": "async", True: "on", False: "off"}
 _UNCHECK = {"async": "async", "on": True, "off": False}
 
@@ -52,7 +54,7 @@ _UNCHECK = {"async": "async", "on": True, "off": False}
 def encode_settings(st):
     """The op's trailing arguments from a _settings() dict, in schema order."""
     return (st["number_units_ignore"], st["kernel_size"], st["unit_testing"], st["mu_learning_rate_factor"], st["single_dim_kernel"],
-            st["forbid_positive_dim1"], st["use_interpolation"], st["algo"], st["dense_bf16"],
+            st["forbid_positive_dim1"], st["use_interpolation"], st["algo"] + (_LINE_GRADS if st.get("dense_line_grads") else 0), st["dense_bf16"],
             _SPLIT[(st["dense_split"], bool(st.get("dense_line")))],
             st["dense_outliers"], _TRI[st["channels_last"]], _CHECK[st["check_offsets"]])
 
@@ -102,7 +104,7 @@ def _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_t
     st = _impl._settings(sigma, number_units_ignore=number_units_ignore, num_output=w.shape[-1], kernel_size=kernel_size,
                          unit_testing=unit_testing, mu_learning_rate_factor=mu_learning_rate_factor, single_dim_kernel=single_dim_kernel,
                          forbid_positive_dim1=forbid_positive_dim1, use_interpolation=use_interpolation, sigma_hint=_sigma_hint(sigma),
-                         check_offsets=_UNCHECK[check_offsets], algo=algo, dense_split=_UNSPLIT[dense_split][0],
+                         check_offsets=_UNCHECK[check_offsets], algo=algo & ~_LINE_GRADS, dense_line_grads=bool(algo & _LINE_GRADS), dense_split=_UNSPLIT[dense_split][0],
                          dense_line=_UNSPLIT[dense_split][1], dense_outliers=dense_outliers, **_layout_settings(dense_bf16, channels_last))
     if input_relu:
         st["input_relu"] = True

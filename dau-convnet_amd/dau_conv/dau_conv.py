@@ -154,6 +154,9 @@ def _get_plan_with(x, w, settings, nhwc, extra_flags):
     # pairs: single-dimension, not dense_split=False, not dense_bf16)
     if settings.get("dense_line"):
         flags |= _capi.FLAG_DENSE_SPLIT_LINE
+    # likewise their parameter gradients: the line members of the two-limb gather-dot (the same pairs checked)
+    if settings.get("dense_line_grads"):
+        flags |= _capi.FLAG_SPLIT_DOT_LINE
     make_key = lambda fl: (N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], fl, settings["algo"],
                            _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"]), x.device.index)
     make_plan = lambda fl: _capi.Plan(N, S, F, G, H, W, max_kernel_size=settings["kernel_size"],
@@ -224,7 +227,13 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
               merge_threshold=1, unit_testing=False, mu_learning_rate_factor=1.0, single_dim_kernel=False,
               forbid_positive_dim1=False, use_interpolation=True, sigma_hint=None, check_offsets="async",
               algo=_capi.ALGO_AUTO, dense_bf16=False, dense_split=None, process_group=None, grad_reduce="mean", name=None,
-              dense_outliers=False, channels_last=None, dense_line=False):
+              dense_outliers=False, channels_last=None, dense_line=False, dense_line_grads=False):
+    if dense_line_grads and not single_dim_kernel:
+        raise ValueError("dense_line_grads=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
+    if dense_line_grads and dense_split is not None and not dense_split:
+        raise ValueError("dense_line_grads=True excludes dense_split=False")
+    if dense_line_grads and dense_bf16:
+        raise ValueError("dense_line_grads=True excludes dense_bf16=True (DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16)")
     if dense_line and not single_dim_kernel:
         raise ValueError("dense_line=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
     if dense_line and dense_split is not None and not dense_split:
@@ -247,7 +256,8 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
                 check_offsets=mode, algo=int(algo), dense_bf16=bool(dense_bf16),
                 dense_split=(None if dense_split is None else bool(dense_split)), dense_outliers=bool(dense_outliers),
                 process_group=process_group, grad_reduce=grad_reduce,
-                channels_last=(None if channels_last is None else bool(channels_last)), dense_line=bool(dense_line))
+                channels_last=(None if channels_last is None else bool(channels_last)), dense_line=bool(dense_line),
+                dense_line_grads=bool(dense_line_grads))
 
 
 def _c(t):
@@ -563,7 +573,7 @@ class _DAUConvolution2d(object):
                  dau_unit_sigma_bound=0.01, dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, check_offsets="async", algo=_capi.ALGO_AUTO,
                  dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None, dense_outliers=False,
-                 channels_last=None, dense_line=False):
+                 channels_last=None, dense_line=False, dense_line_grads=False):
         if len(input_shape) != 4:
             raise ValueError("Only two dimensional DAUConv supported (rank-4 NCHW input).")
         if data_format is None or data_format == "NHWC":
@@ -594,6 +604,7 @@ class _DAUConvolution2d(object):
         self.dense_split = dense_split
         self.dense_outliers = dense_outliers
         self.dense_line = dense_line
+        self.dense_line_grads = dense_line_grads
         self.channels_last = channels_last
         self.process_group = process_group
         self.grad_reduce = grad_reduce
@@ -617,7 +628,7 @@ class _DAUConvolution2d(object):
                         sigma_hint=sigma_hint, check_offsets=self.check_offsets, algo=self.algo,
                         dense_bf16=self.dense_bf16, dense_split=self.dense_split, dense_outliers=self.dense_outliers,
                         process_group=self.process_group, grad_reduce=self.grad_reduce, name=self.name,
-                        channels_last=self.channels_last, dense_line=self.dense_line)
+                        channels_last=self.channels_last, dense_line=self.dense_line, dense_line_grads=self.dense_line_grads)
 
 
 class DAUConv2d(nn.Module):
@@ -638,7 +649,9 @@ class DAUConv2d(nn.Module):
     DAUConv1d, or `dau_unit_single_dim=True`; ValueError elsewhere and together with `dense_split=False` or `dense_bf16=True`): a call whose units all
     lie on the row of their pixel (mu2 == 0) runs its two gather-sum passes as the two-limb GEMM over ONE row of taps -- 1 x 9 for
     offsets within +-4, 1 x 17 within +-8 -- instead of the 9 x 9 kernel or the exact gather; same accuracy; a call with a unit off
-    the line runs what it runs without the argument, bit for bit (DAU_FLAG_DENSE_SPLIT_LINE).  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
+    the line runs what it runs without the argument, bit for bit (DAU_FLAG_DENSE_SPLIT_LINE).  `dense_line_grads=True` (opt-in, the same layers and
+    the same ValueErrors): such a call runs its parameter gradients as the line member of the two-limb gather-dot, horizontal radius 4 or 8, in
+    place of the exact fp32 gather-dot; fp32 accuracy, independent of `dense_line` (DAU_FLAG_SPLIT_DOT_LINE).  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
     their forward and input-gradient passes as a densified bf16 matrix-core GEMM (DAU_FLAG_DENSE_BF16: taps and blurred
     activations rounded to bf16, fp32 sums) and, from three units per channel on, their
     parameter gradients as dense cross-correlations on the same cores -- the whole step about 2x faster than the exact
@@ -693,8 +706,15 @@ class DAUConv2d(nn.Module):
                  dau_unit_single_dim=False, dau_aggregation_forbid_positive_dim1=False, dau_sigma_trainable=False,
                  dau_mu_interpolation=True, unit_testing=False, name=None, in_channels=None, check_offsets="async",
                  algo=_capi.ALGO_AUTO, dense_bf16=False, process_group=None, grad_reduce="mean", dense_split=None,
-                 dense_outliers=False, channels_last=None, fused_epilogue=False, input_activation=None, dense_line=False, **kwargs):
+                 dense_outliers=False, channels_last=None, fused_epilogue=False, input_activation=None, dense_line=False,
+                 dense_line_grads=False, **kwargs):
         super(DAUConv2d, self).__init__()
+        if dense_line_grads and not dau_unit_single_dim:
+            raise ValueError("dense_line_grads=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
+        if dense_line_grads and dense_split is not None and not dense_split:
+            raise ValueError("dense_line_grads=True excludes dense_split=False")
+        if dense_line_grads and dense_bf16:
+            raise ValueError("dense_line_grads=True excludes dense_bf16=True (DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16)")
         if dense_line and not dau_unit_single_dim:
             raise ValueError("dense_line=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
         if dense_line and dense_split is not None and not dense_split:
@@ -752,6 +772,7 @@ class DAUConv2d(nn.Module):
         self.dense_split = dense_split
         self.dense_outliers = dense_outliers
         self.dense_line = bool(dense_line)
+        self.dense_line_grads = bool(dense_line_grads)
         self.channels_last = channels_last
         self.fused_epilogue = bool(fused_epilogue)
         if not (input_activation is None or input_activation == "relu" or callable(input_activation)):
@@ -848,7 +869,8 @@ class DAUConv2d(nn.Module):
             dau_mu_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing, data_format="NCHW",
             name=self.name, check_offsets=self.check_offsets, algo=self.algo, dense_bf16=self.dense_bf16,
             process_group=self.process_group, grad_reduce=self.grad_reduce, dense_split=self.dense_split,
-            dense_outliers=self.dense_outliers, channels_last=self.channels_last, dense_line=self.dense_line)
+            dense_outliers=self.dense_outliers, channels_last=self.channels_last, dense_line=self.dense_line,
+            dense_line_grads=self.dense_line_grads)
         self.built = True
 
     def _var(self, key):
@@ -1038,7 +1060,7 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                biases_initializer=zeros_initializer(), biases_regularizer=None, dau_unit_border_bound=0.01,
                dau_sigma_trainable=False, dau_aggregation_forbid_positive_dim1=False, dau_mu_interpolation=True,
                reuse=None, variables_collections=None, outputs_collections=None, trainable=True, scope=None,
-               dense_outliers=False, fused_epilogue=False, input_activation_fn=None, dense_line=False):
+               dense_outliers=False, fused_epilogue=False, input_activation_fn=None, dense_line=False, dense_line_grads=False):
     """slim-style functional form of DAUConv1d; like dau_conv2d it keeps its variables in the Python-side scope registry and stays
     eager under torch.compile."""
     if data_format not in [None, 'NCHW']:
@@ -1058,7 +1080,8 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
         dau_sigma_trainable=dau_sigma_trainable,
         dau_aggregation_forbid_positive_dim1=dau_aggregation_forbid_positive_dim1,
         dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
-        dense_outliers=dense_outliers, input_activation=input_activation_fn, dense_line=dense_line))
+        dense_outliers=dense_outliers, input_activation=input_activation_fn, dense_line=dense_line,
+        dense_line_grads=dense_line_grads))
     outputs = layer(inputs)
     if normalizer_fn is not None:
         outputs = normalizer_fn(outputs, **(normalizer_params or {}))

@@ -225,6 +225,24 @@ enum {
                                                DAU_FLAG_STATIC_BUCKET and DAU_ALGO_DIRECT; excludes DAU_FLAG_NO_DENSE_SPLIT and
                                                DAU_FLAG_DENSE_BF16; combines with every other flag.  The parameter gradients are not
                                                affected.                                                                         */
+    DAU_FLAG_SPLIT_DOT_LINE = 1 << 16,      /* opt-in, single-dimension layers (needs DAU_FLAG_SINGLE_DIM_KERNEL and
+                                               DAU_FLAG_USE_INTERPOLATION): the parameter-gradient pass (dw, dmu1, dsigma; dmu2 stays zero) of
+                                               a call whose units all lie on the row of their pixel -- every entry of the pass's bare unit
+                                               table has a vertical displacement of 0 and no factor on the row below; ignored units count --
+                                               runs as the line member of the two-limb f16 gather-dot: horizontal radius 4 for offsets within
+                                               +-4, radius 8 within +-8 (where max_kernel_size >= 11 allows such offsets), no vertical halo,
+                                               instead of the exact fp32 gather-dot of bucket 4 / 8 (the kernels behind the reference's
+                                               DAUConvBackward for such layers, dau_conv_backward_core.hpp).  fp32 accuracy, as the 2-D
+                                               two-limb member; a bf16 layer's error is staged in one limb.  The device decides per call: a
+                                               call with a unit off the line runs exactly the kernels of the plan without the flag and
+                                               returns its bits.  Held where the 2-D member would be held for a layer that is not
+                                               single-dimension (bucket 4's set, the whole batch in one pass, three or four units of every
+                                               block of four or DAU_FLAG_DENSE_SPLIT_F16, the workspace under the budget);
+                                               dau_conv_plan_info.gather_dense_split bits 8 / 9 report it, dau_conv_dot_line_status what a call
+                                               took.  dau_conv_backward and dau_conv_backward_param_sums alike.  Without the flag no plan
+                                               changes.  Inert under DAU_FLAG_STATIC_BUCKET and DAU_ALGO_DIRECT; excludes
+                                               DAU_FLAG_NO_DENSE_SPLIT and DAU_FLAG_DENSE_BF16; independent of DAU_FLAG_DENSE_SPLIT_LINE (the
+                                               gather-sum passes) and combines with it and with every other flag.                 */
     DAU_FLAG_DEFAULT = DAU_FLAG_USE_INTERPOLATION
 };
 
@@ -303,7 +321,8 @@ typedef struct dau_conv_plan_info {
                                    two-limb f16 GEMM of that radius (0: never); bit 5: calls within +-4 with few units beyond +-3
                                    can run theirs as the radius-3 GEMM plus the ring pass (DAU_FLAG_DENSE_SPLIT_OUTLIERS); bits 6 and
                                    7: calls whose units lie on a line, offsets within +-4 / within (4, 8], can run theirs as the 1 x 9 /
-                                   1 x 17 line member (DAU_FLAG_DENSE_SPLIT_LINE) */
+                                   1 x 17 line member (DAU_FLAG_DENSE_SPLIT_LINE); bits 8 and 9: such calls can run their parameter
+                                   gradients as the line member of the two-limb gather-dot of radius 4 / 8 (DAU_FLAG_SPLIT_DOT_LINE) */
 } dau_conv_plan_info;
 
 DAU_API int dau_conv_abi_version(void);
@@ -416,6 +435,14 @@ DAU_API int dau_conv_gather_outlier_status(const dau_conv_plan *plan, void *stre
  * as the line member of that radius (DAU_FLAG_DENSE_SPLIT_LINE), 0 if another member did the work.  Either may be NULL. */
 DAU_API int dau_conv_gather_line_status(const dau_conv_plan *plan, void *stream, const void *workspace,
                                 int32_t *off_line_units, int32_t *line_radius_taken);
+
+/* Waits for `stream`, then reports of the last backward call (dau_conv_backward, dau_conv_backward_param_sums) that used `workspace`:
+ * off_line_units = the units of its bare parameter-gradient table that do not lie on the row of their pixel (vertical displacement
+ * != 0 or a factor on the row below that is not zero; ignored units count), counted only by plans that hold a line member of the
+ * gather-dot; line_radius_taken = 4 or 8 if the call's parameter gradients ran as the line member of that radius
+ * (DAU_FLAG_SPLIT_DOT_LINE) in place of the exact gather-dot, 0 if another member did the work.  Either may be NULL. */
+DAU_API int dau_conv_dot_line_status(const dau_conv_plan *plan, void *stream, const void *workspace,
+                             int32_t *off_line_units, int32_t *line_radius_taken);
 
 /* The same report without waiting, from pinned host memory.  A NaN or an out-of-range offset seen by ANY completed call of
  * this plan since the last report is STICKY: it stays until this function (or dau_conv_check_status) has returned it once,

@@ -9,8 +9,11 @@ Each round times `--steps` back-to-back steps of one leg with HIP events after `
 legs.  Prints one JSON line per (layer, dtype): the median over all steps, the median of every round (their spread is the noise of
 the box), on - off, the per-pass gather-sum times of dau_conv_profile_begin / _end (the dominant kernel of the pass: the GEMM or the
 exact gather, without its staging) for either leg, which member the device took, and whether y agrees within the fp32 bar.
+--line-grads: the line members of the two-limb gather-dot instead (dense_line_grads=True, DAU_FLAG_SPLIT_DOT_LINE).  Both legs then
+have dense_line=True; flag off = the exact fp32 gather-dot of bucket 4 / 8, flag on = the line gather-dot of radius 4 / 8.  The
+result lines also carry the per-pass gather-dot time of either leg and what dau_conv_dot_line_status reports.
 usage: python tools/line_step_time.py [--steps 10] [--warmup 3] [--rounds 5] [--formats fp32,bf16] [--layers k9,k17] [--batch 128]
-                                      [--out FILE (appended)]"""
+                                      [--line-grads] [--out FILE (appended)]"""
 import argparse
 import importlib
 import json
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--formats", default="fp32,bf16")
     ap.add_argument("--layers", default="k9,k17")
     ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--line-grads", action="store_true", help="time dense_line_grads=True against dense_line=True alone")
     ap.add_argument("--out", default=None, help="JSON-lines file the result lines are appended to")
     args = ap.parse_args()
     import torch
@@ -52,7 +56,7 @@ def main():
         torch.manual_seed(0)
         return dau_conv.DAUConv1d(filters=F, dau_units=(4, 1), max_kernel_size=k, in_channels=S, use_bias=True,
                                   mu1_initializer=dau_conv.random_uniform_initializer(-m, m), mu_learning_rate_factor=1.0,
-                                  dense_line=line).to(dev)
+                                  dense_line=line or args.line_grads, dense_line_grads=line and args.line_grads).to(dev)
 
     def measure(nets, x, dy):
         def step(name):
@@ -92,9 +96,13 @@ def main():
             prof = plan.profile_end()
             res["gather_sum_ms_per_pass"][name] = {k_: round(ms / max(n_, 1), 4) for k_, (ms, n_) in prof.items() if k_ != "gather_dot"}
             res["line_status"][name] = list(plan.line_status())
+            if args.line_grads:
+                ms, n_ = prof["gather_dot"]
+                res.setdefault("gather_dot_ms_per_pass", {})[name] = round(ms / max(n_, 1), 4)
+                res.setdefault("dot_line_status", {})[name] = list(plan.dot_line_status())
         return res
 
-    head = {"call": "line_step_time", "device": torch.cuda.get_device_name(0), "build_id": _capi.build_id(),
+    head = {"call": "line_step_time_grads" if args.line_grads else "line_step_time", "device": torch.cuda.get_device_name(0), "build_id": _capi.build_id(),
             "steps_per_round": args.steps, "rounds": args.rounds}
     for layer in [l for l in args.layers.split(",") if l]:
         k, m = LAYERS[layer]
