@@ -227,10 +227,14 @@ constexpr unsigned kRingTakenBit = 0x80000000u;
 
 // Pinned host mirror of a plan (written by the last workgroup of prepare_units_kernel, read by dau_conv_last_status and as
 // the next call's offset-bucket hint): the most recent completed call's status, and the sticky record of bad ones.
+// sigma_needed / sigma_worst (written by synth_filters_kernel, read by dau_conv_sigma_status): the prefilter support the most recent
+// call's sigma needs (0: not a positive finite number; 19: more than 17 taps), and the largest such support beyond the plan's own
+// since the host last asked (sticky; 0: none).
 struct HostStatus {
-    unsigned int max_abs_mu_bits, nan_seen, valid, pad0;      // most recent completed call
-    unsigned int bad_max_abs_mu_bits, bad_nan_seen, pad1[2];  // worst status since the host last reported one (sticky)
+    unsigned int max_abs_mu_bits, nan_seen, valid, sigma_needed;      // most recent completed call
+    unsigned int bad_max_abs_mu_bits, bad_nan_seen, sigma_worst, pad1;  // worst status since the host last reported one (sticky)
 };
+static_assert(sizeof(HostStatus) == 32, "the pinned status mirror is 32 bytes (include/dau_conv.h, Ownership)");
 
 // Offset-bucket guard of a launch.  The bucket a call needs depends on max|mu|, which only the device knows when the
 // kernels are enqueued (prepare_units_kernel leaves it in the status block).  The host enqueues the kernel sets of up to
@@ -274,7 +278,10 @@ struct Shape {
 
 // ---- launchers implemented in the kernel TUs --------------------------------------
 // k_filters.hip
-void launch_synth_filters(hipStream_t st, const float* sigma_dev, int k, int flags, float* filters6);
+// host_status (may be null): the plan's pinned mirror, which takes the support this call's sigma needs
+// status (may be null): the call's status block, which the kernel clears for the prepare_units_kernel behind it
+void launch_synth_filters(hipStream_t st, const float* sigma_dev, int k, int flags, float* filters6, HostStatus* host_status = nullptr,
+                          Status* status = nullptr);
 void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k, int flags, float* planes6);
 // k_units.hip
 // host_status (may be null): pinned host copy of the status block, written by the last workgroup to finish
@@ -287,6 +294,9 @@ void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, cons
                           bool line_dot = false);
 void launch_finalize_grads(hipStream_t st, const float* r4, const float* w, Shape sh, int ignore, float lr,
                            int need_mask, bool single_dim, float* dw, float* dmu1, float* dmu2, float* dsigma);
+// `bytes` (a multiple of four) at p set to zero by a kernel: what the passes clear in their workspace, in stream order also in a
+// replayed graph (where a memset node was seen to land among the kernels behind it)
+void launch_zero_words(hipStream_t st, void* p, size_t bytes);
 // k_direct.hip  (DAU_ALGO_DIRECT: plain kernels, any shape)
 void launch_blur_direct(hipStream_t st, const float* x, long planes, int H, int W, const float* filters,
                         int nfilt, int k, float* out);

@@ -868,8 +868,7 @@ int forward_pass(const dau_conv_plan* p, void* stream, const float* x, const flo
         return fail(DAU_INVALID_ARGUMENT, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = ensure_attrs(p)) return rc;
-    DAU_HIP(hipMemsetAsync(ws.status, 0, sizeof(Status), st));
-    launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters);
+    launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters, p->host_status, ws.status);
     launch_prepare_units(st, w, mu1, mu2, p->sh, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table, ws.status,
                          p->host_status, -1, p->sets[0].has[kLine4] ? ws.status : nullptr);
     run_gather_sum(p, st, kFwd, x, y, ws.filters, ws.table, ws.status, ws.gather, epi);
@@ -990,7 +989,7 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
                 }
             }
         }
-        if (dot_line) (void)hipMemsetAsync(&ws.status->line[0], 0, sizeof(unsigned), st);
+        if (dot_line) launch_zero_words(st, &ws.status->line[0], sizeof(unsigned));
     } else {
         launch_blur_direct(st, x, (long)s.N * s.S, s.H, s.W, ws.filters + 1 * kFilterPlane, kNumK, p->blur_k, ws.xk4);
         ProfScope prof(p, 2, st);
@@ -1025,8 +1024,7 @@ int dau_conv_backward(const dau_conv_plan* p, void* stream, const float* x, cons
     const Shape& s = p->sh;
     const int flags = p->d.flags;
     if (int rc = ensure_attrs(p)) return rc;
-    DAU_HIP(hipMemsetAsync(ws.status, 0, sizeof(Status), st));
-    launch_synth_filters(st, sigma, p->blur_k, flags, ws.filters);
+    launch_synth_filters(st, sigma, p->blur_k, flags, ws.filters, p->host_status, ws.status);
 
     const int param_mask = DAU_NEED_DW | DAU_NEED_DMU1 | DAU_NEED_DMU2 | DAU_NEED_DSIGMA;
     if (need_mask & param_mask) {
@@ -1058,8 +1056,7 @@ int dau_conv_backward_param_sums(const dau_conv_plan* p, void* stream, const flo
     if (int rc = check_backward_ws(p, workspace, workspace_bytes, &ws)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = ensure_attrs(p)) return rc;
-    DAU_HIP(hipMemsetAsync(ws.status, 0, sizeof(Status), st));
-    launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters);
+    launch_synth_filters(st, sigma, p->blur_k, p->d.flags, ws.filters, p->host_status, ws.status);
     run_param_sums(p, st, x, dy, mu1, mu2, ws, sums_out, 4);
     DAU_HIP(hipPeekAtLastError());
     return DAU_OK;
@@ -1142,6 +1139,19 @@ int dau_conv_last_status(const dau_conv_plan* p, float* max_abs_mu_out, int32_t*
     // a bad status is reported once: the mirror goes back to "nothing reported" until the next call completes
     if (nan_seen || mx > (float)p->bucket) clear_host_status(p);
     return status_error(p, mx, nan_seen != 0);
+}
+
+int dau_conv_sigma_status(const dau_conv_plan* p, int32_t* needed_out, int32_t* planned_out, int32_t* worst_needed_out) {
+    if (!p || !needed_out || !planned_out || !worst_needed_out) return fail(DAU_INVALID_ARGUMENT, "null argument");
+    *needed_out = 0;
+    *planned_out = p->blur_k;
+    *worst_needed_out = 0;
+    if (!p->host_status) return DAU_OK;                  // no device: no call can have run
+    volatile HostStatus* h = p->host_status;
+    *needed_out = (int32_t)h->sigma_needed;
+    *worst_needed_out = (int32_t)h->sigma_worst;
+    h->sigma_worst = 0u;                                 // reported: sticky until here
+    return DAU_OK;
 }
 
 int dau_conv_filters(const dau_conv_plan* p, void* stream, const float* sigma, float* filters_out) {

@@ -7,11 +7,34 @@
 namespace dau {
 
 // plane_pitch: floats between the six 2-D planes of `out`; taps: the eight 1-D factor arrays (may be null)
+// host_status (may be null): the plan's pinned mirror, which takes the prefilter support THIS call's sigma needs -- the plan's k is
+// fixed at its creation, and a replayed graph runs no host code that could choose another plan (dau_conv_sigma_status)
 __global__ void synth_filters_kernel(const float* __restrict__ sigma_dev, int k, int flags, int plane_pitch,
-                                     float* __restrict__ out, float* __restrict__ taps) {
+                                     float* __restrict__ out, float* __restrict__ taps, HostStatus* __restrict__ host_status,
+                                     Status* __restrict__ status) {
     // one wave; lane t strides over the k*k taps, sums via wave reduction
     const int lane = threadIdx.x;
     const int n = k * k, c = (k - 1) / 2;
+    // status (may be null): the call's status block, cleared here for prepare_units_kernel, which runs next on the stream.  A kernel
+    // and not a memset: in a replayed graph a memset node was seen to land among the kernels behind it (k_split_dot.hip).
+    if (status && lane < (int)(sizeof(Status) / sizeof(unsigned))) reinterpret_cast<unsigned*>(status)[lane] = 0u;
+    if (host_status && lane == 0) {
+        // 2*ceil(5*sigma)+1 in float32, as dau_conv_filter_support computes it; beyond the 17 taps a plan can hold: 19; a sigma
+        // that is not a positive finite number: 0.  Plain stores to mapped pinned memory, as prepare_units_kernel makes its own,
+        // fenced at the end of this kernel; that kernel follows this one on the stream, so a host that sees its valid == 1 for a
+        // call sees this record of the call.
+        const float sf = sigma_dev[0];
+        unsigned need = 0u;
+        if (sf > 0.0f && sf <= 3.402823466e+38f) {
+            const float half = ceilf(5.0f * sf);
+            need = half > 8.0f ? 19u : 2u * (unsigned)half + 1u;
+        }
+        volatile HostStatus* h = host_status;
+        h->sigma_needed = need;
+        // sticky: the worst support needed beyond the plan's since the host last asked (calls of several streams may race here
+        // and with the host's clear, as the offset record's do: either of two racing values lies beyond the plan's)
+        if (need > (unsigned)k && need > h->sigma_worst) h->sigma_worst = need;
+    }
     const double sigma = (double)sigma_dev[0];
     const bool single_dim = flags & DAU_FLAG_SINGLE_DIM_KERNEL;
     const bool forbid_pos = flags & DAU_FLAG_FORBID_POSITIVE_DIM1;
@@ -68,17 +91,20 @@ __global__ void synth_filters_kernel(const float* __restrict__ sigma_dev, int k,
         taps[kTapGXR * kTapPitch + (k - 1 - lane)] = (float)gx;
         taps[kTapGYR * kTapPitch + (k - 1 - lane)] = (float)gy;
     }
+    // the record above is out before this kernel ends (the fence stands here, behind the work, where the stores have long left)
+    if (host_status && lane == 0) __threadfence_system();
 }
 
-void launch_synth_filters(hipStream_t st, const float* sigma_dev, int k, int flags, float* filters6) {
+void launch_synth_filters(hipStream_t st, const float* sigma_dev, int k, int flags, float* filters6, HostStatus* host_status,
+                          Status* status) {
     hipLaunchKernelGGL(synth_filters_kernel, dim3(1), dim3(64), 0, st, sigma_dev, k, flags, kFilterPlane, filters6,
-                       filters6 + kTaps1dOffset);
+                       filters6 + kTaps1dOffset, host_status, status);
 }
 
 // the six planes only, k*k floats each, back to back (dau_conv_filters: the caller's buffer, no scratch)
 void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k, int flags, float* planes6) {
     hipLaunchKernelGGL(synth_filters_kernel, dim3(1), dim3(64), 0, st, sigma_dev, k, flags, k * k, planes6,
-                       static_cast<float*>(nullptr));
+                       static_cast<float*>(nullptr), static_cast<HostStatus*>(nullptr), static_cast<Status*>(nullptr));
 }
 
 }  // namespace dau

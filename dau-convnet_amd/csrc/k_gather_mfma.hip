@@ -971,9 +971,9 @@ void tiled_gather_prepare(hipStream_t st, const TiledConfig& c, const float* in,
                            g.nwin1, window, g.strip_pitch, (int)(uts / 4), g.fb, reinterpret_cast<unsigned int*>(packed), guard);
         return;
     }
-    // Packed slices are padded to whole KiB; the padding is zeroed together with the payload.  The memset is not guarded:
+    // Packed slices are padded to whole KiB; the padding is zeroed together with the payload.  The clear is not guarded:
     // the candidate bucket sets of a call run one after the other in the same workspace, so it is harmless for the other.
-    (void)hipMemsetAsync(packed, 0, (size_t)nfb * c.Cin * uts, st);
+    launch_zero_words(st, packed, (size_t)nfb * c.Cin * uts);
     const long total = (long)nfb * c.Cin * c.G * g.fb;
     const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
     hipLaunchKernelGGL(pack_units_kernel, dim3(grid), dim3(256), 0, st, table, c.Cin, c.G, c.Cout, g.pitch, c.R, g.Rt, g.nwin1,

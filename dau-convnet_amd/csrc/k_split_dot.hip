@@ -61,6 +61,7 @@
 // The kernels of the line forms are named ld_*_kernel / line_dot_kernel (d4::line_dot_kernel, ...): tools and the built-code
 // tests pick the 2-D member's kernels by the names below.  EVERY __global__ function of this file is listed here.
 #if DAU_SD_1D
+#define sd_zero_kernel ld_zero_kernel
 #define sd_absmax_x_kernel ld_absmax_x_kernel
 #define sd_absmax_e_kernel ld_absmax_e_kernel
 #define sd_absmax_nhwc_e_kernel ld_absmax_nhwc_e_kernel
@@ -209,6 +210,14 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
 __device__ __forceinline__ void sd_mark_taken(const Guard& guard) {
     if constexpr (kSdLine) {
         if (guard.status && blockIdx.x == 0 && threadIdx.x == 0) const_cast<Status*>(guard.status)->pad2[1] = (unsigned)kSdRX;
+    }
+}
+
+// the pass's maxima and partial sums start from zero (unguarded, as the memsets it stands for were)
+__global__ void __launch_bounds__(256) sd_zero_kernel(unsigned* __restrict__ a, long na, unsigned* __restrict__ b, long nb) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < na + nb; i += (long)gridDim.x * 256L) {
+        if (i < na) a[i] = 0u;
+        else b[i - na] = 0u;
     }
 }
 
@@ -1353,8 +1362,10 @@ void split_dot_prepare(hipStream_t st, const SplitDotConfig& c, const float* x, 
     unsigned* xmax = reinterpret_cast<unsigned*>(ws + l.maxes_off);
     unsigned* emax = xmax + s.S * kNumK;
     float* xk = reinterpret_cast<float*>(ws + l.xk_off);
-    (void)hipMemsetAsync(xmax, 0, (size_t)(s.S * kNumK + s.F) * 4, st);
-    (void)hipMemsetAsync(ws + l.partial_off, 0, (size_t)g.chunks * kNumK * s.S * s.G * s.F * 4, st);
+    // (a kernel, not two memsets: in a replayed graph a memset node was seen to land among the maxima kernels that follow it --
+    // every fourth word of the maxima cleared late -- while kernel follows kernel in order)
+    hipLaunchKernelGGL(sd_zero_kernel, dim3(64), dim3(256), 0, st, xmax, (long)(s.S * kNumK + s.F),
+                       reinterpret_cast<unsigned*>(ws + l.partial_off), (long)g.chunks * kNumK * s.S * s.G * s.F);
     const int HW = s.H * s.W;
     const bool walks = sd_walks(c);
     h8* xs = reinterpret_cast<h8*>(ws + l.xs_off);

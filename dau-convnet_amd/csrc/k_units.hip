@@ -106,6 +106,19 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
     }
 }
 
+// n 32-bit words at p set to zero.  A kernel where a memset would do: in a replayed graph a memset node was seen to land among the
+// kernels enqueued behind it, while kernel follows kernel in stream order.
+__global__ void zero_words_kernel(unsigned int* __restrict__ p, long n) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+void launch_zero_words(hipStream_t st, void* p, size_t bytes) {
+    const long n = (long)(bytes / 4);                        // (every caller's region is whole words)
+    if (n <= 0) return;
+    const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+    hipLaunchKernelGGL(zero_words_kernel, dim3(grid), dim3(256), 0, st, static_cast<unsigned int*>(p), n);
+}
+
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
                           Status* status, HostStatus* host_status, int count_ignore, Status* line_status, bool line_dot) {

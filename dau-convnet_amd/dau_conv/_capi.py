@@ -6,6 +6,7 @@ PyTorch is used for device memory and the current HIP stream only.
 """
 import ctypes
 import os
+import sys
 
 import torch
 
@@ -105,6 +106,8 @@ def _load():
         lib.dau_conv_epilogue_backward.argtypes = [vp, vp, fp, fp, ctypes.c_int, fp, fp, vp, ctypes.c_size_t]
     if hasattr(lib, "dau_conv_forward_residual"):        # (likewise: the residual add of that epilogue)
         lib.dau_conv_forward_residual.argtypes = [vp, vp, fp, fp, fp, fp, fp, fp, fp, ctypes.c_int, fp, vp, ctypes.c_size_t]
+    if hasattr(lib, "dau_conv_sigma_status"):            # (likewise: the device's record of the support each call's sigma needed)
+        lib.dau_conv_sigma_status.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int32)] * 3
     lib.dau_conv_last_status.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]
     lib.dau_conv_filters.argtypes = [vp, vp, fp, fp]
     lib.dau_conv_unit_table.argtypes = [vp, vp, fp, fp, fp, ctypes.c_int, vp]
@@ -168,7 +171,36 @@ def _req(t, name, shape=None, dtype=torch.float32, memory_format=torch.contiguou
 # One grow-only workspace per (device, stream), shared by every plan: the layers of a network run one after the other on
 # a stream, so they can reuse the same scratch memory (a north-star sized layer needs 3 GB for its backward pass).  The
 # status word at the head of the workspace is read back by check_status() right after the call that wrote it.
+# A call made while its stream is being captured into a graph stays out of it (Plan._workspace).
 _SHARED_WS = {}
+
+
+def capturing(device):
+    """Is the current stream of this device being captured into a graph (torch.cuda.graph, make_graphed_callables, the cudagraph
+    trees of torch.compile)?  False for a CPU device and before the GPU has been initialised."""
+    if device.type != "cuda" or not torch.cuda.is_initialized():
+        return False
+    if device.index is None or device.index == torch.cuda.current_device():
+        return torch.cuda.is_current_stream_capturing()
+    with torch.cuda.device(device):
+        return torch.cuda.is_current_stream_capturing()
+
+
+def _pool_warmup(device):
+    """Is this an ordinary call that the cudagraph trees of torch.compile make to warm a graph up?  They run it with the allocator
+    already pointed at the graph's pool, and after it every tensor still alive in that pool must be an output of the graph: a shared
+    workspace created or grown now would be such a tensor.  (Asked only when one would have to be; torch._inductor is not imported.)
+    get_manager() and CUDAGraphTreeManager.in_warmup are internals of torch._inductor.cudagraph_trees, written against torch 2.10.  A
+    torch without them is not warming up in a way this can see: tests/test_gpu_graph_capture.py's cudagraphs-backend test then fails on
+    the trees' own check of their pool's live tensors.  Any other error is a real one and is raised."""
+    trees = sys.modules.get("torch._inductor.cudagraph_trees")
+    if trees is None:
+        return False
+    try:
+        manager = trees.get_manager(device.index, create_if_none_exists=False)
+        return manager is not None and bool(manager.in_warmup)
+    except AttributeError:
+        return False
 
 
 class Plan(object):
@@ -196,6 +228,10 @@ class Plan(object):
         _check(lib.dau_conv_plan_get_info(self._h, ctypes.byref(info)))
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}
         self._ws = {}
+        self._last_ws = None
+        self._warm = set()           # devices on which an ordinary (not captured) call has completed: its launch attributes are set
+        self.captured = False        # the most recent forward / backward call was made under stream capture
+        self._transient = False      # ... or as the warm-up of a graph whose pool must not keep its workspace (_pool_warmup)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -214,14 +250,49 @@ class Plan(object):
         return n.value
 
     def _workspace(self, which, device):
+        """The scratch memory of one pass (called with `device` current).  Under stream capture: a tensor of exactly the pass's size
+        from the capturing allocator, which the caller drops when the call returns -- the graph's private pool hands memory out again
+        in capture order, which is the order of the replay, so the pool holds the largest workspace of a model, not the sum; the
+        shared workspace is neither read, grown nor replaced, and no pass reads what another left in its workspace."""
         need = self._ws.get(which)
         if need is None:
             need = self._ws[which] = self.workspace_bytes(which)
+        self.captured = torch.cuda.is_current_stream_capturing()
+        self._transient = False
+        if self.captured:
+            if device.index not in self._warm:
+                # the first call of a plan on a device sets launch attributes behind a lock: not a stream operation
+                raise FailedPreconditionError("DAUConv: this plan has made no call on %s yet; run the layer once before capturing "
+                                              "(a plan's first call on a device sets its kernels' launch attributes)" % (device,))
+            return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
         key = (device, torch.cuda.current_stream(device).cuda_stream)
         ws = _SHARED_WS.get(key)
         if ws is None or ws.numel() < need:
+            if _pool_warmup(device):
+                self._transient = True       # a workspace of this call alone, as under capture: nothing of it outlives the call
+                return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
             ws = _SHARED_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
         return ws
+
+    def _called(self, ws, device):
+        """A forward / backward call has been enqueued with this workspace."""
+        if self.captured or self._transient:
+            self._last_ws = None     # the capture's workspace is not kept: it goes back to the graph's pool with the call
+            if not self.captured:
+                self._warm.add(device.index)
+        else:
+            self._last_ws = ws
+            self._warm.add(device.index)
+
+    def _status_ws(self, what):
+        """The workspace whose status block the last call wrote, for the queries that read it back after the call."""
+        if self.captured:
+            raise FailedPreconditionError(
+                "DAUConv: %s() reads the workspace of the plan's last call, and that call was captured into a graph (its workspace "
+                "belongs to the graph's pool); ask last_status() / sigma_status(), which read the plan's pinned mirror" % what)
+        if self._last_ws is None:
+            raise FailedPreconditionError("DAUConv: %s() before any forward / backward call of this plan that kept its workspace" % what)
+        return self._last_ws
 
     def epilogue_supported(self, epilogue=EPILOGUE_BIAS | EPILOGUE_RELU):
         """True if forward() takes this epilogue (EPILOGUE_* bits); raises InvalidArgumentError naming the reason otherwise: a plan
@@ -275,7 +346,7 @@ class Plan(object):
             else:
                 _check(lib.dau_conv_forward(self._h, _stream(dev), _ptr(x), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma), _ptr(y),
                                             _ptr(ws), ws.numel()))
-        self._last_ws = ws
+        self._called(ws, dev)
         return y
 
     def epilogue_backward(self, dy, y=None, relu=False, need_dbias=True, dz=None):
@@ -326,7 +397,7 @@ class Plan(object):
             _check(lib.dau_conv_backward(self._h, _stream(dev), _ptr(x), _ptr(dy), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma),
                                          _ptr(dx), _ptr(dw), _ptr(dmu1), _ptr(dmu2), _ptr(dsigma), _ptr(ws), ws.numel(),
                                          int(need_mask)))
-        self._last_ws = ws
+        self._called(ws, dev)
         return dx, dw, dmu1, dmu2, dsigma
 
     def backward_param_sums(self, x, dy, mu1, mu2, sigma, out=None):
@@ -345,7 +416,7 @@ class Plan(object):
             ws = self._workspace(PASS_BACKWARD, dev)
             _check(lib.dau_conv_backward_param_sums(self._h, _stream(dev), _ptr(x), _ptr(dy), _ptr(mu1), _ptr(mu2), _ptr(sigma),
                                                     _ptr(out), _ptr(ws), ws.numel()))
-        self._last_ws = ws
+        self._called(ws, dev)
         return out
 
     def finalize_param_grads(self, sums, w, need_mask=NEED_DW | NEED_DMU1 | NEED_DMU2 | NEED_DSIGMA):
@@ -367,7 +438,7 @@ class Plan(object):
     def check_status(self):
         """Sync + raise if the last call saw NaN or out-of-bucket offsets; returns max(|mu|)."""
         mx = ctypes.c_float()
-        dev = self._last_ws.device
+        dev = self._status_ws("check_status").device
         with torch.cuda.device(dev):
             _check(lib.dau_conv_check_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(mx)))
         return mx.value
@@ -376,7 +447,7 @@ class Plan(object):
         """Sync; -> (outlier_units, ring_taken) of the last call: the live units with max(|mu1|,|mu2|) > 3, and whether one of its
         gather-sum passes ran as the radius-3 GEMM plus the ring pass (FLAG_DENSE_SPLIT_OUTLIERS) rather than another member."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._last_ws.device
+        dev = self._status_ws("outlier_status").device
         with torch.cuda.device(dev):
             _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, bool(taken.value)
@@ -394,7 +465,7 @@ class Plan(object):
         of their pixel (counted by plans that hold a line member, FLAG_DENSE_SPLIT_LINE), and 4 or 8 if its gather-sum pass ran as the
         line member of that radius, 0 if another member did the work."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._last_ws.device
+        dev = self._status_ws("line_status").device
         with torch.cuda.device(dev):
             _check(lib.dau_conv_gather_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, taken.value
@@ -404,7 +475,7 @@ class Plan(object):
         do not lie on the row of their pixel (counted by plans that hold a line member of the gather-dot, FLAG_SPLIT_DOT_LINE), and
         4 or 8 if its parameter gradients ran as the line member of that radius, 0 if another member did the work."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._last_ws.device
+        dev = self._status_ws("dot_line_status").device
         with torch.cuda.device(dev):
             _check(lib.dau_conv_dot_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, taken.value
@@ -416,6 +487,17 @@ class Plan(object):
         mx, valid = ctypes.c_float(), ctypes.c_int32()
         _check(lib.dau_conv_last_status(self._h, ctypes.byref(mx), ctypes.byref(valid)))
         return mx.value if valid.value else None
+
+    def sigma_status(self):
+        """No sync: (needed, planned, worst_needed) prefilter supports.  planned: the plan's k (2*ceil(5*sigma_hint)+1); needed: what the
+        sigma of the most recent call asked for, as the device recorded it (0: non-finite or not positive; 19: beyond 17); worst_needed:
+        the largest `needed` above `planned` since this was last asked -- sticky, cleared by this call; 0: none.  A graph replay runs
+        no Python, so a sigma trained across a support boundary shows up here (dau_conv.check_pending_offsets() raises for it)."""
+        if not hasattr(lib, "dau_conv_sigma_status"):
+            return 0, self.info["blur_support"], 0
+        v = [ctypes.c_int32() for _ in range(3)]
+        _check(lib.dau_conv_sigma_status(self._h, *[ctypes.byref(c) for c in v]))
+        return tuple(c.value for c in v)
 
     def profile_begin(self):
         _check(lib.dau_conv_profile_begin(self._h))

@@ -80,20 +80,46 @@ def _read_sigma(sigma):
     return float(sigma.detach().reshape(-1)[0].item())
 
 
-def _sigma_hint(sigma):
-    if sigma.numel() != 1:
-        return _read_sigma(sigma)            # a full sigma tensor: the read _settings() performs on every eager call
+def _sigma_hint(sigma, every_call=False, like=None):
+    """every_call: read whatever the copy says, as a full sigma tensor is read (eager's _settings() without a sigma_hint).
+    Under stream capture nothing is read: the most recent copy kept for the tensor at this address, whatever its version counter
+    says -- the device records the support the call's sigma needs (Plan.sigma_status, check_pending_offsets).
+    like: what the op knows of its layer (device, parameter shape, kernel settings).  A graph runner that copies its inputs into
+    buffers of its own (the cudagraph trees behind torch.compile(backend="cudagraphs") do so with parameters) records the op with a
+    sigma at an address no call has read: it then takes the most recent copy an ordinary call `like` it kept -- the warm-up run of
+    the same graph, just before the recording.  LIMIT: two layers alike in all of that whose sigmas need different supports cannot
+    be told apart there (the op sees copies of every parameter): the one that ran earlier records with the later one's support.
+    Too few taps are reported by the device's record (check_pending_offsets raises); too many are a correct but wider truncation
+    than the eager layer's.  Runners that hand the op its own parameters (torch.cuda.graph, make_graphed_callables, Inductor's
+    trees, which treat parameters as static) never take this path."""
+    every_call = every_call or sigma.numel() != 1     # a full sigma tensor: the read _settings() performs on every eager call
     key = (sigma.data_ptr(), sigma.device.index)
     hit = _SIGMA_HOST.get(key)
-    if hit is not None and hit[0]() is sigma and hit[1] == sigma._version:
+    if not every_call and hit is not None and hit[0]() is sigma and hit[1] == sigma._version:
         _SIGMA_HOST.move_to_end(key)
+        if like is not None:                 # (the most recent ordinary call like this one, also when it read nothing)
+            _SIGMA_HOST[like] = (_NO_TENSOR, -1, hit[2])
+            _SIGMA_HOST.move_to_end(like)
+        return hit[2]
+    if _capi.capturing(sigma.device):
+        if hit is None and like is not None:
+            hit = _SIGMA_HOST.get(like)
+        if hit is None:
+            raise _capi.FailedPreconditionError("DAUConv: no host copy of sigma yet; run the layer once before capturing")
         return hit[2]
     value = _read_sigma(sigma)
     _SIGMA_HOST[key] = (weakref.ref(sigma), sigma._version, value)
     _SIGMA_HOST.move_to_end(key)
+    if like is not None:
+        _SIGMA_HOST[like] = (_NO_TENSOR, -1, value)
+        _SIGMA_HOST.move_to_end(like)
     while len(_SIGMA_HOST) > _SIGMA_HOST_MAX:
         _SIGMA_HOST.popitem(last=False)
     return value
+
+
+def _NO_TENSOR():
+    return None
 
 
 def _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
@@ -103,7 +129,9 @@ def _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_t
         raise _capi.InvalidArgumentError("dense_split must be -1, 0, 1, 2 or 3 and check_offsets \"async\", \"on\" or \"off\"")
     st = _impl._settings(sigma, number_units_ignore=number_units_ignore, num_output=w.shape[-1], kernel_size=kernel_size,
                          unit_testing=unit_testing, mu_learning_rate_factor=mu_learning_rate_factor, single_dim_kernel=single_dim_kernel,
-                         forbid_positive_dim1=forbid_positive_dim1, use_interpolation=use_interpolation, sigma_hint=_sigma_hint(sigma),
+                         forbid_positive_dim1=forbid_positive_dim1, use_interpolation=use_interpolation,
+                         sigma_hint=_sigma_hint(sigma, like=("like", sigma.device.index, tuple(w.shape), kernel_size, number_units_ignore,
+                                                             single_dim_kernel, forbid_positive_dim1, use_interpolation)),
                          check_offsets=_UNCHECK[check_offsets], algo=algo & ~_LINE_GRADS, dense_line_grads=bool(algo & _LINE_GRADS), dense_split=_UNSPLIT[dense_split][0],
                          dense_line=_UNSPLIT[dense_split][1], dense_outliers=dense_outliers, **_layout_settings(dense_bf16, channels_last))
     if input_relu:

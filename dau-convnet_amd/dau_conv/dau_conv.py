@@ -32,7 +32,7 @@ import torch.nn as nn
 from . import _capi
 
 __all__ = ["DAUGridMean", "ZeroNLast", "DAUConv2d", "DAUConv1d", "dau_conv2d", "dau_conv1d", "dau_conv",
-           "dau_conv_grad", "check_pending_offsets", "is_channels_last"]
+           "dau_conv_grad", "check_pending_offsets", "is_channels_last", "release_captured_plans"]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -45,6 +45,36 @@ __all__ = ["DAUGridMean", "ZeroNLast", "DAUConv2d", "DAUConv1d", "dau_conv2d", "
 # offset-bucket hint and its pending status.  The cache is bounded; a dropped plan is asked for its status first.
 _PLANS = collections.OrderedDict()
 _PLAN_CACHE_MAX = 64
+# The keys of the plans a call has used while its stream was being captured into a graph (torch.cuda.graph, make_graphed_callables,
+# the cudagraph trees of torch.compile).  Every replay of such a graph writes the plan's pinned status mirror, which dies with the
+# plan: these plans stay in _PLANS, the eviction skips them and they do not count against _PLAN_CACHE_MAX, until
+# release_captured_plans().
+_PINNED = set()
+
+
+def _pin(plan):
+    """A captured call has used this plan: keep it (a plan made outside the cache has no key and is its caller's to keep)."""
+    key = getattr(plan, "_cache_key", None)
+    if key is not None and _PLANS.get(key) is plan:
+        _PINNED.add(key)
+
+
+def _evict():
+    """Drop the least recently used plans that no captured graph uses until the others number _PLAN_CACHE_MAX at most."""
+    if _PINNED:
+        _PINNED.intersection_update(_PLANS.keys())   # (a cache that was emptied by hand takes its pins with it)
+    while len(_PLANS) - len(_PINNED) > _PLAN_CACHE_MAX:
+        key = next(iter(_PLANS)) if not _PINNED else next(k for k in _PLANS if k not in _PINNED)
+        old = _PLANS.pop(key)
+        old.last_status()        # a NaN / out-of-range offset it has seen and not yet reported is raised here, not lost
+
+
+def release_captured_plans():
+    """For a caller who has deleted their graphs: the plans that captured calls have used are ordinary cache entries again (and the
+    oldest are dropped if the cache is over its bound).  A graph that is replayed after this may write the freed status mirror of a
+    dropped plan: call it only when no such graph is left."""
+    _PINNED.clear()
+    _evict()
 
 
 def is_channels_last(t):
@@ -192,9 +222,8 @@ def _get_plan_with(x, w, settings, nhwc, extra_flags):
                       "kernels (the tiled MFMA kernels do not support this shape); expect them to be orders of magnitude slower"
                       % (N, S, F, H, W, G, settings["kernel_size"], " and the ".join(which)), RuntimeWarning, stacklevel=3)
     _PLANS[key] = plan
-    while len(_PLANS) > _PLAN_CACHE_MAX:
-        _, old = _PLANS.popitem(last=False)
-        old.last_status()        # a NaN / out-of-range offset it has seen and not yet reported is raised here, not lost
+    plan._cache_key = key
+    _evict()
     return plan
 
 
@@ -215,10 +244,21 @@ def _check_after(plan, mode):
 
 def check_pending_offsets(device=None):
     """Wait for the device and raise if any plan's latest call saw a NaN / out-of-range offset (for check_offsets="async"
-    users: call at the end of a step or before reading results)."""
+    users: call at the end of a step or before reading results) -- or a sigma that needs a wider prefilter than the plan holds
+    (FailedPreconditionError).  The second cannot happen to eager calls, which choose their plan from a fresh host copy of sigma; it
+    is what a replayed graph must be asked for: its plans' supports are frozen at capture, no Python runs in a replay, and the device
+    records what each call's sigma would have needed (Plan.sigma_status()).  A sigma that needs LESS than the plan holds is no
+    error: the wider support is still a correct truncation.  Either record is reported once."""
     torch.cuda.synchronize(device)
     for plan in list(_PLANS.values()):
         plan.last_status()
+    for plan in list(_PLANS.values()):
+        _, planned, worst = plan.sigma_status()
+        if worst > planned:
+            raise _capi.FailedPreconditionError(
+                "DAUConv: sigma has grown beyond the prefilter support of a captured plan: a call needed %d x %d taps "
+                "(2*ceil(5*sigma)+1), the plan holds %d x %d (N=%d C=%d->%d %dx%d).  A replayed graph keeps the plan it was "
+                "captured with: capture again" % (worst, worst, planned, planned, plan.N, plan.S, plan.F, plan.H, plan.W))
 
 
 def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, num_output=64, kernel_size=9, pad=4,
@@ -243,8 +283,9 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
     if not unit_normalization or square_unit_normalization:
         raise _capi.InvalidArgumentError("only unit_normalization=True, square_unit_normalization=False is implemented")
     if sigma_hint is None:
-        # same host read of sigma[0] the reference performs in LayerSetUp (base_dau_conv_layer.cpp:140-143)
-        sigma_hint = float(sigma[(0,) * sigma.dim()].item())
+        # same host read of sigma[0] the reference performs in LayerSetUp (base_dau_conv_layer.cpp:140-143); under stream capture
+        # the copy the last such read of this tensor left (_ops._sigma_hint)
+        sigma_hint = _ops._sigma_hint(sigma, every_call=True)
     if grad_reduce not in ("mean", "sum"):
         raise _capi.InvalidArgumentError("grad_reduce must be \"mean\" or \"sum\"")
     # "async" or a truth value (1, 1.0, numpy.bool_ ... count as True): nothing else reaches _check_before / _check_after
@@ -295,10 +336,25 @@ def _forward(plan, st, input, weights, mu1, mu2, sigma, bias=None, relu=False, r
     input = _act(input, plan)
     if residual is not None:
         residual = _act(residual, plan)
-    _check_before(plan, st["check_offsets"])
+    mode = _check_mode(st, input)
+    _check_before(plan, mode)
     y = plan.forward(input, weights, mu1, mu2, sigma, bias=bias, relu=relu, residual=residual)
-    _check_after(plan, st["check_offsets"])
+    if plan.captured:
+        _pin(plan)
+    _check_after(plan, mode)
     return y, input
+
+
+def _check_mode(st, input):
+    """check_offsets of this call, and the refusals of a call under stream capture: check_offsets=True waits for the stream, which a
+    capture cannot, and runs as "async" there; process_group= runs an all-reduce."""
+    mode = st["check_offsets"]
+    if (mode is True or st["process_group"] is not None) and _capi.capturing(input.device):
+        if st["process_group"] is not None:
+            raise _capi.InvalidArgumentError("DAUConv: a process_group= layer cannot be captured into a graph (its backward runs an "
+                                             "all-reduce on a stream of its own); capture the layer without process_group=")
+        return "async"
+    return mode
 
 
 def _need_mask(needs_input_grad):
@@ -311,7 +367,8 @@ def _backward(plan, st, input, grad, weights, mu1, mu2, sigma, need, y=None, rel
     """-> (the gradient of the sum, dbias, (dx, dw, dmu1, dmu2, dsigma)), for a caller that wants at least one of them.  input as
     _forward returned it; relu / need_dbias: backward of the fused epilogue, from the forward's y.  The residual joins the sum
     before the activation, so its gradient IS the first result (dz, or grad in the plan's layout without a ReLU)."""
-    _check_before(plan, st["check_offsets"])
+    mode = _check_mode(st, input)
+    _check_before(plan, mode)
     grad = _act(grad, plan)
     dbias = None
     if need_dbias or relu:
@@ -326,7 +383,9 @@ def _backward(plan, st, input, grad, weights, mu1, mu2, sigma, need, y=None, rel
         out = _data_parallel_backward(plan, input, grad, weights, mu1, mu2, sigma, need, group, st["grad_reduce"])
     else:
         out = plan.backward(input, grad, weights, mu1, mu2, sigma, need)
-    _check_after(plan, st["check_offsets"])
+    if plan.captured:
+        _pin(plan)
+    _check_after(plan, mode)
     return grad, dbias, out
 
 
@@ -637,8 +696,13 @@ class DAUConv2d(nn.Module):
     Additions: `in_channels` (build the variables at construction), `algo`, and `check_offsets`: how the op's offset
     preconditions (NaN, |mu| beyond the kernel; dau_conv_op.cpp:250-262) are enforced -- "async" (default): read the
     previous call's on-device result from pinned host memory before each call, no stall, errors surface one call late
-    (`dau_conv.check_pending_offsets()` flushes); True: wait for every call and raise at once, as the reference does;
-    False: never read the result back.  `dense_split` (None: the library's choice, True: always, False: never): calls whose
+    (`dau_conv.check_pending_offsets()` flushes); True: wait for every call and raise at once, as the reference does
+    (a call under stream capture cannot wait: there True behaves as "async");
+    False: never read the result back.  Graph capture (`torch.cuda.graph`, `make_graphed_callables`, the cudagraph trees of
+    torch.compile): run the layer once before capturing; a captured call reads no sigma on the host, takes its workspace from the
+    graph's pool and pins its plan (`dau_conv.release_captured_plans()`); the plan and its prefilter support are frozen in the graph,
+    and `dau_conv.check_pending_offsets()` also raises when a replay's sigma needed more taps than the plan holds; a `process_group=`
+    layer cannot be captured.  `dense_split` (None: the library's choice, True: always, False: never): calls whose
     offsets lie within +-2 / +-3 / +-4 run their two gather-sum passes as a densified GEMM on the f16 matrix cores with both
     operands split into two binary16 limbs -- fp32 accuracy (the exact kernels' parity bar), about 1.7x faster at four units per
     channel pair; by default a plan holds the radii that pay for its unit count.  Every image is scaled on its own, so an output
@@ -897,6 +961,12 @@ class DAUConv2d(nn.Module):
             # set_dau_variables_manually): the reference re-reads sigma every time it builds its layer (:140-146)
             tag = (s._version, s.data_ptr())
             if self._sigma_host is None or self._sigma_tag != tag:
+                if _capi.capturing(s.device):
+                    # no host read under stream capture: the most recent copy, whatever the version counter says -- the device
+                    # records the support this call's sigma needs (Plan.sigma_status, check_pending_offsets)
+                    if self._sigma_host is None:
+                        raise _capi.FailedPreconditionError("DAUConv: no host copy of sigma yet; run the layer once before capturing")
+                    return s.reshape(1, 1, 1, 1).expand(self._param_shape), self._sigma_host
                 self._sigma_host = float(s.detach().reshape(-1)[0].item())
                 self._sigma_tag = tag
             return s.reshape(1, 1, 1, 1).expand(self._param_shape), self._sigma_host

@@ -79,9 +79,19 @@
  * of a slabbed pass are bit-identical to the whole-batch pass (images are independent).
  *
  * HIP graphs.  After one ordinary call (which sets the kernels' launch attributes) forward and
- * backward only enqueue kernels and one 16-byte memset on the caller's stream, so they can be
+ * backward only enqueue kernels on the caller's stream (what a pass clears in its workspace it clears with a kernel), so they can be
  * captured into a graph; the bucket candidates are frozen at capture time, the device-side
- * guards still pick the kernels the replay's offsets need.
+ * guards still pick the kernels the replay's offsets need.  A plan's prefilter support k is frozen
+ * too, like its bucket candidates: it was chosen from sigma_hint when the plan was made, the taps
+ * are computed from the device's sigma on every call, and a replay runs no host code that could
+ * choose another plan when a trained sigma crosses a support boundary.  The device therefore
+ * records, in the plan's pinned mirror, the support each call's sigma would have needed; a caller
+ * who replays must ask dau_conv_sigma_status (and dau_conv_last_status for the offsets) and capture
+ * again with a new plan when more was needed than the plan holds.  A captured call may use a
+ * workspace of its own that is released after the capture in capture order: no pass reads what an
+ * earlier call left in its workspace.  The plan must outlive every graph that holds a call of it
+ * (each replay writes its mirror), and the queries that read a workspace back
+ * (dau_conv_check_status and the _status entries that take one) need that workspace to be alive.
  */
 #ifndef DAU_CONV_H_
 #define DAU_CONV_H_
@@ -451,6 +461,16 @@ DAU_API int dau_conv_dot_line_status(const dau_conv_plan *plan, void *stream, co
  * call (valid_out = 0 when none has completed yet).  A caller that checks this before each call learns of a bad offset
  * at most a few calls late, without ever stalling the stream. */
 DAU_API int dau_conv_last_status(const dau_conv_plan *plan, float *max_abs_mu_out, int32_t *valid_out);
+
+/* The prefilter support against the sigma the calls really saw, without waiting, from pinned host memory: planned_out = the plan's k
+ * (2*ceil(5*sigma_hint)+1, dau_conv_plan_info.blur_support); needed_out = what the sigma of the most recent call needs by the same
+ * rule, computed on the device from the tensor the call was given (0: not a positive finite number; any support beyond 17 reads 19);
+ * worst_needed_out = the largest such value ABOVE the plan's k that any call has recorded since this function last returned --
+ * sticky, and cleared by this call; 0: none.  A call whose sigma needs more than the plan holds has run with too few taps: make a
+ * plan from the new sigma (and capture again if the call was replayed from a graph).  needed_out < planned_out is no error: the
+ * wider support is still a correct truncation.  A host that sees a call's status in dau_conv_last_status sees its record here.
+ * All three pointers are required (DAU_INVALID_ARGUMENT otherwise); a plan created without a device answers 0, k, 0. */
+DAU_API int dau_conv_sigma_status(const dau_conv_plan *plan, int32_t *needed_out, int32_t *planned_out, int32_t *worst_needed_out);
 
 /* Building blocks exposed for parity tests (device pointers in and out).
  * filters_out: 6 planes of k*k floats in the order Gn, Dw, Dmu1, Dmu2, Dsigma, Gerr.
