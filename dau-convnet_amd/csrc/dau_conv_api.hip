@@ -275,6 +275,12 @@ struct ProfScope {
 // results never depend on the hint.  This replaces the reference's blocking amax + D2H copy per call (dau_conv_op.cpp:223-253)
 // and makes a layer with a large max_kernel_size but small offsets run the small-offset kernels (the reference's tests rely on
 // that, dau_conv_test.py:433,436).
+// That holds for the gather-sum passes (y, dx), whose sums run over the units of one output element in the table's order whatever
+// the tile: every set gives the same bits.  The tiled gather-dot sums over the positions of a region, and the regions differ from
+// set to set: its bits depend on the set.  The parameter-gradient pass therefore takes no hint: it enqueues EVERY set that holds the
+// kernel, smallest first, each guarded by its own range of offsets, so that the set that runs -- the smallest that covers the
+// call's max|mu| -- depends on the call alone, whatever other layers, streams or threads that share the plan left in the mirror
+// (tests/test_gpu_concurrency.py).  It is the set a hint from the call's own previous offsets chose.
 struct Candidate {
     const BucketSet* set;
     Guard guard;
@@ -318,7 +324,7 @@ int status_error(const dau_conv_plan* p, float mx, bool nan_seen) {
 // With line members (DAU_FLAG_DENSE_SPLIT_LINE): they go first, under (-1, 4] and (4, 8], and run where the call's table has no unit
 // off the line; every member that follows and shares offsets with them runs there only where it has one -- the flag-off plan's kernels.
 // The line members of the gather-dot (DAU_FLAG_SPLIT_DOT_LINE) likewise, on the count of the pass's own bare table (run_param_sums).
-constexpr int kMaxCandidates = 9;
+constexpr int kMaxCandidates = 14;   // (the most: 2 line + 2 ahead + the radius-4 dense member + 7 bucket sets, in a parameter-gradient pass)
 int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
     const BucketSet* s0 = &p->sets[0];
@@ -366,7 +372,11 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
         }
     }
     if (s0->has[kDense4[kind]] && hinted != s0 && s0 != top) add(s0, kDense4[kind], (float)s0->bucket);
-    if (hinted && lo < (float)hinted->bucket) add(hinted, member_of(hinted), (float)hinted->bucket);
+    if (kind == kGatherDot) {                                // by the call's own offsets alone (see Candidate)
+        for (int i = 0; i + 1 < p->nsets; ++i)
+            if (p->sets[i].has[kFirst[kind]] && lo < (float)p->sets[i].bucket)
+                add(&p->sets[i], member_of(&p->sets[i]), (float)p->sets[i].bucket);
+    } else if (hinted && lo < (float)hinted->bucket) add(hinted, member_of(hinted), (float)hinted->bucket);
     if (n == 0) return 1;                                    // no hint, nothing dense: the static set, unguarded
     add(top, member_of(top), INFINITY);
     return n;

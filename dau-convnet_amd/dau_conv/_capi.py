@@ -4,9 +4,11 @@ This is the only route from Python into the operator: there is no CPU or eager-P
 fallback.  If the HIP library is missing the import fails loudly.
 PyTorch is used for device memory and the current HIP stream only.
 """
+import collections
 import ctypes
 import os
 import sys
+import threading
 
 import torch
 
@@ -203,8 +205,26 @@ def _pool_warmup(device):
         return False
 
 
+# What a plan remembers of a forward / backward call: the workspace it kept (None: the call's own, gone with it), and whether the call
+# was made under stream capture / as the warm-up of a graph's pool
+_Call = collections.namedtuple("_Call", "ws captured transient")
+_NO_CALL = _Call(None, False, False)
+
+
 class Plan(object):
-    """Owns one dau_conv_plan; scratch memory comes from the per-stream shared workspace."""
+    """Owns one dau_conv_plan; scratch memory comes from the per-stream shared workspace.
+
+    Streams and threads.  The dau_conv_plan itself is immutable, and one Plan is shared by every layer of a shape (the cache of
+    dau_conv.py), so it may be called from several streams and host threads at once: each (device, stream) has a workspace of its
+    own, and ctypes releases the GIL during a call.  What a Plan remembers of "the last call" -- `captured`, and the workspace whose
+    status block check_status(), outlier_status(), line_status() and dot_line_status() read back -- is therefore kept per
+    (device, stream), and every host thread asks about the stream of ITS most recent call: a thread that calls forward() and then
+    check_status() gets the status of its own call, whatever other threads have enqueued on other streams in between.  The
+    backward pass of autograd runs on a thread of torch's, on the stream of the forward call: it updates that stream's record, so
+    the thread that called .backward() sees the backward call, as a single-threaded caller always did.  A thread that has made no
+    call of its own is answered from the most recent call of any thread.  Two threads that call one plan on the SAME stream share
+    that stream's workspace and record: the later call's status replaces the earlier one's, as with two calls of one thread.
+    last_status() and sigma_status() read the plan's pinned mirror and belong to the plan, not to a stream."""
 
     def __init__(self, N, S, F, G, H, W, max_kernel_size=9, number_units_ignore=0, flags=FLAG_USE_INTERPOLATION,
                  algo=ALGO_AUTO, sigma_hint=0.5, mu_learning_rate_factor=1.0, device=None):
@@ -228,16 +248,35 @@ class Plan(object):
         _check(lib.dau_conv_plan_get_info(self._h, ctypes.byref(info)))
         self.info = {n: getattr(info, n) for n, _ in _Info._fields_}
         self._ws = {}
-        self._last_ws = None
         self._warm = set()           # devices on which an ordinary (not captured) call has completed: its launch attributes are set
-        self.captured = False        # the most recent forward / backward call was made under stream capture
-        self._transient = False      # ... or as the warm-up of a graph whose pool must not keep its workspace (_pool_warmup)
+        self._calls = {}             # (device index, stream handle) -> _Call: the most recent forward / backward call made there
+        self._tls = threading.local()    # .key: where the calling thread made its most recent call; .pending: its call in the making
+        self._any_key = None         # where any thread made the most recent call (for a thread that has made none)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h and lib is not None:        # at interpreter shutdown the module globals may already be gone
             lib.dau_conv_plan_destroy(h)
             self._h = None
+
+    def _call(self):
+        """The record the calling thread asks about: of the stream of its own most recent call, else of any thread's."""
+        return self._calls.get(getattr(self._tls, "key", None) or self._any_key, _NO_CALL)
+
+    @property
+    def captured(self):
+        """The most recent forward / backward call (of this thread: see the class) was made under stream capture"""
+        return self._call().captured
+
+    @property
+    def _transient(self):
+        """... or as the warm-up of a graph whose pool must not keep its workspace (_pool_warmup)"""
+        return self._call().transient
+
+    @property
+    def _last_ws(self):
+        """The workspace that call kept (None: it kept none)"""
+        return self._call().ws
 
     @property
     def io_layout(self):
@@ -257,42 +296,43 @@ class Plan(object):
         need = self._ws.get(which)
         if need is None:
             need = self._ws[which] = self.workspace_bytes(which)
-        self.captured = torch.cuda.is_current_stream_capturing()
-        self._transient = False
-        if self.captured:
+        captured = torch.cuda.is_current_stream_capturing()
+        key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+        self._tls.pending = (key, captured, False)       # (the calling thread's: the GIL is released during the library call)
+        if captured:
             if device.index not in self._warm:
                 # the first call of a plan on a device sets launch attributes behind a lock: not a stream operation
                 raise FailedPreconditionError("DAUConv: this plan has made no call on %s yet; run the layer once before capturing "
                                               "(a plan's first call on a device sets its kernels' launch attributes)" % (device,))
             return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-        key = (device, torch.cuda.current_stream(device).cuda_stream)
-        ws = _SHARED_WS.get(key)
+        shared = (device, key[1])
+        ws = _SHARED_WS.get(shared)
         if ws is None or ws.numel() < need:
             if _pool_warmup(device):
-                self._transient = True       # a workspace of this call alone, as under capture: nothing of it outlives the call
+                self._tls.pending = (key, False, True)   # a workspace of this call alone, as under capture: nothing of it outlives the call
                 return torch.empty(max(need, 1), dtype=torch.uint8, device=device)
-            ws = _SHARED_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+            ws = _SHARED_WS[shared] = torch.empty(need, dtype=torch.uint8, device=device)
         return ws
 
     def _called(self, ws, device):
-        """A forward / backward call has been enqueued with this workspace."""
-        if self.captured or self._transient:
-            self._last_ws = None     # the capture's workspace is not kept: it goes back to the graph's pool with the call
-            if not self.captured:
-                self._warm.add(device.index)
-        else:
-            self._last_ws = ws
+        """A forward / backward call has been enqueued with this workspace (by the thread that asked _workspace for it)."""
+        key, captured, transient = self._tls.pending
+        # (the capture's workspace is not kept: it goes back to the graph's pool with the call)
+        self._calls[key] = _Call(None if captured or transient else ws, captured, transient)
+        self._tls.key = self._any_key = key
+        if not captured:
             self._warm.add(device.index)
 
     def _status_ws(self, what):
         """The workspace whose status block the last call wrote, for the queries that read it back after the call."""
-        if self.captured:
+        call = self._call()          # (one look: another thread may make a call on the same stream while this one asks)
+        if call.captured:
             raise FailedPreconditionError(
                 "DAUConv: %s() reads the workspace of the plan's last call, and that call was captured into a graph (its workspace "
                 "belongs to the graph's pool); ask last_status() / sigma_status(), which read the plan's pinned mirror" % what)
-        if self._last_ws is None:
+        if call.ws is None:
             raise FailedPreconditionError("DAUConv: %s() before any forward / backward call of this plan that kept its workspace" % what)
-        return self._last_ws
+        return call.ws
 
     def epilogue_supported(self, epilogue=EPILOGUE_BIAS | EPILOGUE_RELU):
         """True if forward() takes this epilogue (EPILOGUE_* bits); raises InvalidArgumentError naming the reason otherwise: a plan
@@ -438,18 +478,20 @@ class Plan(object):
     def check_status(self):
         """Sync + raise if the last call saw NaN or out-of-bucket offsets; returns max(|mu|)."""
         mx = ctypes.c_float()
-        dev = self._status_ws("check_status").device
+        ws = self._status_ws("check_status")
+        dev = ws.device
         with torch.cuda.device(dev):
-            _check(lib.dau_conv_check_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(mx)))
+            _check(lib.dau_conv_check_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(mx)))
         return mx.value
 
     def outlier_status(self):
         """Sync; -> (outlier_units, ring_taken) of the last call: the live units with max(|mu1|,|mu2|) > 3, and whether one of its
         gather-sum passes ran as the radius-3 GEMM plus the ring pass (FLAG_DENSE_SPLIT_OUTLIERS) rather than another member."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._status_ws("outlier_status").device
+        ws = self._status_ws("outlier_status")
+        dev = ws.device
         with torch.cuda.device(dev):
-            _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
+            _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, bool(taken.value)
 
     def split_dot_geometry(self):
@@ -465,9 +507,10 @@ class Plan(object):
         of their pixel (counted by plans that hold a line member, FLAG_DENSE_SPLIT_LINE), and 4 or 8 if its gather-sum pass ran as the
         line member of that radius, 0 if another member did the work."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._status_ws("line_status").device
+        ws = self._status_ws("line_status")
+        dev = ws.device
         with torch.cuda.device(dev):
-            _check(lib.dau_conv_gather_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
+            _check(lib.dau_conv_gather_line_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, taken.value
 
     def dot_line_status(self):
@@ -475,9 +518,10 @@ class Plan(object):
         do not lie on the row of their pixel (counted by plans that hold a line member of the gather-dot, FLAG_SPLIT_DOT_LINE), and
         4 or 8 if its parameter gradients ran as the line member of that radius, 0 if another member did the work."""
         units, taken = ctypes.c_int32(), ctypes.c_int32()
-        dev = self._status_ws("dot_line_status").device
+        ws = self._status_ws("dot_line_status")
+        dev = ws.device
         with torch.cuda.device(dev):
-            _check(lib.dau_conv_dot_line_status(self._h, _stream(dev), _ptr(self._last_ws), ctypes.byref(units), ctypes.byref(taken)))
+            _check(lib.dau_conv_dot_line_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
         return units.value, taken.value
 
     def last_status(self):

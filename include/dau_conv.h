@@ -70,7 +70,20 @@
  * (read from the pinned mirror, no sync) plus the largest set, each guarded on the device by
  * THIS call's max|mu|, so exactly one does the work and results never depend on the hint (with
  * DAU_FLAG_DENSE_BF16 the bucket-4 member, the only one with bf16 arithmetic, is enqueued as a guarded
- * candidate on EVERY call, so that too is decided by the call's own offsets alone).
+ * candidate on EVERY call, so that too is decided by the call's own offsets alone).  That is the rule of the
+ * gather-sum passes (y, dx), whose sums do not depend on the tile: every set gives the same bits.  The tiled
+ * parameter-gradient kernel sums over regions that differ from set to set, so its bits depend on the set: that
+ * pass takes no hint and enqueues every set it holds, each guarded by its own range of offsets -- the smallest
+ * set that covers THIS call's max|mu| runs.  So all six results of a call are, bit for bit, a function of the
+ * call's own arguments, whatever other calls, streams or threads that share the plan left in the mirror.
+ *
+ * Streams and threads.  One plan; any number of streams and host threads; one workspace per call in flight.  Per
+ * workspace: the status block a call writes, hence dau_conv_check_status and the _status queries that take a
+ * workspace -- they report the call that used THAT workspace, whatever ran beside it.  Per plan, shared by all its
+ * callers: the pinned mirror -- the most recent completed call (of any stream: the hint, and what
+ * dau_conv_last_status reports without an error), the sticky bad-offset record (an error of any stream stays
+ * until dau_conv_last_status, or dau_conv_check_status on the workspace of the bad call, has returned it once)
+ * and the sigma record.  dau_conv_last_error is per host thread.
  *
  * Workspace.  Every pass stages its input before it gathers.  Where the staged copy of the
  * whole batch would exceed 12 GB (DAU_WORKSPACE_BUDGET_GB in the environment at plan

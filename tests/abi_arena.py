@@ -11,6 +11,12 @@ ELEMENTS off their 256-byte alignment; parameters stay aligned.
 
 The harness calls the library through ctypes itself (dau_conv._capi.lib), on torch's current stream; dau_conv._capi.Plan only
 creates the plan.
+
+forward(), backward() and param_sums_finalize() run one call to its end.  Each is also there in two halves for the tests that keep
+several calls of one plan in flight (test_gpu_concurrency.py): enqueue_forward() / enqueue_backward() /
+enqueue_param_sums_finalize() build the arena on torch's current stream -- which is what makes an arena belong to a stream and,
+inside a threading.Thread, to that thread -- call the library and return (arena, rc, requested) without waiting; Arena.finish(rc,
+requested) waits for the device and reads everything back.
 """
 import ctypes
 from collections import OrderedDict, namedtuple
@@ -173,13 +179,22 @@ class Arena(object):
         return rep
 
 
+def enqueue_forward(capi, plan, inputs, io="f32", skew=0, fill=0xFF, declared_short=0, arena=None):
+    """The enqueue half of forward(): an arena on torch's current stream, dau_conv_forward on that stream -> (arena, rc, requested).
+    Nothing waits for the call; arena.finish(rc, requested) does, and a test that wants several calls in flight finishes none
+    before it has enqueued them all.  arena: one the caller built earlier with the same arguments (building one uploads its inputs,
+    which makes the host wait for the stream), so that a burst of calls is enqueued with nothing between them."""
+    a = arena or Arena(capi, plan, inputs, io, capi.PASS_FORWARD, skew, fill)
+    rc = capi.lib.dau_conv_forward(plan._h, a.stream, a.ptr("x"), a.ptr("w"), a.ptr("mu1"), a.ptr("mu2"), a.ptr("sigma"), a.ptr("y"),
+                                   a.ptr("workspace"), a.ws_bytes - declared_short)
+    return a, rc, ("y",) if rc == capi.DAU_OK else ()
+
+
 def forward(capi, plan, inputs, io="f32", skew=0, fill=0xFF, declared_short=0, outlier_status=False):
     """dau_conv_forward in an arena of its own -> Report (declared_short: bytes by which the declared workspace size is reduced;
     outlier_status: also dau_conv_gather_outlier_status on the arena's workspace -> report.outliers = (units, ring_taken))"""
-    a = Arena(capi, plan, inputs, io, capi.PASS_FORWARD, skew, fill)
-    rc = capi.lib.dau_conv_forward(plan._h, a.stream, a.ptr("x"), a.ptr("w"), a.ptr("mu1"), a.ptr("mu2"), a.ptr("sigma"), a.ptr("y"),
-                                   a.ptr("workspace"), a.ws_bytes - declared_short)
-    rep = a.finish(rc, ("y",) if rc == capi.DAU_OK else ())
+    a, rc, requested = enqueue_forward(capi, plan, inputs, io, skew, fill, declared_short)
+    rep = a.finish(rc, requested)
     if outlier_status:
         rep.outliers = _outlier_status(capi, plan, a)
     return rep
@@ -190,16 +205,22 @@ def _requested(capi, need_mask):
     return tuple(n for n, b in bits if need_mask & b)
 
 
-def backward(capi, plan, inputs, io="f32", skew=0, fill=0xFF, need_mask=None, declared_short=0, outlier_status=False):
-    """dau_conv_backward in an arena of its own; a gradient that need_mask does not request is passed as NULL -> Report
-    (outlier_status: also dau_conv_gather_outlier_status on the arena's workspace -> report.outliers = (units, ring_taken))"""
+def enqueue_backward(capi, plan, inputs, io="f32", skew=0, fill=0xFF, need_mask=None, declared_short=0, arena=None):
+    """The enqueue half of backward() -> (arena, rc, requested); see enqueue_forward"""
     need_mask = capi.NEED_ALL if need_mask is None else need_mask
-    a = Arena(capi, plan, inputs, io, capi.PASS_BACKWARD, skew, fill)
+    a = arena or Arena(capi, plan, inputs, io, capi.PASS_BACKWARD, skew, fill)
     req = _requested(capi, need_mask)
     rc = capi.lib.dau_conv_backward(plan._h, a.stream, a.ptr("x"), a.ptr("dy"), a.ptr("w"), a.ptr("mu1"), a.ptr("mu2"), a.ptr("sigma"),
                                     *([a.ptr(n, n in req) for n in ("dx",) + GRADS] + [a.ptr("workspace"), a.ws_bytes - declared_short,
                                                                                       int(need_mask)]))
-    rep = a.finish(rc, req if rc == capi.DAU_OK else ())
+    return a, rc, req if rc == capi.DAU_OK else ()
+
+
+def backward(capi, plan, inputs, io="f32", skew=0, fill=0xFF, need_mask=None, declared_short=0, outlier_status=False):
+    """dau_conv_backward in an arena of its own; a gradient that need_mask does not request is passed as NULL -> Report
+    (outlier_status: also dau_conv_gather_outlier_status on the arena's workspace -> report.outliers = (units, ring_taken))"""
+    a, rc, requested = enqueue_backward(capi, plan, inputs, io, skew, fill, need_mask, declared_short)
+    rep = a.finish(rc, requested)
     if outlier_status:
         rep.outliers = _outlier_status(capi, plan, a)
     return rep
@@ -212,14 +233,21 @@ def _outlier_status(capi, plan, arena):
     return units.value, bool(taken.value)
 
 
-def param_sums_finalize(capi, plan, inputs, io="f32", skew=0, fill=0xFF, declared_short=0):
-    """dau_conv_backward_param_sums into a poisoned `sums` buffer, then dau_conv_finalize_param_grads of the four kinds -> Report"""
-    a = Arena(capi, plan, inputs, io, capi.PASS_BACKWARD, skew, fill, with_sums=True)
+def enqueue_param_sums_finalize(capi, plan, inputs, io="f32", skew=0, fill=0xFF, declared_short=0, arena=None):
+    """The enqueue half of param_sums_finalize() -> (arena, rc, requested): rc is the second entry point's, or the first's if that
+    refused the call (then nothing is requested); see enqueue_forward"""
+    a = arena or Arena(capi, plan, inputs, io, capi.PASS_BACKWARD, skew, fill, with_sums=True)
     rc = capi.lib.dau_conv_backward_param_sums(plan._h, a.stream, a.ptr("x"), a.ptr("dy"), a.ptr("mu1"), a.ptr("mu2"), a.ptr("sigma"),
                                                a.ptr("sums"), a.ptr("workspace"), a.ws_bytes - declared_short)
     if rc != capi.DAU_OK:
-        return a.finish(rc, ())
+        return a, rc, ()
     mask = capi.NEED_DW | capi.NEED_DMU1 | capi.NEED_DMU2 | capi.NEED_DSIGMA
     rc = capi.lib.dau_conv_finalize_param_grads(plan._h, a.stream, a.ptr("sums"), a.ptr("w"), a.ptr("dw"), a.ptr("dmu1"), a.ptr("dmu2"),
                                                 a.ptr("dsigma"), mask)
-    return a.finish(rc, GRADS + ("sums",))
+    return a, rc, GRADS + ("sums",)
+
+
+def param_sums_finalize(capi, plan, inputs, io="f32", skew=0, fill=0xFF, declared_short=0):
+    """dau_conv_backward_param_sums into a poisoned `sums` buffer, then dau_conv_finalize_param_grads of the four kinds -> Report"""
+    a, rc, requested = enqueue_param_sums_finalize(capi, plan, inputs, io, skew, fill, declared_short)
+    return a.finish(rc, requested)

@@ -221,3 +221,40 @@ def test_harness_reports_a_write_to_an_output_that_was_not_requested(stand_in):
     assert f.untouched["dx"] is False or f.canaries       # (the band is at least, not exactly, 1 MiB)
     with pytest.raises(AssertionError):
         f.assert_clean()
+
+
+def _same_report(a, b):
+    assert (a.rc, a.status_rc, a.max_abs_mu) == (b.rc, b.status_rc, b.max_abs_mu)
+    assert a.canaries == b.canaries and a.inputs_changed == b.inputs_changed and a.untouched == b.untouched
+    assert sorted(a.outputs) == sorted(b.outputs) and sorted(a.values) == sorted(b.values)
+    for n in a.outputs:
+        assert a.outputs[n].dtype == b.outputs[n].dtype and a.outputs[n].shape == b.outputs[n].shape
+        assert np.array_equal(aa.as_bits(a.outputs[n]), aa.as_bits(b.outputs[n])), n
+        assert np.array_equal(aa.as_bits(a.values[n]), aa.as_bits(b.values[n])), n
+
+
+@pytest.mark.parametrize("io", ["f32", "f16"])
+def test_enqueue_then_finish_is_the_combined_call(stand_in, io):
+    """The two halves the concurrency tests use -- enqueue_*(), later Arena.finish() -- leave exactly the Report of forward() /
+    backward() / param_sums_finalize(): accepted and refused calls, a prebuilt arena, and a call whose damage the report names."""
+    capi, plan, inputs = stand_in(io)
+    pairs = ((aa.forward, aa.enqueue_forward, {}), (aa.backward, aa.enqueue_backward, dict(need_mask=capi.NEED_DX | capi.NEED_DW)),
+             (aa.backward, aa.enqueue_backward, {}), (aa.param_sums_finalize, aa.enqueue_param_sums_finalize, {}))
+    for short in (0, 1):
+        for whole, half, kw in pairs:
+            want = whole(capi, plan, inputs, io, 1, 0x7B, declared_short=short, **kw)
+            a, rc, requested = half(capi, plan, inputs, io, 1, 0x7B, declared_short=short, **kw)
+            assert isinstance(a, aa.Arena) and rc == want.rc and sorted(requested) == sorted(want.outputs)
+            _same_report(a.finish(rc, requested), want)
+    # several calls enqueued before the first is finished, one of them into an arena built ahead of the call
+    ahead = aa.Arena(capi, plan, inputs, io, capi.PASS_BACKWARD, 1, 0xFF)
+    pending = [aa.enqueue_forward(capi, plan, inputs, io, 1, 0xFF), aa.enqueue_backward(capi, plan, inputs, io, 1, 0xFF, arena=ahead),
+               aa.enqueue_param_sums_finalize(capi, plan, inputs, io, 1, 0xFF)]
+    assert pending[1][0] is ahead
+    for (a, rc, requested), whole in zip(pending, (aa.forward, aa.backward, aa.param_sums_finalize)):
+        _same_report(a.finish(rc, requested), whole(capi, plan, inputs, io, 1, 0xFF))
+    capi.lib.damage = ("y", 0, 3)
+    a, rc, requested = aa.enqueue_forward(capi, plan, inputs, io, 1, 0xFF)
+    rep = a.finish(rc, requested)
+    _same_report(rep, aa.forward(capi, plan, inputs, io, 1, 0xFF))
+    assert rep.canaries == [("before_dx", 3, 0)]
