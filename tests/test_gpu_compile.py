@@ -3,10 +3,13 @@ kernels the eager layer runs, on the same bits: outputs and every gradient are c
 through Dynamo and AOT autograd -- everything the ops' registration has to get right -- without generating code.
 The smallest layer of the layer tests: N=2, 4 -> 8 channels, 8x9 maps, dau_units=(2, 2), kernel 9."""
 import copy
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
+
+from layers import make_layer, same as _same
 
 pytestmark = pytest.mark.gpu
 
@@ -27,18 +30,7 @@ def _fresh_dynamo_and_the_plan_cache_as_it_was():
         impl._PLANS.pop(key).last_status()      # (a pending offset error would be raised here, not lost)
 
 
-def _layer(S=S, F=F, cls=None, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", True)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    kw.setdefault("bias_initializer", dau_conv.random_normal_initializer(stddev=0.5))
-    kw.setdefault("dau_units", (2, 2))
-    kw.setdefault("max_kernel_size", 9)
-    kw.setdefault("mu1_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    if cls is None:
-        kw.setdefault("mu2_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    return (cls or dau_conv.DAUConv2d)(filters=F, in_channels=S, **kw).cuda()
+_layer = functools.partial(make_layer, S=S, F=F)
 
 
 def _data(seed=3, S=S, F=F, H=H, W=W, out_hw=None, dtype=torch.float32, channels_last=False):
@@ -64,12 +56,6 @@ def _step(fn, layer, x, dy, residual=None, autocast=None, x_grad=True, residual_
     y.backward(dy.to(y.dtype))
     grads = {n: (None if p.grad is None else p.grad.clone()) for n, p in layer.named_parameters()}
     return y.detach(), x.grad, grads, None if residual is None else residual.grad
-
-
-def _same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    assert bool(torch.isfinite(a.float()).all()), what
-    assert torch.equal(a, b), "%s: %d of %d values differ" % (what, int((a != b).sum()), a.numel())
 
 
 def _compare(eager, compiled, layers, x, dy, residual=None, autocast=None, trained=("weights", "mu1", "mu2")):

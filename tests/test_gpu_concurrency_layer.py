@@ -10,6 +10,7 @@ Shapes as in test_gpu_graph_capture.py: N=4, 12 -> 24 channels, 28 x 28, 2 x 2 u
 capture, at most two streams and two threads beside the main one; each test is one pass, and a thread that has not come back after
 JOIN_SECONDS fails its test, which then makes no further GPU call."""
 import copy
+import functools
 import importlib
 import threading
 
@@ -17,6 +18,7 @@ import pytest
 import torch
 
 import dau_conv
+import layers as fixtures
 from dau_conv import _capi
 
 pytestmark = pytest.mark.gpu
@@ -39,26 +41,9 @@ def _fresh_plan_cache():
     clear()
 
 
-def make_layer(seed=0, in_channels=S, filters=F, mu=2.5, **kw):
-    torch.manual_seed(seed)
-    init = dau_conv.random_uniform_initializer(-mu, mu)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    return dau_conv.DAUConv2d(filters=filters, dau_units=(2, 2), max_kernel_size=9, in_channels=in_channels, mu1_initializer=init,
-                              mu2_initializer=init, **kw).cuda()
-
-
-def rand(seed, shape, normal=False):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    return (torch.randn if normal else torch.rand)(shape, device="cuda", generator=g)
-
-
-def rand_x(seed, shape=(N, S, H, W)):
-    return rand(seed, shape)
-
-
-def rand_dy(seed, shape=(N, F, H, W)):
-    return rand(seed, shape, normal=True)
+make_layer = functools.partial(fixtures.make_layer, S=S, F=F, mu=2.5, bias_initializer=None)       # (the layer's own zero bias)
+rand_x = functools.partial(fixtures.rand_x, shape=(N, S, H, W))
+rand_dy = functools.partial(fixtures.rand_dy, shape=(N, F, H, W))
 
 
 def fwd_bwd(layer, x, dy):
@@ -128,8 +113,8 @@ def test_two_layers_of_one_shape_on_two_streams():
 # ---- 8 -----------------------------------------------------------------------------------------------------------------------------------
 def test_one_streams_workspace_grows_while_the_other_works():
     layers, twins, streams, xs, dys = _pair()
-    big = make_layer(seed=3, in_channels=48, filters=48)
-    bx, bdy = rand_x(300, (N, 48, 56, 56)), rand_dy(301, (N, 48, 56, 56))
+    big = make_layer(seed=3, S=48, F=48)
+    bx, bdy = rand_x(300, shape=(N, 48, 56, 56)), rand_dy(301, shape=(N, 48, 56, 56))
     torch.cuda.synchronize()
     before = shared_workspaces()
     got = [[None] * STEPS, [None] * STEPS]

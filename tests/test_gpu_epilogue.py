@@ -3,8 +3,7 @@ the very value dau_conv_forward stores, before the store's one rounding -- so fo
 relu(forward(x) + bias), for the 16-bit formats identity with the rounded float32 fused result, and for NHWC identity with the NCHW
 call.  dau_conv_epilogue_backward: dz is aten::threshold_backward bit for bit; dbias is a hierarchical fp32 sum in which no value
 passes through more than 256 additions, hence |dbias[f] - exact| <= 256 * 2^-24 * sum |dz[:, f]| = 2^-16 * sum |dz[:, f]|.
-The rows are the shapes that corner these kernels in test_gpu_nhwc.py; each proves through Plan.info / outlier_status that its
-member runs."""
+The rows are member_rows.FUSED_ROWS; each proves through Plan.info / outlier_status that its member runs."""
 import ctypes
 
 import numpy as np
@@ -12,73 +11,15 @@ import pytest
 import torch
 
 import abi_arena as aa
-from util import assert_parity
+import member_rows as mr
+from member_rows import I, IO, OUTLIERS, act as _act, inputs as _inputs, io_of as _io_of, nhwc as _nhwc, params as _params, plan as _plan
+from util import assert_parity, bits as _bits
 
 pytestmark = pytest.mark.gpu
 
-I = 1 << 0                                   # USE_INTERPOLATION
-SPLIT, NO_SPLIT, OUTLIERS = 1 << 9, 1 << 10, 1 << 12
-IO = {"f32": (0, torch.float32), "f16": (1 << 11, torch.float16), "bf16": (1 << 4, torch.bfloat16)}
 BIAS, RELU = 1, 2
 EPILOGUES = (BIAS, BIAS | RELU, RELU)
-
-# name -> (flags, (N, S, F, G, H, W), k, m)
-ROWS = {
-    "split_17x13_m2": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 2.0),            # F = 5: the guarded bias load, element stores
-    "split_17x13_m3": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.0),
-    "split_17x13_m4": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.99),
-    "split_tall_28x28": (SPLIT, (2, 16, 40, 4, 28, 28), 9, 3.0),        # tall tiles, 16-byte NHWC stores
-    "outliers_28x28": (SPLIT | OUTLIERS, (2, 16, 40, 4, 28, 28), 9, 3.0),   # the ADD epilogue: the bias joins after the ring's sum
-    "exact_stacked_28x28": (NO_SPLIT, (4, 8, 16, 6, 28, 28), 9, 3.0),
-    "exact_bucket8": (NO_SPLIT, (2, 5, 8, 2, 40, 72), 17, 7.0),
-    "k65_gather_windows": (0, (2, 2, 20, 9, 37, 100), 65, 20.0),        # four windows: the epilogue belongs to the last
-    "default_128": (0, (2, 128, 128, 4, 16, 16), 9, 3.0),               # the chunk-pair loop
-}
-
-
-def _inputs(name):
-    flags, (N, S, F, G, H, W), k, m = ROWS[name]
-    rs = np.random.RandomState(1 + sum(ord(c) for c in name))
-    x = rs.rand(N, S, H, W).astype(np.float32)
-    dy = rs.randn(N, F, H, W).astype(np.float32)
-    w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
-    lim = k // 2 - 0.01
-    mu1 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    mu2 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    if flags & OUTLIERS:
-        mu1.flat[5] = 3.5
-    return x, dy, w, mu1, mu2
-
-
-def _plan(name, io, nhwc=False, extra=0):
-    from dau_conv import _capi
-    flags, (N, S, F, G, H, W), k, m = ROWS[name]
-    plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5,
-                      flags=I | flags | IO[io][0] | extra | (_capi.FLAG_IO_NHWC if nhwc else 0))
-    if name == "default_128":
-        assert plan.info["gather_dense_split"] == 0b11100
-    if name.startswith("split"):
-        assert plan.info["gather_dense_split"] & 0b11100 == 0b11100
-    if name.startswith("exact"):
-        assert plan.info["gather_dense_split"] == 0
-    if name == "k65_gather_windows":
-        assert plan.info["gather_windows"] == 4
-    if flags & OUTLIERS:
-        assert plan.info["gather_dense_split"] & (1 << 5)
-    return plan
-
-
-def _params(name):
-    x, dy, w, mu1, mu2 = _inputs(name)
-    dev = lambda a: torch.from_numpy(a).cuda()
-    S, G, F = w.shape[1:]
-    return dev(w), dev(mu1), dev(mu2), torch.full((1, S, G, F), 0.5, device="cuda")
-
-
-def _act(a, dtype, plan):
-    fmt = torch.channels_last if plan.io_layout == "NHWC" else torch.contiguous_format
-    return a.to(dtype).contiguous(memory_format=fmt)
-
+ROWS = mr.FUSED_ROWS
 
 _SHARED = {}        # name -> (x fp32 on the device, unfused fp32 y, bias): computed once, never written
 
@@ -101,18 +42,12 @@ def _fused(plan, name, x, epilogue):
     of its static bucket, as the call that made the shared unfused y did -- a later call of a kernel-65 plan would run the set of the
     bucket its offsets need, one window pass instead of four, whose sums come in another order"""
     _, _, bias = _shared(name)
-    io = {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[plan.io_dtype]
-    plan = _plan(name, io, plan.io_layout == "NHWC")
+    plan = _plan(name, _io_of(plan), plan.io_layout == "NHWC")
     y = plan.forward(x, *_params(name), bias=bias if epilogue & BIAS else None, relu=bool(epilogue & RELU))
     plan.check_status()
-    if ROWS[name][0] & OUTLIERS:
+    if mr.ROWS[name][0] & OUTLIERS:
         assert plan.outlier_status() == (1, True), "the radius-3 + ring member did not run"
     return y
-
-
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _unfused(y, bias, epilogue):
@@ -264,10 +199,6 @@ def test_epilogue_backward_with_values_that_are_not_finite(io):
 
 
 # ---- memory: outputs and workspace as slices of poisoned allocations, aligned and one element off -----------------------------------
-def _nhwc(a):
-    return np.ascontiguousarray(a.transpose(0, 2, 3, 1))
-
-
 @pytest.mark.parametrize("skew", [0, 1])
 @pytest.mark.parametrize("nhwc", [False, True], ids=["nchw", "nhwc"])
 @pytest.mark.parametrize("io", ["f32", "f16"])

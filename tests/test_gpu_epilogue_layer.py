@@ -3,27 +3,19 @@ op's store: the output keeps the input's dtype (so the next layer of an autocast
 float32 the output and every gradient that depends on dz are bit for bit the unfused layer's, and the bias gradient -- a
 hierarchical fp32 sum -- lies within 2^-16 * sum |dz| of the exact sum."""
 import copy
+import functools
 import warnings
 
 import pytest
 import torch
 import torch.nn as nn
 
+from layers import check_bias_grad as _check_bias_grad, close as _close, make_layer
+
 pytestmark = pytest.mark.gpu
 
 
-def _layer(S=8, F=16, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", True)
-    kw.setdefault("activation", torch.relu)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    kw.setdefault("bias_initializer", dau_conv.random_normal_initializer(stddev=0.5))
-    kw.setdefault("dau_units", (2, 2))
-    kw.setdefault("max_kernel_size", 9)
-    kw.setdefault("mu1_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    kw.setdefault("mu2_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    return dau_conv.DAUConv2d(filters=F, in_channels=S, **kw).cuda()
+_layer = functools.partial(make_layer, activation=torch.relu)
 
 
 def _pair(**kw):
@@ -40,19 +32,6 @@ def _step(layer, x, dy):
     y = layer(x)
     y.backward(dy)
     return y.detach(), x.grad, {n: p.grad.clone() for n, p in layer.named_parameters() if p.grad is not None}
-
-
-def _close(got, want, rel=2e-3):
-    got, want = got.float(), want.float()
-    assert torch.isfinite(got).all()
-    err = ((got - want).abs() - rel * want.abs() - rel * want.abs().max()).max().item()
-    assert err <= 0, "differs by %.3e (max |want| %.3e)" % ((got - want).abs().max().item(), want.abs().max().item())
-
-
-def _check_bias_grad(got, y, dy):
-    dz = torch.where(y <= 0, torch.zeros_like(dy), dy).double()
-    exact, bound = dz.sum(dim=(0, 2, 3)), 2.0 ** -16 * dz.abs().sum(dim=(0, 2, 3))
-    assert bool(((got.double() - exact).abs() <= bound).all()), ((got.double() - exact).abs().tolist(), bound.tolist())
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

@@ -2,29 +2,18 @@
 GradScaler training and model.half().  The layer runs in the dtype of its input and casts nothing; parameters of any floating
 dtype are used as float32 and receive their gradients in their own dtype."""
 import copy
+import functools
 
 import pytest
 import torch
 import torch.nn as nn
 
+from layers import close as _close, make_layer
+
 pytestmark = pytest.mark.gpu
 
 
-def _layer(S=8, F=16, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", False)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    return dau_conv.DAUConv2d(filters=F, dau_units=(2, 2), max_kernel_size=9, in_channels=S,
-                              mu1_initializer=dau_conv.random_uniform_initializer(-3, 3),
-                              mu2_initializer=dau_conv.random_uniform_initializer(-3, 3), **kw).cuda()
-
-
-def _close(got, want, rel=2e-3):
-    got, want = got.float(), want.float()
-    assert torch.isfinite(got).all()
-    err = ((got - want).abs() - rel * want.abs() - rel * want.abs().max()).max().item()
-    assert err <= 0, "differs by %.3e (max |want| %.3e)" % ((got - want).abs().max().item(), want.abs().max().item())
+_layer = functools.partial(make_layer, use_bias=False, bias_initializer=None)     # (where a test asks for the bias: zeros)
 
 
 def test_layer_dtypes_and_values():

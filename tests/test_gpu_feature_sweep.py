@@ -26,16 +26,11 @@ import pytest
 import torch
 
 import feature_sweep as fs
-from util import assert_parity, record_margins
+from util import assert_parity, bits as _bits, record_margins
 
 pytestmark = pytest.mark.gpu
 
 DTYPE = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-
-
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _widened(t):

@@ -8,6 +8,7 @@ tested against the oracle elsewhere; the first test ties a replay to the oracle 
 Shapes: N=4, 12 -> 24 channels, 28 x 28, 2 x 2 units, kernel 9 unless said otherwise.  Captures are single-stream (linear graphs), every
 one is preceded by a synchronize, and no graph is replayed after an assertion about it has failed."""
 import copy
+import functools
 import importlib
 import warnings
 
@@ -16,6 +17,7 @@ import pytest
 import torch
 
 import dau_conv
+import layers as fixtures
 from dau_conv import _capi
 from oracle import dau_oracle as orc
 from util import assert_parity
@@ -38,26 +40,9 @@ def _fresh_plan_cache():
     clear()
 
 
-def make_layer(cls=None, seed=0, kernel=9, mu=2.5, in_channels=S, filters=F, **kw):
-    torch.manual_seed(seed)
-    init = dau_conv.random_uniform_initializer(-mu, mu)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    if cls is not dau_conv.DAUConv1d:
-        kw["mu2_initializer"] = init
-    return (cls or dau_conv.DAUConv2d)(filters=filters, dau_units=(2, 2), max_kernel_size=kernel, in_channels=in_channels,
-                                       mu1_initializer=init, **kw).cuda()
-
-
-def rand_x(seed, dtype=torch.float32, shape=(N, S, H, W), memory_format=torch.contiguous_format):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    return torch.rand(shape, device="cuda", generator=g).to(dtype).contiguous(memory_format=memory_format)
-
-
-def rand_dy(seed, dtype=torch.float32, shape=(N, F, H, W), memory_format=torch.contiguous_format):
-    g = torch.Generator(device="cuda")
-    g.manual_seed(seed)
-    return torch.randn(shape, device="cuda", generator=g).to(dtype).contiguous(memory_format=memory_format)
+make_layer = functools.partial(fixtures.make_layer, S=S, F=F, mu=2.5, bias_initializer=None)       # (the layer's own zero bias)
+rand_x = functools.partial(fixtures.rand_x, shape=(N, S, H, W))
+rand_dy = functools.partial(fixtures.rand_dy, shape=(N, F, H, W))
 
 
 def fwd_bwd(layer, x, dy, autocast=None, **fw):
@@ -201,7 +186,7 @@ def test_a_capture_leaves_the_shared_workspace_alone():
         assert last is None or (last.data_ptr(), last.numel()) in before.values(), "the plan keeps a workspace of the capture"
     replay_equals_eager(graph, outs, layer, twin, x, dy, "first replay")
     # a larger layer grows (replaces) the shared workspace; the graph holds none of it
-    big = make_layer(seed=1, in_channels=48, filters=48)
+    big = make_layer(seed=1, S=48, F=48)
     fwd_bwd(big, rand_x(3, shape=(N, 48, 56, 56)).requires_grad_(True), rand_dy(4, shape=(N, 48, 56, 56)))
     torch.cuda.synchronize()
     grown = shared()
@@ -232,22 +217,22 @@ def test_formats_replay_as_eager(case):
     elif case == "conv1d_line":
         cls, kw = dau_conv.DAUConv1d, dict(dense_line=True, dense_line_grads=True)
     kw.setdefault("use_bias", False)                         # (an unfused float32 bias would promote a 16-bit output)
-    layer = make_layer(cls, **kw)
+    layer = make_layer(cls=cls, **kw)
     if case == "bf16":
         layer = layer.bfloat16()
     twin = copy.deepcopy(layer)
-    x = rand_x(1, dtype, memory_format=mf)
+    x = rand_x(1, dtype=dtype, memory_format=mf)
     if case == "input_relu":
         x = x - 0.5
     x.requires_grad_(True)
-    dy = rand_dy(2, dtype, memory_format=mf)
+    dy = rand_dy(2, dtype=dtype, memory_format=mf)
     fwd_bwd(layer, x, dy, autocast, **fw)                    # warm-up
     graph, outs = capture_fwd_bwd(layer, x, dy, None, autocast, **fw)
     if fw:
         outs = outs + [fw["residual"].grad]
     for i in range(2):
         if i:
-            x.data.copy_(rand_x(30, dtype, memory_format=mf) - (0.5 if case == "input_relu" else 0.0))
+            x.data.copy_(rand_x(30, dtype=dtype, memory_format=mf) - (0.5 if case == "input_relu" else 0.0))
         graph.replay()
         torch.cuda.synchronize()
         got = [t.clone() for t in outs]
@@ -267,7 +252,7 @@ def test_formats_replay_as_eager(case):
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kernel,start,end", [(9, 2.5, 3.9), (17, 3.0, 7.0)])
 def test_offsets_move_across_members_and_buckets_in_a_replay(kernel, start, end):
-    layer = make_layer(kernel=kernel, mu=start)
+    layer = make_layer(max_kernel_size=kernel, mu=start)
     with torch.no_grad():                                    # max|mu| is exactly `start`
         for mu in (layer.mu1, layer.mu2):
             mu.mul_(start / float(mu.abs().max()))
@@ -423,7 +408,7 @@ def test_torch_compile_cudagraphs_backend_trains_as_eager():
     import torch._dynamo
     torch._dynamo.reset()
     stack = torch.nn.Sequential(make_layer(dau_sigma_trainable=True), torch.nn.ReLU(),
-                                make_layer(seed=1, in_channels=F, dau_sigma_trainable=True))
+                                make_layer(seed=1, S=F, dau_sigma_trainable=True))
     twin = copy.deepcopy(stack)
     opt, topt = torch.optim.SGD(stack.parameters(), lr=1e-3), torch.optim.SGD(twin.parameters(), lr=1e-3)
     target = rand_dy(77)

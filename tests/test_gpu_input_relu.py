@@ -2,92 +2,34 @@
 fed the raw x returns the bits the SAME plan without the flag returns on x' = where(x <= 0, 0, x) -- y and the four parameter
 gradients -- and its dx is where(x <= 0, 0, dx of that reference), for float32, float16 and bfloat16, NCHW and NHWC.  x is randn
 (sign-symmetric); every test asserts that between 0.2 and 0.8 of it is <= 0, so a clamp that does nothing cannot pass.  The rows are
-those of test_gpu_residual.py (a copy: that file stays as it is), the smallest shapes that reach every member; each proves through
-Plan.info / outlier_status that its member runs, and every call runs on a fresh plan, forward first and backward second, so that the
-flagged calls take the bucket sets the reference calls took (test_gpu_residual.py explains why)."""
+member_rows.FUSED_ROWS, the smallest shapes that reach every member; each proves through Plan.info / outlier_status that its member
+runs, and every call runs on a fresh plan, forward first and backward second, so that the flagged calls take the bucket sets the
+reference calls took (test_gpu_residual.py explains why)."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 import torch
 
-from util import assert_parity
+import member_rows as mr
+from member_rows import IO, OUTLIERS, SLAB_ROWS, lay as _lay, nhwc_view as _nhwc_view
+from util import assert_parity, assert_same_bits, bits as _bits
 
 pytestmark = pytest.mark.gpu
 
-I = 1 << 0                                   # USE_INTERPOLATION
-SPLIT, NO_SPLIT, OUTLIERS = 1 << 9, 1 << 10, 1 << 12
 INPUT_RELU = 1 << 14
-IO = {"f32": (0, torch.float32), "f16": (1 << 11, torch.float16), "bf16": (1 << 4, torch.bfloat16)}
 GRADS = ("dw", "dmu1", "dmu2", "dsigma")
-
-# name -> (flags, (N, S, F, G, H, W), k, m)
-ROWS = {
-    "split_17x13_m2": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 2.0),            # S = 7, F = 5: channel clamps, element access
-    "split_17x13_m3": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.0),
-    "split_17x13_m4": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.99),
-    "split_tall_28x28": (SPLIT, (2, 16, 40, 4, 28, 28), 9, 3.0),        # tall tiles, 16-byte NHWC loads and stores
-    "outliers_28x28": (SPLIT | OUTLIERS, (2, 16, 40, 4, 28, 28), 9, 3.0),   # the ring and the ADD form
-    "exact_stacked_28x28": (NO_SPLIT, (4, 8, 16, 6, 28, 28), 9, 3.0),   # the exact gather, stacked planes
-    "exact_bucket8": (NO_SPLIT, (2, 5, 8, 2, 40, 72), 17, 7.0),
-    "k65_gather_windows": (0, (2, 2, 20, 9, 37, 100), 65, 20.0),        # four windows: the mask belongs to the last
-    "default_128": (0, (2, 128, 128, 4, 16, 16), 9, 3.0),               # the chunk-pair loop and the two-limb gather-dot
-}
-# a slab is an even number of images that divides the batch: the slab test runs the rows of four images
-SLAB_ROWS = {"exact_stacked_28x28": "exact_stacked_28x28", "split_tall_28x28": "split_tall_28x28_n4"}
-ALL_ROWS = dict(ROWS, split_tall_28x28_n4=(SPLIT, (4, 16, 40, 4, 28, 28), 9, 3.0))
-
-
-def _inputs(name):
-    flags, (N, S, F, G, H, W), k, m = ALL_ROWS[name]
-    rs = np.random.RandomState(1 + sum(ord(c) for c in name))
-    x = rs.randn(N, S, H, W).astype(np.float32)                         # sign-symmetric: the ReLU cuts about half
-    dy = rs.randn(N, F, H, W).astype(np.float32)
-    w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
-    lim = k // 2 - 0.01
-    mu1 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    mu2 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    if flags & OUTLIERS:
-        mu1.flat[5] = 3.5
-    return x, dy, w, mu1, mu2
+ROWS = mr.FUSED_ROWS                         # the parametrised tests run these, the slab test the rows of four images
+_inputs = functools.partial(mr.inputs, x="randn")      # sign-symmetric: the ReLU cuts about half
+_params = functools.partial(mr.params, x="randn")
+_assert_same_bits = functools.partial(assert_same_bits, keys=("y", "dx") + GRADS)
 
 
 def _plan(name, io, nhwc=False, fused=False):
-    from dau_conv import _capi
-    flags, (N, S, F, G, H, W), k, m = ALL_ROWS[name]
-    plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5,
-                      flags=I | flags | IO[io][0] | (INPUT_RELU if fused else 0) | (_capi.FLAG_IO_NHWC if nhwc else 0))
+    plan = mr.plan(name, io, nhwc, INPUT_RELU if fused else 0)
     assert plan.input_relu == fused
-    if name == "default_128":
-        assert plan.info["gather_dense_split"] == 0b11100 and plan.info["algo_backward"] == _capi.ALGO_TILED
-    if name.startswith("split"):
-        assert plan.info["gather_dense_split"] & 0b11100 == 0b11100
-    if name.startswith("exact"):
-        assert plan.info["gather_dense_split"] == 0
-    if name == "exact_bucket8":
-        assert plan.info["offset_bucket"] == 8
-    if name == "k65_gather_windows":
-        assert plan.info["gather_windows"] == 4
-    if flags & OUTLIERS:
-        assert plan.info["gather_dense_split"] & (1 << 5)
     return plan
-
-
-def _params(name):
-    _, _, w, mu1, mu2 = _inputs(name)
-    dev = lambda a: torch.from_numpy(a).cuda()
-    S, G, F = w.shape[1:]
-    return dev(w), dev(mu1), dev(mu2), torch.full((1, S, G, F), 0.5, device="cuda")
-
-
-def _lay(a, plan):
-    fmt = torch.channels_last if plan.io_layout == "NHWC" else torch.contiguous_format
-    return a.contiguous(memory_format=fmt)
-
-
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _clamp(x):
@@ -104,11 +46,11 @@ def _run(plan, name, x, dy, **fwd):
     p = _params(name)
     y = plan.forward(_lay(x, plan), *p, **fwd)
     plan.check_status()
-    if ALL_ROWS[name][0] & OUTLIERS:
+    if mr.ROWS[name][0] & OUTLIERS:
         assert plan.outlier_status() == (1, True), "the radius-3 + ring member did not run (forward)"
     dx, dw, dmu1, dmu2, dsigma = plan.backward(_lay(x, plan), _lay(dy, plan), *p)
     plan.check_status()
-    if ALL_ROWS[name][0] & OUTLIERS:
+    if mr.ROWS[name][0] & OUTLIERS:
         assert plan.outlier_status() == (1, True), "the radius-3 + ring member did not run (dx)"
     return dict(y=y, dx=dx, dw=dw, dmu1=dmu1, dmu2=dmu2, dsigma=dsigma)
 
@@ -137,13 +79,6 @@ def _reference(name, io, x=None):
     if x is None:
         _REF[key] = out
     return out
-
-
-def _assert_same_bits(got, want, what, keys=("y", "dx") + GRADS):
-    for k in keys:
-        g, w = _bits(got[k]), _bits(want[k])
-        assert g.shape == w.shape, (what, k)
-        assert torch.equal(g, w), "%s: %d of %d values of %s differ" % (what, int((g != w).sum()), w.numel(), k)
 
 
 # ---- 1. float32, 16-bit, layouts, slabs ---------------------------------------------------------------------------------------------
@@ -243,12 +178,6 @@ def test_special_values_and_an_all_negative_image(name, nhwc):
     other = _run(_plan(name, "f32", nhwc, fused=True), name, x2, dy)
     for k in ("y", "dx"):
         assert torch.equal(_bits(got[k])[:dead], _bits(other[k])[:dead]), "%s: %s of the other images moved" % (name, k)
-
-
-def _nhwc_view(buf, shape, offset):
-    """a channels_last tensor of logical `shape` whose memory is buf[offset : offset + numel]"""
-    N, C, H, W = shape
-    return buf[offset:offset + N * C * H * W].view(N, H, W, C).permute(0, 3, 1, 2)
 
 
 def _raw_backward(plan, name, x, dy, dx):

@@ -10,33 +10,9 @@ import pytest
 import torch
 import torch.nn as nn
 
+from layers import _leave_the_plan_cache_as_it_was, make_layer as _layer, same as _same  # noqa: F401 (the autouse fixture)
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(autouse=True)
-def _leave_the_plan_cache_as_it_was():
-    """the layer's plan cache is bounded and least-recently-used: the plans these tests add would push other modules' plans out of
-    it (tests elsewhere compare its keys before and after a call), so each test takes its own out again"""
-    import importlib
-    impl = importlib.import_module("dau_conv.dau_conv")
-    before = set(impl._PLANS)
-    yield
-    for key in [k for k in impl._PLANS if k not in before]:
-        impl._PLANS.pop(key).last_status()      # (a pending offset error would be raised here, not lost)
-
-
-def _layer(S=8, F=16, cls=None, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", True)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    kw.setdefault("bias_initializer", dau_conv.random_normal_initializer(stddev=0.5))
-    kw.setdefault("dau_units", (2, 2))
-    kw.setdefault("max_kernel_size", 9)
-    kw.setdefault("mu1_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    if cls is None:
-        kw.setdefault("mu2_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    return (cls or dau_conv.DAUConv2d)(filters=F, in_channels=S, **kw).cuda()
 
 
 def _pair(**kw):
@@ -54,12 +30,6 @@ def _step(fn, params, x, dy):
     y = fn(x)
     y.backward(dy.to(y.dtype) if dy.shape == y.shape else dy)
     return y.detach(), x.grad, [None if p.grad is None else p.grad.clone() for p in params]
-
-
-def _same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, what
-    assert bool(torch.isfinite(a.float()).all()), what
-    assert torch.equal(a, b), "%s: %d of %d values differ" % (what, int((a != b).sum()), a.numel())
 
 
 def _share(x):

@@ -9,61 +9,18 @@ import torch
 
 import abi_arena as aa
 from oracle import dau_oracle as orc
-from util import assert_parity
+import member_rows as mr
+from member_rows import IO, OUTLIERS, inputs as _inputs, nhwc as _nhwc
+from util import assert_parity, bits as _bits
 
 pytestmark = pytest.mark.gpu
 
-I, UT, SD = 1 << 0, 1 << 1, 1 << 2          # USE_INTERPOLATION, UNIT_TESTING, SINGLE_DIM_KERNEL
-SPLIT, NO_SPLIT, OUTLIERS = 1 << 9, 1 << 10, 1 << 12
-IO = {"f32": (0, torch.float32), "f16": (1 << 11, torch.float16), "bf16": (1 << 4, torch.bfloat16)}
 NAMES = ("y", "dx", "dw", "dmu1", "dmu2", "dsigma")
-
-# name -> (flags, (N, S, F, G, H, W), k, m, what it exercises)
-ROWS = {
-    # the three radii; S not a multiple of 8 (nor of 4: element loads); F pads; two bands plus a short last row block; W % 4 != 0
-    "split_17x13_m2": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 2.0),
-    "split_17x13_m3": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.0),
-    "split_17x13_m4": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.99),
-    # two 64-column segments, halo across the seam
-    "split_9x70_m2": (SPLIT, (2, 7, 5, 2, 9, 70), 9, 2.0),
-    "split_9x70_m3": (SPLIT, (2, 7, 5, 2, 9, 70), 9, 3.0),
-    "split_9x70_m4": (SPLIT, (2, 7, 5, 2, 9, 70), 9, 3.99),
-    # tall tiles, two 32-channel wave groups, 16-byte loads and stores
-    "split_tall_28x28": (SPLIT, (2, 16, 40, 4, 28, 28), 9, 3.0),
-    # the ADD epilogue: planar partial sums of the ring pass, NHWC store (one unit at 3.5)
-    "outliers_28x28": (SPLIT | OUTLIERS, (2, 16, 40, 4, 28, 28), 9, 3.0),
-    "exact_stacked_28x28": (NO_SPLIT, (4, 8, 16, 6, 28, 28), 9, 3.0),     # stacked planes, exact gather-dot
-    "exact_bucket8": (NO_SPLIT, (2, 5, 8, 2, 40, 72), 17, 7.0),
-    "k65_33x20": (0, (2, 3, 8, 3, 33, 20), 65, 20.0),                    # gather-dot offset windows
-    "k65_gather_windows": (0, (2, 2, 20, 9, 37, 100), 65, 20.0),         # four gather-sum window passes: the accumulate re-read
-    "unit_testing_24x24": (UT, (2, 8, 16, 4, 24, 24), 9, 3.0),
-    "unit_testing_32x32": (UT, (2, 8, 16, 4, 32, 32), 9, 3.0),           # last row and column of the error dropped
-    "single_dim": (SD, (2, 8, 16, 2, 16, 16), 9, 3.0),
-    "default_128": (0, (2, 128, 128, 4, 16, 16), 9, 3.0),                # default plan: split gather radii and the split gather-dot
-}
-
-
-def _inputs(name):
-    flags, (N, S, F, G, H, W), k, m = ROWS[name]
-    rs = np.random.RandomState(1 + sum(ord(c) for c in name))
-    x = rs.rand(N, S, H, W).astype(np.float32)
-    dy = rs.randn(N, F, H, W).astype(np.float32)
-    w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
-    lim = k // 2 - 0.01
-    mu1 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    mu2 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    if flags & OUTLIERS:
-        mu1.flat[5] = 3.5
-    if flags & SD:
-        mu2[:] = 0.0
-    return x, dy, w, mu1, mu2
+ROWS = mr.NHWC_ROWS
 
 
 def _plans(name, io):
-    from dau_conv import _capi
-    flags, (N, S, F, G, H, W), k, m = ROWS[name]
-    mk = lambda extra: _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5, flags=I | flags | IO[io][0] | extra)
-    nchw, nhwc = mk(0), mk(_capi.FLAG_IO_NHWC)
+    nchw, nhwc = mr.plan(name, io), mr.plan(name, io, nhwc=True)
     assert nhwc.info == nchw.info and nhwc.io_layout == "NHWC"
     return nchw, nhwc
 
@@ -85,24 +42,11 @@ def _run(plan, x, dy, w, mu1, mu2, dtype, outliers=False):
     return (y,) + tuple(grads)
 
 
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
-
-
 @pytest.mark.parametrize("io", ["f32", "f16", "bf16"])
 @pytest.mark.parametrize("name", list(ROWS))
 def test_nhwc_call_returns_the_bits_of_the_nchw_call(name, io):
-    flags = ROWS[name][0]
-    nchw, nhwc = _plans(name, io)
-    if name == "default_128":
-        assert nhwc.info["gather_dense_split"] == 0b11100
-    if name == "k65_gather_windows":
-        assert nhwc.info["gather_windows"] == 4
-    if name == "unit_testing_32x32":
-        assert nhwc.info["drop_last_col"] == 1 and nhwc.info["drop_last_row"] == 1
-    if flags & OUTLIERS:
-        assert nhwc.info["gather_dense_split"] & (1 << 5)
+    flags = mr.ROWS[name][0]
+    nchw, nhwc = _plans(name, io)               # (mr.plan has asserted through Plan.info that each holds the row's member)
     data = _inputs(name)
     want = _run(nchw, *data, dtype=IO[io][1], outliers=bool(flags & OUTLIERS))
     got = _run(nhwc, *data, dtype=IO[io][1], outliers=bool(flags & OUTLIERS))
@@ -130,12 +74,8 @@ def test_nhwc_default_plan_against_the_oracle():
 @pytest.mark.parametrize("name", ["split_17x13_m3", "exact_stacked_28x28", "default_128"])
 def test_param_sums_route_gives_the_bits_of_backward(name, io):
     _, nhwc = _plans(name, io)
-    x, dy, w, mu1, mu2 = _inputs(name)
-    dev = lambda a: torch.from_numpy(a).cuda()
-    xd, dyd = (dev(a).to(IO[io][1]).contiguous(memory_format=torch.channels_last) for a in (x, dy))
-    S, G, F = w.shape[1:]
-    sigma = torch.full((1, S, G, F), 0.5, device="cuda")
-    wd, m1, m2 = dev(w), dev(mu1), dev(mu2)
+    xd, dyd = (mr.act(torch.from_numpy(a).cuda(), IO[io][1], nhwc) for a in _inputs(name)[:2])
+    wd, m1, m2, sigma = mr.params(name)
     want = nhwc.backward(xd, dyd, wd, m1, m2, sigma)[1:]
     sums = nhwc.backward_param_sums(xd, dyd, m1, m2, sigma)
     got = nhwc.finalize_param_grads(sums, wd)
@@ -145,10 +85,6 @@ def test_param_sums_route_gives_the_bits_of_backward(name, io):
 
 
 # ---- the memory contract on NHWC arrays: canaries, poisoned outputs and workspace, bases one element off alignment ---------------
-def _nhwc(a):
-    return np.ascontiguousarray(a.transpose(0, 2, 3, 1))
-
-
 _ARENA_FIRST = {}        # (shape name, io, entry point) -> {output: bits} of the first variant that ran
 
 

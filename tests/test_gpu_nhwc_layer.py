@@ -3,6 +3,7 @@
 output, a channels_last input gradient -- and the bits of the same layer on the contiguous tensors.  Where the library has no NHWC
 plan (dense_bf16 layers, shapes of the direct kernels) and with channels_last=False the layer converts and returns contiguous
 tensors, as it always did."""
+import functools
 import sys
 import warnings
 
@@ -10,30 +11,19 @@ import pytest
 import torch
 import torch.nn as nn
 
+from layers import make_layer
+from util import bits as _bits
+
 pytestmark = pytest.mark.gpu
 
 CL = torch.channels_last
 
 
-def _layer(S=6, F=8, cls=None, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", False)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    kw.setdefault("dau_units", (2, 2))
-    kw.setdefault("max_kernel_size", 9)
-    kw.setdefault("mu1_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    if (cls or dau_conv.DAUConv2d) is dau_conv.DAUConv2d:
-        kw.setdefault("mu2_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    return (cls or dau_conv.DAUConv2d)(filters=F, in_channels=S, **kw).cuda()
+_layer = functools.partial(make_layer, S=6, F=8, use_bias=False)
 
 
 def _is_cl(t):
     return t.is_contiguous(memory_format=CL) and not t.is_contiguous()
-
-
-def _bits(t):
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _step(layer, x, dy):

@@ -45,7 +45,7 @@ import pytest
 import torch
 
 from oracle import dau_oracle as orc
-from util import assert_parity, make_inputs, record_margins
+from util import assert_parity, bits as _bits, make_inputs, record_margins
 
 pytestmark = pytest.mark.gpu
 
@@ -143,11 +143,6 @@ def _run(plan, data, sigma, outliers=False):
 def _np(out):
     """-> {name: float32 numpy array in logical [N, C, H, W] order}"""
     return {n: t.float().contiguous().cpu().numpy() for n, t in zip(NAMES, out)}
-
-
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _same_bits(got, ref, what):

@@ -1,87 +1,25 @@
 """GPU: the residual add of the fused epilogue at the plan level.  dau_conv_forward_residual stores
 y = act((sum + bias[f]) + r[n,f,h,w]) -- two fp32 adds in that order and a clamp on the very value dau_conv_forward stores, before the
 store's one rounding -- so for float32 the bar is identity with relu((forward(x) + bias) + r), for the 16-bit formats identity with
-the rounded float32 fused result on the widened x and r, and for NHWC identity with the NCHW call.  The rows are those of
-test_gpu_epilogue.py (a copy: that file stays as it is); each proves through Plan.info / outlier_status that its member runs, and each
-fused call runs on a fresh plan so that it takes the bucket set the unfused call took."""
+the rounded float32 fused result on the widened x and r, and for NHWC identity with the NCHW call.  The rows are
+member_rows.FUSED_ROWS; each proves through Plan.info / outlier_status that its member runs, and each fused call runs on a fresh plan
+so that it takes the bucket set the unfused call took."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
-from util import assert_parity
+import member_rows as mr
+from member_rows import I, IO, OUTLIERS, SLAB_ROWS, act as _act, inputs as _inputs, io_of as _io_of, nhwc_view as _nhwc_view, params as _params, \
+    plan as _plan
+from util import assert_parity, bits as _bits
 
 pytestmark = pytest.mark.gpu
 
-I = 1 << 0                                   # USE_INTERPOLATION
-SPLIT, NO_SPLIT, OUTLIERS = 1 << 9, 1 << 10, 1 << 12
-IO = {"f32": (0, torch.float32), "f16": (1 << 11, torch.float16), "bf16": (1 << 4, torch.bfloat16)}
 BIAS, RELU = 1, 2
 EPILOGUES = (0, BIAS, BIAS | RELU, RELU)     # each WITH a residual: 0 is the plain fused add
-
-# name -> (flags, (N, S, F, G, H, W), k, m)
-ROWS = {
-    "split_17x13_m2": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 2.0),            # F = 5: guarded loads of bias and residual, element access
-    "split_17x13_m3": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.0),
-    "split_17x13_m4": (SPLIT, (2, 7, 5, 2, 17, 13), 9, 3.99),
-    "split_tall_28x28": (SPLIT, (2, 16, 40, 4, 28, 28), 9, 3.0),        # tall tiles, 16-byte NHWC loads and stores
-    "outliers_28x28": (SPLIT | OUTLIERS, (2, 16, 40, 4, 28, 28), 9, 3.0),   # the ADD epilogue: bias and residual join after the ring's sum
-    "exact_stacked_28x28": (NO_SPLIT, (4, 8, 16, 6, 28, 28), 9, 3.0),
-    "exact_bucket8": (NO_SPLIT, (2, 5, 8, 2, 40, 72), 17, 7.0),
-    "k65_gather_windows": (0, (2, 2, 20, 9, 37, 100), 65, 20.0),        # four windows: the epilogue belongs to the last
-    "default_128": (0, (2, 128, 128, 4, 16, 16), 9, 3.0),               # the chunk-pair loop
-}
-# a slab is an even number of images that divides the batch (image pairs stay together): a batch of two cannot run in slabs, so the
-# slab test runs the tall-tile row with four images
-SLAB_ROWS = {"exact_stacked_28x28": "exact_stacked_28x28", "split_tall_28x28": "split_tall_28x28_n4"}
-# every row the helpers know: the parametrised tests run ROWS, the slab test its four-image row as well
-ALL_ROWS = dict(ROWS, split_tall_28x28_n4=(SPLIT, (4, 16, 40, 4, 28, 28), 9, 3.0))
-
-
-def _inputs(name):
-    flags, (N, S, F, G, H, W), k, m = ALL_ROWS[name]
-    rs = np.random.RandomState(1 + sum(ord(c) for c in name))
-    x = rs.rand(N, S, H, W).astype(np.float32)
-    dy = rs.randn(N, F, H, W).astype(np.float32)
-    w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
-    lim = k // 2 - 0.01
-    mu1 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    mu2 = np.clip(rs.uniform(-m, m, (1, S, G, F)), -lim, lim).astype(np.float32)
-    if flags & OUTLIERS:
-        mu1.flat[5] = 3.5
-    return x, dy, w, mu1, mu2
-
-
-def _plan(name, io, nhwc=False, extra=0):
-    from dau_conv import _capi
-    flags, (N, S, F, G, H, W), k, m = ALL_ROWS[name]
-    plan = _capi.Plan(N, S, F, G, H, W, max_kernel_size=k, sigma_hint=0.5,
-                      flags=I | flags | IO[io][0] | extra | (_capi.FLAG_IO_NHWC if nhwc else 0))
-    if name == "default_128":
-        assert plan.info["gather_dense_split"] == 0b11100
-    if name.startswith("split"):
-        assert plan.info["gather_dense_split"] & 0b11100 == 0b11100
-    if name.startswith("exact"):
-        assert plan.info["gather_dense_split"] == 0
-    if name == "k65_gather_windows":
-        assert plan.info["gather_windows"] == 4
-    if flags & OUTLIERS:
-        assert plan.info["gather_dense_split"] & (1 << 5)
-    return plan
-
-
-def _params(name):
-    x, dy, w, mu1, mu2 = _inputs(name)
-    dev = lambda a: torch.from_numpy(a).cuda()
-    S, G, F = w.shape[1:]
-    return dev(w), dev(mu1), dev(mu2), torch.full((1, S, G, F), 0.5, device="cuda")
-
-
-def _act(a, dtype, plan):
-    fmt = torch.channels_last if plan.io_layout == "NHWC" else torch.contiguous_format
-    return a.to(dtype).contiguous(memory_format=fmt)
-
+ROWS = mr.FUSED_ROWS                         # the parametrised tests run these, the slab test its four-image row as well
 
 _SHARED = {}        # name -> (x fp32 on the device, unfused fp32 y, bias, residual fp32): computed once, never written
 
@@ -100,10 +38,6 @@ def _shared(name):
     return _SHARED[name]
 
 
-def _io_of(plan):
-    return {torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[plan.io_dtype]
-
-
 def _fused(plan, name, x, epilogue, r, extra_plan=None):
     """the fused forward with the residual `r` (a tensor in the plan's dtype and layout, or None) on a plan of its own with `plan`'s
     flags: a plan's first call has no offset-bucket hint and runs the kernels of its static bucket, as the call that made the shared
@@ -112,14 +46,9 @@ def _fused(plan, name, x, epilogue, r, extra_plan=None):
     plan = extra_plan if extra_plan is not None else _plan(name, _io_of(plan), plan.io_layout == "NHWC")
     y = plan.forward(x, *_params(name), bias=bias if epilogue & BIAS else None, relu=bool(epilogue & RELU), residual=r)
     plan.check_status()
-    if ALL_ROWS[name][0] & OUTLIERS:
+    if mr.ROWS[name][0] & OUTLIERS:
         assert plan.outlier_status() == (1, True), "the radius-3 + ring member did not run"
     return y
-
-
-def _bits(t):
-    """the stored bits in logical [N, C, H, W] order, whatever the layout"""
-    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
 def _unfused(y, bias, r, epilogue):
@@ -199,12 +128,6 @@ def _raw(plan, name, x, bias, r, epilogue, y):
                                              p(sigma), p(bias), p(r), epilogue, p(y), p(ws), ws.numel())
     assert rc == _capi.DAU_OK, _capi.lib.dau_conv_last_error()
     torch.cuda.synchronize()
-
-
-def _nhwc_view(buf, shape, offset):
-    """a channels_last tensor of logical `shape` whose memory is buf[offset : offset + numel]"""
-    N, F, H, W = shape
-    return buf[offset:offset + N * F * H * W].view(N, H, W, F).permute(0, 3, 1, 2)
 
 
 @pytest.mark.parametrize("io", ["f32", "f16", "bf16"])

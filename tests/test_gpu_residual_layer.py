@@ -3,27 +3,19 @@ residual block, y = relu((dau(x) + bias) + r), with both adds and the ReLU insid
 gradient that depends on dz are bit for bit those of the composition torch.relu(layer_without_activation(x) + r), the residual's
 gradient is dz itself, the output keeps the input's dtype, and any residual the kernels cannot take is added in torch."""
 import copy
+import functools
 import warnings
 
 import pytest
 import torch
 import torch.nn as nn
 
+from layers import check_bias_grad as _check_bias_grad, close as _close, make_layer
+
 pytestmark = pytest.mark.gpu
 
 
-def _layer(S=8, F=16, **kw):
-    import dau_conv
-    torch.manual_seed(0)
-    kw.setdefault("use_bias", True)
-    kw.setdefault("activation", torch.relu)
-    kw.setdefault("mu_learning_rate_factor", 1.0)
-    kw.setdefault("bias_initializer", dau_conv.random_normal_initializer(stddev=0.5))
-    kw.setdefault("dau_units", (2, 2))
-    kw.setdefault("max_kernel_size", 9)
-    kw.setdefault("mu1_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    kw.setdefault("mu2_initializer", dau_conv.random_uniform_initializer(-3, 3))
-    return dau_conv.DAUConv2d(filters=F, in_channels=S, **kw).cuda()
+_layer = functools.partial(make_layer, activation=torch.relu)
 
 
 def _pair(**kw):
@@ -43,19 +35,6 @@ def _step(fn, layer, x, r, dy):
     y = fn(x, r)
     y.backward(dy)
     return y.detach(), x.grad, r.grad, {n: p.grad.clone() for n, p in layer.named_parameters() if p.grad is not None}
-
-
-def _close(got, want, rel=2e-3):
-    got, want = got.float(), want.float()
-    assert torch.isfinite(got).all()
-    err = ((got - want).abs() - rel * want.abs() - rel * want.abs().max()).max().item()
-    assert err <= 0, "differs by %.3e (max |want| %.3e)" % ((got - want).abs().max().item(), want.abs().max().item())
-
-
-def _check_bias_grad(got, y, dy):
-    dz = torch.where(y <= 0, torch.zeros_like(dy), dy).double()
-    exact, bound = dz.sum(dim=(0, 2, 3)), 2.0 ** -16 * dz.abs().sum(dim=(0, 2, 3))
-    assert bool(((got.double() - exact).abs() <= bound).all()), ((got.double() - exact).abs().tolist(), bound.tolist())
 
 
 def _data(S, F, seed=3):

@@ -7,18 +7,8 @@ import re
 
 import pytest
 
+from layers import _leave_the_plan_cache_as_it_was  # noqa: F401 (the autouse fixture)
 from test_capi_symbols import HEADER
-
-@pytest.fixture(autouse=True)
-def _leave_the_plan_cache_as_it_was():
-    """the layer's plan cache is bounded and least-recently-used: the plans these tests add would push other modules' plans out of
-    it (tests elsewhere compare its keys before and after a call), so each test takes its own out again"""
-    import importlib
-    impl = importlib.import_module("dau_conv.dau_conv")
-    before = set(impl._PLANS)
-    yield
-    for key in [k for k in impl._PLANS if k not in before]:
-        impl._PLANS.pop(key).last_status()      # (a pending offset error would be raised here, not lost)
 
 
 # S, F, G, H, W, kernel: the north-star layer, a small exact plan, a four-window plan, a forced-split odd shape

@@ -50,10 +50,26 @@ def case_kernel_size(c):
     raise ValueError(m)
 
 
-def make_inputs(seed, N, S, F, G, H, W, k, m, ignore=0):
-    """Synthetic tensors of SURVEY.md 8(d): x ~ U[0,1), dy ~ N(0,1), w ~ N(0, 0.1^2), mu ~ U(-m, m) clipped to the kernel."""
+def bits(t):
+    """the stored bits of a 16- or 32-bit tensor in logical [N, C, H, W] order, whatever the layout"""
+    import torch
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def assert_same_bits(got, want, what, keys):
+    """got[k] and want[k] hold the same bits, for every k of keys"""
+    import torch
+    for k in keys:
+        g, w = bits(got[k]), bits(want[k])
+        assert g.shape == w.shape, (what, k)
+        assert torch.equal(g, w), "%s: %d of %d values of %s differ" % (what, int((g != w).sum()), w.numel(), k)
+
+
+def make_inputs(seed, N, S, F, G, H, W, k, m, ignore=0, x="rand"):
+    """Synthetic tensors of SURVEY.md 8(d): x ~ U[0,1), dy ~ N(0,1), w ~ N(0, 0.1^2), mu ~ U(-m, m) clipped to the kernel.
+    x="randn" draws a sign-symmetric x instead, at the same place of the stream (every later draw changes with it)."""
     rs = np.random.RandomState(seed)
-    x = rs.rand(N, S, H, W).astype(np.float32)
+    x = getattr(rs, x)(N, S, H, W).astype(np.float32)
     dy = rs.randn(N, F, H, W).astype(np.float32)
     w = (rs.randn(1, S, G, F) * 0.1).astype(np.float32)
     if ignore:
