@@ -64,8 +64,6 @@ __device__ __forceinline__ void with_act(int act, F&& f) {
 // with its traits wrapped in NhwcOut<>.  (A common body inlined into two kernels was tried first: it changed the code of the NCHW ones.)
 // blur4_pack_kernel, whose instantiations the tests count by name, is one text compiled under two names (k_blur4_pack_body.hpp); the
 // small kernels that are no templates (pack_error, sd_stage_e / _e1, sd_absmax_e) have NHWC kernels written for that layout.
-// blur4_pack_kernel, whose instantiations the tests count by name, is one text compiled under two names (k_blur4_pack_body.hpp); the
-// small kernels that are no templates (pack_error, sd_stage_e / _e1, sd_absmax_e) have NHWC kernels written for that layout.
 constexpr int kNhwcArg = 0x100;
 template <class T> struct NhwcOut : T {};
 template <class T> struct IsNhwcOut : std::false_type {};
@@ -208,22 +206,29 @@ constexpr int kFilterFloats = kTaps1dOffset + kNumTap1d * kTapPitch;
 struct Status {
     unsigned int max_abs_mu_bits;  // float bits of max(|mu1|,|mu2|); valid because |x| bits order like uints
     unsigned int nan_seen;
-    // pad[0]: ticket counter of prepare_units_kernel's workgroups.  pad[1]: bits 0..30 the live units with max(|mu1|,|mu2|) > 3
-    // ("outlier units", counted by prepare_units_kernel), bit 31 set by the ring pass of a call whose gather-sum ran as the
-    // radius-3 GEMM plus ring (k_dense_ring.hip; dau_conv_gather_outlier_status reports both)
-    unsigned int pad[2];
-    // DAU_FLAG_DENSE_SPLIT_LINE.  line[0]: the units of the call's gather-sum table that do NOT lie on the row of their pixel
+    unsigned int ticket;           // ticket counter of prepare_units_kernel's workgroups
+    // bits 0..30 the live units with max(|mu1|,|mu2|) > 3 ("outlier units", counted by prepare_units_kernel), bit 31
+    // (kRingTakenBit) set by the ring pass of a call whose gather-sum ran as the radius-3 GEMM plus ring (k_dense_ring.hip;
+    // dau_conv_gather_outlier_status reports both)
+    unsigned int outlier_units;
+    // DAU_FLAG_DENSE_SPLIT_LINE.  off_line_units: the units of the call's gather-sum table that do NOT lie on the row of their pixel
     // (oy != 0 or a weight on the row below that is not zero -- a NaN counts; ignored units count too), counted by
-    // prepare_units_kernel.  line[1]: the radius of the line member that ran the pass (written by its scales kernel), 0 if none did.
-    unsigned int line[2];
-    // DAU_FLAG_SPLIT_DOT_LINE (dau_conv_dot_line_status).  pad2[0]: the units of the call's bare parameter-gradient table that do
-    // not lie on the row of their pixel, counted by the prepare_units_kernel of that pass -- which counts them into line[0] too,
-    // where the guards read the count; the pass puts line[0] back to zero behind itself, so that after a backward call line[0] is
-    // the count of the input-gradient table alone.  pad2[1]: the radius of the line member of the gather-dot that ran the pass
-    // (written by its dy maxima kernel), 0 if none did.
-    unsigned int pad2[2];
+    // prepare_units_kernel.  line_radius: the radius of the line member that ran the pass (written by its scales kernel), 0 if none did.
+    unsigned int off_line_units, line_radius;
+    // DAU_FLAG_SPLIT_DOT_LINE (dau_conv_dot_line_status).  dot_off_line_units: the units of the call's bare parameter-gradient table
+    // that do not lie on the row of their pixel, counted by the prepare_units_kernel of that pass -- which counts them into
+    // off_line_units too, where the guards read the count; the pass puts off_line_units back to zero behind itself, so that after
+    // a backward call off_line_units is the count of the input-gradient table alone.  dot_line_radius: the radius of the line
+    // member of the gather-dot that ran the pass (written by its dy maxima kernel), 0 if none did.
+    unsigned int dot_off_line_units, dot_line_radius;
 };
 constexpr unsigned kRingTakenBit = 0x80000000u;
+// synth_filters_kernel clears the block by word count, run_param_sums clears one word of it, and the queries read a copy of it
+static_assert(sizeof(Status) == 32, "the status block is eight words");
+static_assert(offsetof(Status, max_abs_mu_bits) == 0 && offsetof(Status, nan_seen) == 4 && offsetof(Status, ticket) == 8 &&
+              offsetof(Status, outlier_units) == 12 && offsetof(Status, off_line_units) == 16 && offsetof(Status, line_radius) == 20 &&
+              offsetof(Status, dot_off_line_units) == 24 && offsetof(Status, dot_line_radius) == 28,
+              "the status block keeps the order of its words");
 
 // Pinned host mirror of a plan (written by the last workgroup of prepare_units_kernel, read by dau_conv_last_status and as
 // the next call's offset-bucket hint): the most recent completed call's status, and the sticky record of bad ones.
@@ -241,7 +246,7 @@ static_assert(sizeof(HostStatus) == 32, "the pinned status mirror is 32 bytes (i
 // two candidate buckets; every kernel of a set starts with guard_pass() and returns at once unless the actual max|mu|
 // falls into (lo, hi] -- exactly one set does the work, without a device->host sync (the reference blocks on a D2H copy
 // of the amax for this, dau_conv_op.cpp:229-253).  status == nullptr: unguarded.
-// A guard may also ask for the call's outlier-unit count (Status.pad[1]) to lie in [cnt_lo, cnt_hi] while max|mu| <= cnt_upto
+// A guard may also ask for the call's outlier-unit count (Status::outlier_units) to lie in [cnt_lo, cnt_hi] while max|mu| <= cnt_upto
 // (the default range means "any"): the radius-3 + ring member runs below a count limit, the members that share its offset range
 // above it.
 struct Guard {
@@ -249,19 +254,19 @@ struct Guard {
     float lo, hi;
     unsigned cnt_lo = 0u, cnt_hi = 0xffffffffu;
     float cnt_upto = INFINITY;
-    // DAU_FLAG_DENSE_SPLIT_LINE, DAU_FLAG_SPLIT_DOT_LINE (Status.line[0], the units off the line of the pass's table).  +R: a line member, runs only where that count is 0.
+    // DAU_FLAG_DENSE_SPLIT_LINE, DAU_FLAG_SPLIT_DOT_LINE (Status::off_line_units, the units off the line of the pass's table).  +R: a line member, runs only where that count is 0.
     // -R: a member that shares offsets within +-R with a line member, runs there only where the count is not 0.  0: any.
     // Kernels only READ the status block through their guard, with one exception: the scales kernel of a line member whose guard
-    // has passed writes its radius to Status::line[1] (k_dense_split.hip, split_scales_kernel under DAU_SPLIT_1D).
+    // has passed writes its radius to Status::line_radius (k_dense_split.hip, split_scales_kernel under DAU_SPLIT_1D).
     int line = 0;
 };
 __device__ __forceinline__ bool guard_pass(const Guard& g) {
     if (!g.status) return true;
     const float mx = __uint_as_float(g.status->max_abs_mu_bits);
-    const unsigned cnt = g.status->pad[1] & ~kRingTakenBit;
+    const unsigned cnt = g.status->outlier_units & ~kRingTakenBit;
     if (!(mx > g.lo && mx <= g.hi && (mx > g.cnt_upto || (cnt >= g.cnt_lo && cnt <= g.cnt_hi)))) return false;
     if (g.line == 0) return true;
-    const bool on_line = g.status->line[0] == 0u;
+    const bool on_line = g.status->off_line_units == 0u;
     return g.line > 0 ? on_line : (mx > (float)-g.line || !on_line);
 }
 
@@ -286,8 +291,8 @@ void launch_synth_filters_compact(hipStream_t st, const float* sigma_dev, int k,
 // k_units.hip
 // host_status (may be null): pinned host copy of the status block, written by the last workgroup to finish
 // count_ignore: the units left out of the status block's outlier count (-1: `ignore`; the input-gradient table ignores no unit)
-// line_status (may be null; DAU_FLAG_DENSE_SPLIT_LINE / DAU_FLAG_SPLIT_DOT_LINE): the status block whose line[0] takes the count of this
-// table's units off the line; line_dot: the table of the parameter-gradient pass, whose count goes to pad2[0] as well
+// line_status (may be null; DAU_FLAG_DENSE_SPLIT_LINE / DAU_FLAG_SPLIT_DOT_LINE): the status block whose off_line_units takes the count of this
+// table's units off the line; line_dot: the table of the parameter-gradient pass, whose count goes to dot_off_line_units as well
 void launch_prepare_units(hipStream_t st, const float* w, const float* mu1, const float* mu2, Shape sh,
                           int ignore, int flags, int bucket, bool transposed_negated, UnitRef* table,
                           Status* status, HostStatus* host_status, int count_ignore = -1, Status* line_status = nullptr,

@@ -90,20 +90,41 @@ enum Member {
     kNumMembers
 };
 enum PassKind { kGatherSum, kGatherDot };
-// the offsets a bucket-4 member covers (its device guard's upper end)
-constexpr int kRadius[kNumMembers] = {0, 2, 3, 4, 4, 8, 3, 4, 0, 4, 8, 4, 3, 4};
+// the entry points and the config type a member has: its function table below and its array in BucketSet
+enum Family { kFamTiledGather, kFamDense, kFamTiledDot, kFamSplitDot, kFamWgrad };
+// What a member is.  Every non-exact member has an arithmetic of its own and goes ahead of the bucket sets under its own guard,
+// except the radius-4 bf16 members: they run in place of their set's exact kernels.
+struct MemberInfo {
+    int kind;        // PassKind
+    int family;      // Family
+    int slot;        // its row in the family's function table and config array
+    int radius;      // the offsets a bucket-4 member covers (its device guard's upper end)
+    bool ahead;      // goes ahead of the bucket sets
+    bool line;       // a line form: runs the calls whose units lie on a line
+    int info_bit;    // the bit of dau_conv_plan_info::gather_dense_split that reports it (-1: none)
+};
+constexpr MemberInfo kMember[kNumMembers] = {
+    {kGatherSum, kFamTiledGather, 0, 0, false, false, -1},   // kTiledGather
+    {kGatherSum, kFamDense, 0, 2, true, false, 2},           // kSplit2
+    {kGatherSum, kFamDense, 1, 3, true, false, 3},           // kSplit3
+    {kGatherSum, kFamDense, 2, 4, true, false, 4},           // kSplit4
+    {kGatherSum, kFamDense, 3, 4, true, true, 6},            // kLine4
+    {kGatherSum, kFamDense, 4, 8, true, true, 7},            // kLine8
+    {kGatherSum, kFamDense, 5, 3, true, false, -1},          // kBf16R3
+    {kGatherSum, kFamDense, 6, 4, false, false, -1},         // kBf16R4
+    {kGatherDot, kFamTiledDot, 0, 0, false, false, -1},      // kTiledDot
+    {kGatherDot, kFamSplitDot, 0, 4, true, true, 8},         // kDotLine4
+    {kGatherDot, kFamSplitDot, 1, 8, true, true, 9},         // kDotLine8
+    {kGatherDot, kFamSplitDot, 2, 4, true, false, -1},       // kSplitDot
+    {kGatherDot, kFamWgrad, 0, 3, true, false, -1},          // kWgradR3
+    {kGatherDot, kFamWgrad, 1, 4, false, false, -1},         // kWgradR4
+};
+constexpr int kRingInfoBit = 5;                              // likewise, the radius-3 + ring member (BucketSet::ring)
 constexpr int kFirst[2] = {kTiledGather, kTiledDot}, kEnd[2] = {kTiledDot, kNumMembers};   // the members of a pass kind
-// The radius-4 bf16 member runs in place of its set's exact kernels; every other non-exact member has an arithmetic of its own
-// and goes ahead of the bucket sets under its own guard.
-constexpr int kDense4[2] = {kBf16R4, kWgradR4};
-constexpr bool goes_ahead(int m) { return m != kTiledGather && m != kTiledDot && m != kBf16R4 && m != kWgradR4; }
-constexpr bool is_line(int m) { return m == kLine4 || m == kLine8 || m == kDotLine4 || m == kDotLine8; }
-constexpr int kFirstLine[2] = {kLine4, kDotLine4};         // the two line members of a pass kind, radius 4 and 8
-
 // gather-sum directions, which are also their profile slots: y from x (S -> F) and dx from the error (F -> S)
 enum Dir { kFwd, kDx };
 
-// the dense gather-sum members kSplit2 .. kBf16R4, one set of entry points each (index m - kSplit2)
+// the dense gather-sum members kSplit2 .. kBf16R4, one set of entry points each
 struct DenseFns {
     bool (*configure)(int, int, int, int, int, int, int, int, int, DenseConfig*);
     size_t (*workspace_bytes)(const DenseConfig&);
@@ -123,8 +144,22 @@ const DenseFns kDense[] = {
     {r3::dense_gather_configure, r3::dense_gather_workspace_bytes, r3::dense_gather_init, r3::dense_gather_prepare, run_plain<r3::dense_gather_run>},
     {r4::dense_gather_configure, r4::dense_gather_workspace_bytes, r4::dense_gather_init, r4::dense_gather_prepare, run_plain<r4::dense_gather_run>},
 };
-constexpr int kNumDense = kBf16R4 - kSplit2 + 1;
-// the bf16 dense parameter-gradient members kWgradR3, kWgradR4 (index m - kWgradR3)
+constexpr int kNumDense = sizeof(kDense) / sizeof(kDense[0]);
+// the two-limb gather-dot members kDotLine4, kDotLine8 and kSplitDot: the 2-D member has the entry points of its line forms
+struct SplitDotFns {
+    bool (*configure)(const Shape&, int, int, SplitDotConfig*);
+    size_t (*workspace_bytes)(const SplitDotConfig&);
+    void (*init)(const SplitDotConfig&);
+    void (*prepare)(hipStream_t, const SplitDotConfig&, const float*, const float*, const float*, int, int, void*, const Guard&);
+    void (*run)(hipStream_t, const SplitDotConfig&, const UnitRef*, float*, void*, const Guard&);
+};
+const SplitDotFns kSplitDotFns[] = {
+    {d4::split_dot_configure, d4::split_dot_workspace_bytes, d4::split_dot_init, d4::split_dot_prepare, d4::split_dot_run},
+    {d8::split_dot_configure, d8::split_dot_workspace_bytes, d8::split_dot_init, d8::split_dot_prepare, d8::split_dot_run},
+    {split_dot_configure, split_dot_workspace_bytes, split_dot_init, split_dot_prepare, split_dot_run},
+};
+constexpr int kNumSplitDot = sizeof(kSplitDotFns) / sizeof(kSplitDotFns[0]);
+// the bf16 dense parameter-gradient members kWgradR3, kWgradR4
 struct WgradFns {
     bool (*configure)(const Shape&, int, bool, WgradConfig*);
     size_t (*workspace_bytes)(const WgradConfig&);
@@ -136,19 +171,8 @@ const WgradFns kWgrad[] = {
     {r3::dense_wgrad_configure, r3::dense_wgrad_workspace_bytes, r3::dense_wgrad_init, r3::dense_wgrad_run},
     {r4::dense_wgrad_configure, r4::dense_wgrad_workspace_bytes, r4::dense_wgrad_init, r4::dense_wgrad_run},
 };
-
-// the line members of the two-limb gather-dot kDotLine4, kDotLine8 (index m - kDotLine4)
-struct DotLineFns {
-    bool (*configure)(const Shape&, int, int, SplitDotConfig*);
-    size_t (*workspace_bytes)(const SplitDotConfig&);
-    void (*init)(const SplitDotConfig&);
-    void (*prepare)(hipStream_t, const SplitDotConfig&, const float*, const float*, const float*, int, int, void*, const Guard&);
-    void (*run)(hipStream_t, const SplitDotConfig&, const UnitRef*, float*, void*, const Guard&);
-};
-const DotLineFns kDotLine[] = {
-    {d4::split_dot_configure, d4::split_dot_workspace_bytes, d4::split_dot_init, d4::split_dot_prepare, d4::split_dot_run},
-    {d8::split_dot_configure, d8::split_dot_workspace_bytes, d8::split_dot_init, d8::split_dot_prepare, d8::split_dot_run},
-};
+static_assert(kMember[kBf16R4].slot == kNumDense - 1 && kMember[kSplitDot].slot == kNumSplitDot - 1 && kMember[kWgradR4].slot == 1,
+              "a member's slot is its row in its family's function table");
 
 // The kernels of one offset bucket.  A plan holds one set per bucket up to the static one (the bucket max_kernel_size allows);
 // which set and member run is decided per call from the actual max|mu| (pick_candidates below).
@@ -156,11 +180,10 @@ struct BucketSet {
     int bucket = 0;
     bool has[kNumMembers] = {};   // the members this set holds
     TiledConfig tiled[2];         // [Dir]
-    DenseConfig dense[kNumDense][2];
+    DenseConfig dense[kNumDense][2];   // [MemberInfo::slot][Dir]
     TiledDotConfig tiled_dot;
-    SplitDotConfig sdot;
-    SplitDotConfig sdline[2];     // kDotLine4, kDotLine8
-    WgradConfig wgrad[2];
+    SplitDotConfig sdot[kNumSplitDot]; // [MemberInfo::slot]
+    WgradConfig wgrad[2];              // [MemberInfo::slot]
     // Batch slabs.  Every pass stages its whole input before it gathers; where that staged copy would exceed the workspace
     // budget (DAU_WORKSPACE_BUDGET_GB at plan creation, default 12: only the 512 x 512 configurations get there) the pass
     // runs slab by slab over the batch -- the configs above are made for `slab_*` images, the passes loop -- so that the
@@ -172,30 +195,35 @@ struct BucketSet {
     bool ring = false;
     unsigned ring_limit = 0;
     RingConfig ringcfg[2];        // [Dir]
+    const DenseConfig& ring_dense(int dir) const { return dense[kMember[kSplit3].slot][dir]; }   // kSplit3's config, which the ring member runs on
 };
 // The outlier-unit count up to which the radius-3 + ring member runs, in thousandths of the plan's live units: the largest tested
 // fraction at which its two gather-sum passes took at most 0.9 x what the members it stands in for take on the same inputs
 // -- 1 %: 0.79 x at 0.1 %, 0.89 x at 1 %, 1.14 x at 3 % at the north-star layer (profiles/r9_ab_dense_outliers.jsonl).
 constexpr int kRingLimitPermille = 10;
 constexpr int kBuckets[] = {4, 8, 16, 18, 20, 24, 32};
-constexpr int kNumBuckets = 7;
+constexpr int kNumBuckets = sizeof(kBuckets) / sizeof(kBuckets[0]);
 
-// workspace a set's gather-sum members need in one direction, and its parameter-gradient members
-size_t gather_bytes(const BucketSet& bs, int dir) {
-    size_t need = bs.has[kTiledGather] ? tiled_gather_workspace_bytes(bs.tiled[dir]) : 0;
-    for (int m = kSplit2; m <= kBf16R4; ++m)
-        if (bs.has[m]) need = std::max(need, kDense[m - kSplit2].workspace_bytes(bs.dense[m - kSplit2][dir]));
-    // the ring list and the fp32 partial sums of the slab, behind the radius-3 form's own workspace
-    if (bs.ring) need = std::max(need, s3::split_gather_workspace_bytes(bs.dense[kSplit3 - kSplit2][dir]) + ring_workspace_bytes(bs.ringcfg[dir]));
-    return need;
+// The one place that maps a member to its entry points and its config: f(workspace_bytes, init, config) for member m of a set
+// (dir: a gather-sum member's direction).
+template <class F>
+auto with_member(const BucketSet& bs, int m, int dir, F&& f) {
+    const int i = kMember[m].slot;
+    switch (kMember[m].family) {
+    case kFamTiledGather: return f(tiled_gather_workspace_bytes, tiled_gather_init, bs.tiled[dir]);
+    case kFamDense: return f(kDense[i].workspace_bytes, kDense[i].init, bs.dense[i][dir]);
+    case kFamTiledDot: return f(tiled_dot_workspace_bytes, tiled_dot_init, bs.tiled_dot);
+    case kFamSplitDot: return f(kSplitDotFns[i].workspace_bytes, kSplitDotFns[i].init, bs.sdot[i]);
+    default: return f(kWgrad[i].workspace_bytes, kWgrad[i].init, bs.wgrad[i]);
+    }
 }
-size_t dot_bytes(const BucketSet& bs) {
-    size_t need = bs.has[kTiledDot] ? tiled_dot_workspace_bytes(bs.tiled_dot) : 0;
-    if (bs.has[kSplitDot]) need = std::max(need, split_dot_workspace_bytes(bs.sdot));
-    for (int m = kDotLine4; m <= kDotLine8; ++m)
-        if (bs.has[m]) need = std::max(need, kDotLine[m - kDotLine4].workspace_bytes(bs.sdline[m - kDotLine4]));
-    for (int m = kWgradR3; m <= kWgradR4; ++m)
-        if (bs.has[m]) need = std::max(need, kWgrad[m - kWgradR3].workspace_bytes(bs.wgrad[m - kWgradR3]));
+// workspace the members of one pass kind need in a set: they run one after the other in the same memory
+size_t pass_bytes(const BucketSet& bs, int kind, int dir = kFwd) {
+    size_t need = 0;
+    for (int m = kFirst[kind]; m < kEnd[kind]; ++m)
+        if (bs.has[m]) need = std::max(need, with_member(bs, m, dir, [](auto bytes, auto, const auto& cfg) { return bytes(cfg); }));
+    // the ring list and the fp32 partial sums of the slab, behind the radius-3 form's own workspace
+    if (kind == kGatherSum && bs.ring) need = std::max(need, s3::split_gather_workspace_bytes(bs.ring_dense(dir)) + ring_workspace_bytes(bs.ringcfg[dir]));
     return need;
 }
 
@@ -328,7 +356,11 @@ constexpr int kMaxCandidates = 14;   // (the most: 2 line + 2 ahead + the radius
 int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, Candidate out[kMaxCandidates]) {
     const BucketSet* top = &p->top();
     const BucketSet* s0 = &p->sets[0];
-    auto member_of = [&](const BucketSet* b) { return b->has[kDense4[kind]] ? kDense4[kind] : kFirst[kind]; };
+    auto member_of = [&](const BucketSet* b) {               // the member that runs in place of the set's exact kernels, or those
+        for (int m = kFirst[kind]; m < kEnd[kind]; ++m)
+            if (kMember[m].radius && !kMember[m].ahead && b->has[m]) return m;
+        return kFirst[kind];
+    };
     out[0] = Candidate{top, Guard{nullptr, 0.0f, 0.0f}, member_of(top)};
     if (!p->dynamic) return 1;
     const BucketSet* hinted = nullptr;
@@ -347,12 +379,12 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
     float lo = -1.0f;
     bool with_ring = false;
     int line_r = 0;                                          // the offsets the line members cover
-    for (int m = kFirstLine[kind]; m <= kFirstLine[kind] + 1; ++m) {
-        if (!s0->has[m]) continue;
-        Guard g{dev_status, (float)line_r - (line_r ? 0.0f : 1.0f), (float)kRadius[m]};
-        g.line = kRadius[m];
+    for (int m = kFirst[kind]; m < kEnd[kind]; ++m) {        // (smaller radius first)
+        if (!(kMember[m].line && s0->has[m])) continue;
+        Guard g{dev_status, (float)line_r - (line_r ? 0.0f : 1.0f), (float)kMember[m].radius};
+        g.line = kMember[m].radius;
         out[n++] = Candidate{s0, g, m};
-        line_r = kRadius[m];
+        line_r = kMember[m].radius;
     }
     auto add = [&](const BucketSet* b, int member, float hi) {
         Guard g{dev_status, lo, hi};
@@ -362,8 +394,8 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
         lo = hi;
     };
     for (int m = kFirst[kind]; m < kEnd[kind]; ++m) {
-        if (!(goes_ahead(m) && s0->has[m]) || is_line(m)) continue;
-        add(s0, m, (float)kRadius[m]);
+        if (!(kMember[m].ahead && s0->has[m]) || kMember[m].line) continue;
+        add(s0, m, (float)kMember[m].radius);
         if (m == kSplit3 && s0->ring) {
             Guard g{dev_status, 3.0f, 4.0f, 0u, s0->ring_limit};
             g.line = -line_r;
@@ -371,7 +403,7 @@ int pick_candidates(const dau_conv_plan* p, const Status* dev_status, int kind, 
             with_ring = true;
         }
     }
-    if (s0->has[kDense4[kind]] && hinted != s0 && s0 != top) add(s0, kDense4[kind], (float)s0->bucket);
+    if (member_of(s0) != kFirst[kind] && hinted != s0 && s0 != top) add(s0, member_of(s0), (float)s0->bucket);
     if (kind == kGatherDot) {                                // by the call's own offsets alone (see Candidate)
         for (int i = 0; i + 1 < p->nsets; ++i)
             if (p->sets[i].has[kFirst[kind]] && lo < (float)p->sets[i].bucket)
@@ -397,12 +429,8 @@ int ensure_attrs(const dau_conv_plan* p) {
         const BucketSet& bs = p->sets[i];
         for (int m = 0; m < kNumMembers; ++m) {
             if (!bs.has[m]) continue;
-            if (m == kTiledGather) for (int dir : {kFwd, kDx}) tiled_gather_init(bs.tiled[dir]);
-            else if (m <= kBf16R4) for (int dir : {kFwd, kDx}) kDense[m - kSplit2].init(bs.dense[m - kSplit2][dir]);
-            else if (m == kTiledDot) tiled_dot_init(bs.tiled_dot);
-            else if (m == kSplitDot) split_dot_init(bs.sdot);
-            else if (m == kDotLine4 || m == kDotLine8) kDotLine[m - kDotLine4].init(bs.sdline[m - kDotLine4]);
-            else kWgrad[m - kWgradR3].init(bs.wgrad[m - kWgradR3]);
+            for (int dir = kFwd; dir <= (kMember[m].kind == kGatherSum ? kDx : kFwd); ++dir)   // (a gather-sum member: both directions)
+                with_member(bs, m, dir, [](auto, auto init, const auto& cfg) { init(cfg); });
         }
         if (bs.ring) ring_init();
         const hipError_t e = hipGetLastError();
@@ -414,15 +442,10 @@ int ensure_attrs(const dau_conv_plan* p) {
     return DAU_OK;
 }
 
-// workspace of the tiled passes: the largest need of any set (the candidates run one after the other in the same memory)
-size_t tiled_gather_bytes(const dau_conv_plan* p, int dir) {
+// workspace of a tiled pass: the largest need of any set (the candidates run one after the other in the same memory)
+size_t tiled_pass_bytes(const dau_conv_plan* p, int kind, int dir = kFwd) {
     size_t need = 0;
-    for (int i = 0; i < p->nsets; ++i) need = std::max(need, gather_bytes(p->sets[i], dir));
-    return need;
-}
-size_t tiled_dot_bytes(const dau_conv_plan* p) {
-    size_t need = 0;
-    for (int i = 0; i < p->nsets; ++i) need = std::max(need, dot_bytes(p->sets[i]));
+    for (int i = 0; i < p->nsets; ++i) need = std::max(need, pass_bytes(p->sets[i], kind, dir));
     return need;
 }
 
@@ -440,7 +463,7 @@ FwdWs carve_forward(const dau_conv_plan* p, void* ws) {
     w.status = c.take<Status>(1);
     w.filters = c.take<float>(kFilterFloats);
     w.table = c.take<UnitRef>(p->units());
-    if (p->algo_fwd == DAU_ALGO_TILED) w.gather = c.take<char>(tiled_gather_bytes(p, kFwd));
+    if (p->algo_fwd == DAU_ALGO_TILED) w.gather = c.take<char>(tiled_pass_bytes(p, kGatherSum, kFwd));
     else w.gather = c.take<float>((size_t)p->sh.N * p->sh.S * p->sh.H * p->sh.W);
     w.bytes = c.off;
     return w;
@@ -467,9 +490,9 @@ BwdWs carve_backward(const dau_conv_plan* p, void* ws) {
     w.table_bare = c.take<UnitRef>(p->units());
     w.table_t = c.take<UnitRef>(p->units());
     w.r4 = c.take<float>(kNumK * p->units());
-    if (p->algo_bwd == DAU_ALGO_TILED) w.tiled_dot = c.take<char>(tiled_dot_bytes(p));
+    if (p->algo_bwd == DAU_ALGO_TILED) w.tiled_dot = c.take<char>(tiled_pass_bytes(p, kGatherDot));
     else w.xk4 = c.take<float>((size_t)kNumK * s.N * s.S * s.H * s.W);
-    if (p->algo_fwd == DAU_ALGO_TILED) w.gather_dx = c.take<char>(tiled_gather_bytes(p, kDx));
+    if (p->algo_fwd == DAU_ALGO_TILED) w.gather_dx = c.take<char>(tiled_pass_bytes(p, kGatherSum, kDx));
     else w.gather_dx = c.take<float>((size_t)s.N * s.F * s.H * s.W);
     w.bytes = c.off;
     return w;
@@ -500,7 +523,7 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
         const int m = cand[ci].member;
         const bool ring = cand[ci].ring;
         // the ring member's list and partial sums lie behind the radius-3 form's workspace; the list is built once per pass
-        void* ring_ws = ring ? static_cast<char*>(ws) + s3::split_gather_workspace_bytes(bs.dense[kSplit3 - kSplit2][dir]) : nullptr;
+        void* ring_ws = ring ? static_cast<char*>(ws) + s3::split_gather_workspace_bytes(bs.ring_dense(dir)) : nullptr;
         if (ring) ring_build_list(st, bs.ringcfg[dir], table, ring_ws, g);
         for (int n0 = 0; n0 < s.N; n0 += bs.slab_gather) {                 // one slab unless the staged copy exceeds the budget
             const float* ins = slab_ptr(in, (size_t)n0 * cin * s.H * s.W, p->esize());
@@ -517,8 +540,8 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
                     tiled_gather_run(st, cfg, outs, ws, window > 0, g, window + 1 == nwin ? epis : Epilogue{});
                 }
             } else {                                                       // a dense member: one GEMM per slab
-                const DenseFns& fn = kDense[m - kSplit2];
-                const DenseConfig& cfg = bs.dense[m - kSplit2][dir];
+                const DenseFns& fn = kDense[kMember[m].slot];
+                const DenseConfig& cfg = bs.dense[kMember[m].slot][dir];
                 fn.prepare(st, cfg, ins, filters, mirrored, table, ws, g);
                 ProfScope prof(p, dir, st);
                 if (ring) {                                                // the ring pass, then the GEMM whose epilogue adds its sums
@@ -530,6 +553,191 @@ void run_gather_sum(const dau_conv_plan* p, hipStream_t st, int dir, const float
             }
         }
     }
+}
+
+// The flag rules of a desc, in the order in which they are checked: a desc that sets any of `flags` must set all of `needs` and
+// none of `excludes`.
+struct FlagRule {
+    int flags, needs, excludes;
+    const char* message;
+};
+constexpr int kWgradFlags = DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS;
+constexpr int kNoSplitFlags = DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT;
+constexpr FlagRule kFlagRules[] = {
+    {DAU_FLAG_IO_F16, 0, DAU_FLAG_IO_BF16 | DAU_FLAG_DENSE_BF16 | kWgradFlags,
+     "DAU_FLAG_IO_F16 excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS"},
+    {DAU_FLAG_DENSE_BF16, DAU_FLAG_IO_BF16, 0, "DAU_FLAG_DENSE_BF16 needs DAU_FLAG_IO_BF16 (it is the bf16 layer's gather-sum)"},
+    {DAU_FLAG_DENSE_SPLIT_F16, 0, kNoSplitFlags, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT"},
+    {DAU_FLAG_DENSE_SPLIT_OUTLIERS, 0, kNoSplitFlags, "DAU_FLAG_DENSE_SPLIT_OUTLIERS excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT"},
+    {DAU_FLAG_DENSE_SPLIT_LINE, DAU_FLAG_SINGLE_DIM_KERNEL, 0, "DAU_FLAG_DENSE_SPLIT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL"},
+    {DAU_FLAG_DENSE_SPLIT_LINE, 0, kNoSplitFlags, "DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT"},
+    {DAU_FLAG_SPLIT_DOT_LINE, DAU_FLAG_SINGLE_DIM_KERNEL, 0, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL"},
+    {DAU_FLAG_SPLIT_DOT_LINE, DAU_FLAG_USE_INTERPOLATION, 0, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_USE_INTERPOLATION"},
+    {DAU_FLAG_SPLIT_DOT_LINE, 0, kNoSplitFlags, "DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT"},
+    {kWgradFlags, DAU_FLAG_DENSE_BF16, 0, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other"},
+    {DAU_FLAG_DENSE_WGRAD_NEVER, 0, DAU_FLAG_DENSE_WGRAD_ALWAYS, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other"},
+    {DAU_FLAG_IO_NHWC, 0, DAU_FLAG_DENSE_BF16 | kWgradFlags, "DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS"},
+    {DAU_FLAG_INPUT_RELU, 0, DAU_FLAG_DENSE_BF16, "DAU_FLAG_INPUT_RELU excludes DAU_FLAG_DENSE_BF16 (the bf16-product forms have no input prologue)"},
+};
+
+// (a) what a desc must satisfy whatever the kernels support; gives the static offset bucket and the prefilter support
+int validate_desc(const dau_conv_desc* desc, int& bucket, int& blur_k) {
+    if (desc->struct_size != (int32_t)sizeof(dau_conv_desc))
+        return fail(DAU_INVALID_ARGUMENT, "dau_conv_desc.struct_size %d != %zu", desc->struct_size, sizeof(dau_conv_desc));
+    if (desc->batch < 1 || desc->in_channels < 1 || desc->out_channels < 1 || desc->units_per_channel < 1 ||
+        desc->height < 1 || desc->width < 1)
+        return fail(DAU_INVALID_ARGUMENT, "all of N,S,F,G,H,W must be >= 1");
+    if (desc->number_units_ignore < 0 || desc->number_units_ignore >= desc->units_per_channel)
+        return fail(DAU_INVALID_ARGUMENT, "number_units_ignore must be in [0, G)");
+    if (desc->max_kernel_size < 3 || desc->max_kernel_size % 2 == 0)
+        return fail(DAU_INVALID_ARGUMENT, "kernel_size must be odd and >= 3");
+    // offset bucket from the largest displacement the attrs allow (dau_conv_op.cpp:236-253)
+    bucket = 0;
+    for (int b : kBuckets)
+        if (!bucket && desc->max_kernel_size / 2 <= b) bucket = b;
+    if (!bucket)
+        return fail(DAU_INVALID_ARGUMENT,
+                    "DAUConv: offsets larger than the 32 px the kernels stage (set max_kernel_size <= 65)");
+    if (!(desc->sigma_hint > 0.0f))  // DAU_CHECK(sigma > 0) base_dau_conv_layer.cpp:143
+        return fail(DAU_FAILED_PRECONDITION, "Must use sigma > 0 - initialize it with appropriate value");
+    blur_k = dau_conv_filter_support(desc->sigma_hint);
+    if (blur_k > kMaxBlurSupport)
+        return fail(DAU_INVALID_ARGUMENT, "sigma %.3f needs a %dx%d prefilter; at most %dx%d is supported", desc->sigma_hint,
+                    blur_k, blur_k, kMaxBlurSupport, kMaxBlurSupport);
+    if (desc->algo < DAU_ALGO_AUTO || desc->algo > DAU_ALGO_TILED) return fail(DAU_INVALID_ARGUMENT, "unknown algo");
+    for (const FlagRule& r : kFlagRules)
+        if ((desc->flags & r.flags) && ((desc->flags & r.needs) != r.needs || (desc->flags & r.excludes)))
+            return fail(DAU_INVALID_ARGUMENT, "%s", r.message);
+    return DAU_OK;
+}
+
+// (b) the members and configs of the set of bs.bucket
+void configure_set(const dau_conv_plan& p, double budget_bytes, BucketSet& bs) {
+    const Shape& s = p.sh;
+    const int flags = p.d.flags, b = bs.bucket, blur_k = p.blur_k, act = p.act(), ignore = p.d.number_units_ignore;
+    const bool want_dense = (flags & DAU_FLAG_DENSE_BF16) && p.d.algo != DAU_ALGO_DIRECT;
+    const bool split_forced = (flags & DAU_FLAG_DENSE_SPLIT_F16) != 0;
+    const bool split_allowed = !(flags & kNoSplitFlags) && p.d.algo != DAU_ALGO_DIRECT;
+    const int g_live = s.G - ignore;
+    const long live_units = (long)s.S * s.F * g_live, ignored_units = (long)s.S * s.F * ignore;
+    // a line member of radius 8 is held where the plan's offsets reach it and the one of radius 4 (the member before it) is held
+    // (DAU_FLAG_STATIC_BUCKET: no per-call selection, the line flags are inert as the outliers flag is)
+    auto line_wanted = [&](int m, int flag) {
+        return (flags & flag) && !(flags & DAU_FLAG_STATIC_BUCKET) && (kMember[m].radius == 4 || (p.bucket >= 8 && bs.has[m - 1]));
+    };
+    // does the dense gather-sum form of `taps` taps pay in both directions (or is it forced)
+    auto pays = [&](double taps) {
+        return split_forced || (split_pays(taps, s.S, s.F, g_live, s.H, s.W) && split_pays(taps, s.F, s.S, g_live, s.H, s.W));
+    };
+    // both directions of dense gather-sum member m, for n images
+    auto configure_dense = [&](int m, int n) {
+        const int i = kMember[m].slot, r = kMember[m].radius;
+        return kDense[i].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &bs.dense[i][kFwd]) &&
+               kDense[i].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &bs.dense[i][kDx]);
+    };
+    auto configure_gather = [&](int n) {
+        bs.has[kTiledGather] = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kFwd]) &&
+                               tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kDx]);
+        const bool dense_set = b == 4 && bs.has[kTiledGather];   // the dense members: bucket 4 only
+        // downwards, as the bf16 radius-3 member needs the radius-4 one
+        for (int m = kBf16R4; m >= kSplit2; --m) {
+            if (kMember[m].line) continue;                   // (below)
+            const double side = 2.0 * kMember[m].radius + 1;
+            const bool want = m == kBf16R4 ? want_dense : m == kBf16R3 ? bs.has[kBf16R4] : split_allowed && pays(side * side);
+            bs.has[m] = dense_set && want && configure_dense(m, n);
+        }
+        // the line members: bucket 4's set like the others
+        for (int m = kLine4; m <= kLine8; ++m)
+            bs.has[m] = dense_set && line_wanted(m, DAU_FLAG_DENSE_SPLIT_LINE) && split_allowed && pays(2.0 * kMember[m].radius + 1) &&
+                        configure_dense(m, n);
+        // radius 3 + ring: where the radius-3 member is; its list holds the entries of ring_limit live units and of the ignored ones
+        // (the input-gradient table ignores no unit, and the count leaves them out)
+        bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
+        if (bs.ring) {
+            bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
+            for (int dir : {kFwd, kDx}) ring_configure(bs.ring_dense(dir), (long)bs.ring_limit + ignored_units, &bs.ringcfg[dir]);
+        }
+        return std::max(pass_bytes(bs, kGatherSum, kFwd), pass_bytes(bs, kGatherSum, kDx));
+    };
+    auto configure_dot = [&](int n) {
+        Shape sn = s; sn.N = n;
+        bs.has[kTiledDot] = tiled_dot_configure(sn, b, blur_k, act, ignore, &bs.tiled_dot);
+        return pass_bytes(bs, kGatherDot);
+    };
+    // (c) slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
+    auto pick_slab = [&](auto&& configure) {
+        int chosen = s.N;
+        for (int n = s.N; n >= 2; --n) {
+            if (s.N % n || (n != s.N && (n & 1))) continue;
+            chosen = n;
+            if ((double)configure(n) <= budget_bytes) break;
+        }
+        configure(chosen);
+        return chosen;
+    };
+    bs.slab_gather = pick_slab(configure_gather);
+    bs.slab_dot = pick_slab(configure_dot);
+    const bool whole_dot = b == 4 && bs.has[kTiledDot] && bs.slab_dot == s.N;
+    // dense parameter gradients: the bf16-dense layer's bucket-4 set, whole batch in one slab, three or more units (its cost
+    // does not depend on the unit count: 15.3 ms at the north-star size against 16.0 ms for the exact gather-dot of a
+    // four-unit block, 9.7 ms of two units); DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS: never / from one unit on.  The radius-3
+    // form where the radius-4 one and the radius-3 gather-sum are there.
+    const int min_units = (flags & DAU_FLAG_DENSE_WGRAD_NEVER) ? 1 << 30 : (flags & DAU_FLAG_DENSE_WGRAD_ALWAYS) ? 1 : 3;
+    for (int m = kWgradR4; m >= kWgradR3; --m) {
+        const WgradFns& fn = kWgrad[kMember[m].slot];
+        WgradConfig& cfg = bs.wgrad[kMember[m].slot];
+        const bool want = m == kWgradR4 ? whole_dot && bs.has[kBf16R4] && s.G >= min_units : bs.has[kWgradR4] && bs.has[kBf16R3];
+        bs.has[m] = want && fn.configure(s, blur_k, (flags & DAU_FLAG_IO_BF16) != 0, &cfg) && (double)fn.workspace_bytes(cfg) <= budget_bytes;
+    }
+    // two-limb f16 gather-dot: bucket 4, interpolation on, the whole batch in one pass; by default where the blocks of four
+    // units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with DAU_FLAG_DENSE_SPLIT_F16 whatever the unit
+    // count.  fp32, f16 and bf16 layers alike; a bf16 layer's error is staged in one limb (split_dot_configure).  The 2-D
+    // member for 2-D units; its line members (DAU_FLAG_SPLIT_DOT_LINE, single-dimension layers) are held where it would be.
+    const bool interp2d = (flags & DAU_FLAG_USE_INTERPOLATION) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL);
+    const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
+    for (int m = kDotLine4; m <= kSplitDot; ++m) {
+        const SplitDotFns& fn = kSplitDotFns[kMember[m].slot];
+        SplitDotConfig& cfg = bs.sdot[kMember[m].slot];
+        const bool want = kMember[m].line ? line_wanted(m, DAU_FLAG_SPLIT_DOT_LINE) : interp2d;
+        bs.has[m] = split_allowed && whole_dot && (split_forced || fill) && want && fn.configure(s, blur_k, act, &cfg) &&
+                    (double)fn.workspace_bytes(cfg) <= budget_bytes;
+    }
+    // Storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does (the
+    // staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ.  Likewise the layout: an NHWC
+    // plan is the NCHW plan of the same desc, its configs marked here, after they are made (addresses only).  And the input ReLU:
+    // the plan of the same desc, the configs that stage x (forward gather-sum, parameter gradients) marked.  (The bf16-product
+    // forms read neither mark: plan creation refuses them together with these flags.)
+    const int nhwc = (flags & DAU_FLAG_IO_NHWC) != 0, in_relu = (flags & DAU_FLAG_INPUT_RELU) != 0;
+    auto mark = [&](auto& cfg, bool stages_x) { cfg.nhwc = nhwc; cfg.in_relu = stages_x && in_relu; };
+    for (int dir : {kFwd, kDx}) {
+        mark(bs.tiled[dir], dir == kFwd);
+        for (DenseConfig* cfg : bs.dense) mark(cfg[dir], dir == kFwd);
+    }
+    mark(bs.tiled_dot, true);
+    for (SplitDotConfig& cfg : bs.sdot) mark(cfg, true);
+}
+
+// (d) what the plan's flags and algo need of the sets that were made; then the algorithms and the per-call selection
+int finish_plan(dau_conv_plan* p) {
+    const int flags = p->d.flags, algo = p->d.algo;
+    const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
+    const struct { int flag; const char* name; } tiled_only[] = {
+        {DAU_FLAG_IO_F16, "DAU_FLAG_IO_F16"}, {DAU_FLAG_IO_BF16, "DAU_FLAG_IO_BF16"}, {DAU_FLAG_IO_NHWC, "DAU_FLAG_IO_NHWC"},
+        {DAU_FLAG_INPUT_RELU, "DAU_FLAG_INPUT_RELU"}};
+    for (const auto& t : tiled_only)
+        if ((flags & t.flag) && (algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
+            return fail(DAU_INVALID_ARGUMENT, "%s needs the tiled kernels, which do not support this shape / algo", t.name);
+    if (algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
+    p->algo_fwd = (algo != DAU_ALGO_DIRECT && fwd_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
+    p->algo_bwd = (algo != DAU_ALGO_DIRECT && dot_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
+    // dynamic selection: tiled kernels, more than one bucket or a member that goes ahead of the sets, not switched off
+    // (DAU_FLAG_STATIC_BUCKET)
+    bool ahead = false;
+    for (int m = 0; m < kNumMembers; ++m) ahead = ahead || (kMember[m].ahead && p->sets[0].has[m]);
+    p->dynamic = (p->nsets > 1 || ahead) && !(flags & DAU_FLAG_STATIC_BUCKET) &&
+                 (p->algo_fwd == DAU_ALGO_TILED || p->algo_bwd == DAU_ALGO_TILED);
+    if (!p->dynamic || p->algo_fwd != DAU_ALGO_TILED) p->sets[0].ring = false;   // no per-call selection: the flag is inert
+    return DAU_OK;
 }
 
 }  // namespace
@@ -549,65 +757,8 @@ int dau_conv_filter_support(float sigma) { return 2 * (int)std::ceil(5.0f * sigm
 
 int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     if (!desc || !plan_out) return fail(DAU_INVALID_ARGUMENT, "null argument");
-    if (desc->struct_size != (int32_t)sizeof(dau_conv_desc))
-        return fail(DAU_INVALID_ARGUMENT, "dau_conv_desc.struct_size %d != %zu", desc->struct_size, sizeof(dau_conv_desc));
-    if (desc->batch < 1 || desc->in_channels < 1 || desc->out_channels < 1 || desc->units_per_channel < 1 ||
-        desc->height < 1 || desc->width < 1)
-        return fail(DAU_INVALID_ARGUMENT, "all of N,S,F,G,H,W must be >= 1");
-    if (desc->number_units_ignore < 0 || desc->number_units_ignore >= desc->units_per_channel)
-        return fail(DAU_INVALID_ARGUMENT, "number_units_ignore must be in [0, G)");
-    if (desc->max_kernel_size < 3 || desc->max_kernel_size % 2 == 0)
-        return fail(DAU_INVALID_ARGUMENT, "kernel_size must be odd and >= 3");
-    // offset bucket from the largest displacement the attrs allow (dau_conv_op.cpp:236-253)
-    const int half = desc->max_kernel_size / 2;
-    int bucket;
-    if (half <= 4) bucket = 4;
-    else if (half <= 8) bucket = 8;
-    else if (half <= 16) bucket = 16;
-    else if (half <= 18) bucket = 18;
-    else if (half <= 20) bucket = 20;
-    else if (half <= 24) bucket = 24;
-    else if (half <= 32) bucket = 32;
-    else
-        return fail(DAU_INVALID_ARGUMENT,
-                    "DAUConv: offsets larger than the 32 px the kernels stage (set max_kernel_size <= 65)");
-    if (!(desc->sigma_hint > 0.0f))  // DAU_CHECK(sigma > 0) base_dau_conv_layer.cpp:143
-        return fail(DAU_FAILED_PRECONDITION, "Must use sigma > 0 - initialize it with appropriate value");
-    const int blur_k = dau_conv_filter_support(desc->sigma_hint);
-    if (blur_k > kMaxBlurSupport)
-        return fail(DAU_INVALID_ARGUMENT, "sigma %.3f needs a %dx%d prefilter; at most %dx%d is supported", desc->sigma_hint,
-                    blur_k, blur_k, kMaxBlurSupport, kMaxBlurSupport);
-    if (desc->algo < DAU_ALGO_AUTO || desc->algo > DAU_ALGO_TILED) return fail(DAU_INVALID_ARGUMENT, "unknown algo");
-    const int flags = desc->flags;
-    const bool bf16 = (flags & DAU_FLAG_IO_BF16) != 0;
-    const bool f16 = (flags & DAU_FLAG_IO_F16) != 0;
-    if (f16 && (flags & (DAU_FLAG_IO_BF16 | DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_F16 excludes DAU_FLAG_IO_BF16, DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
-    if ((flags & DAU_FLAG_DENSE_BF16) && !bf16)
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 needs DAU_FLAG_IO_BF16 (it is the bf16 layer's gather-sum)");
-    if ((flags & DAU_FLAG_DENSE_SPLIT_F16) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_F16 excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
-    if ((flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_OUTLIERS excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
-    if ((flags & DAU_FLAG_DENSE_SPLIT_LINE) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL");
-    if ((flags & DAU_FLAG_DENSE_SPLIT_LINE) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
-    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_SINGLE_DIM_KERNEL");
-    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && !(flags & DAU_FLAG_USE_INTERPOLATION))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE needs DAU_FLAG_USE_INTERPOLATION");
-    if ((flags & DAU_FLAG_SPLIT_DOT_LINE) && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_NO_DENSE_SPLIT)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_NO_DENSE_SPLIT");
-    if ((flags & (DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)) &&
-        (!(flags & DAU_FLAG_DENSE_BF16) || (flags & DAU_FLAG_DENSE_WGRAD_NEVER && flags & DAU_FLAG_DENSE_WGRAD_ALWAYS)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS qualify DAU_FLAG_DENSE_BF16 and exclude each other");
-    const bool nhwc = (flags & DAU_FLAG_IO_NHWC) != 0;
-    if (nhwc && (flags & (DAU_FLAG_DENSE_BF16 | DAU_FLAG_DENSE_WGRAD_NEVER | DAU_FLAG_DENSE_WGRAD_ALWAYS)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16 and DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS");
-    const bool in_relu = (flags & DAU_FLAG_INPUT_RELU) != 0;
-    if (in_relu && (flags & DAU_FLAG_DENSE_BF16))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_INPUT_RELU excludes DAU_FLAG_DENSE_BF16 (the bf16-product forms have no input prologue)");
+    int bucket, blur_k;
+    if (int rc = validate_desc(desc, bucket, blur_k)) return rc;
 
     std::unique_ptr<dau_conv_plan> p(new (std::nothrow) dau_conv_plan());
     if (!p) return fail(DAU_INTERNAL, "out of host memory");
@@ -615,147 +766,20 @@ int dau_conv_plan_create(const dau_conv_desc* desc, dau_conv_plan** plan_out) {
     p->sh = Shape{desc->batch, desc->in_channels, desc->out_channels, desc->units_per_channel, desc->height, desc->width};
     p->bucket = bucket;
     p->blur_k = blur_k;
-    const bool ut = flags & DAU_FLAG_UNIT_TESTING;
+    const bool ut = desc->flags & DAU_FLAG_UNIT_TESTING;
     p->drop_col = ut ? edge_disabled(desc->width) : 0;
     p->drop_row = ut ? edge_disabled(desc->height) : 0;
 
-    const Shape& s = p->sh;
-    // storage format of the activations: an f16 plan configures every member exactly as the fp32 plan of the same desc does
-    // (the staged copies are fp32 in both), only the loads of x / dy and the stores of y / dx differ
-    // likewise the layout: an NHWC plan is the NCHW plan of the same desc, its configs marked after they are made (addresses only)
-    // and the input ReLU: the plan of the same desc, the configs that stage x (forward gather-sum, parameter gradients) marked
-    const int act = f16 ? kActF16 : bf16 ? kActBF16 : kActF32;
     const char* budget_env = getenv("DAU_WORKSPACE_BUDGET_GB");
     const double budget_bytes = (budget_env ? atof(budget_env) : 12.0) * 1e9;
-    const bool want_dense = (flags & DAU_FLAG_DENSE_BF16) && desc->algo != DAU_ALGO_DIRECT;
-    const bool split_forced = (flags & DAU_FLAG_DENSE_SPLIT_F16) != 0;
-    const bool split_allowed = !(flags & (DAU_FLAG_NO_DENSE_SPLIT | DAU_FLAG_DENSE_BF16)) && desc->algo != DAU_ALGO_DIRECT;
-    const int g_live = s.G - desc->number_units_ignore;
-    const long live_units = (long)s.S * s.F * g_live, ignored_units = (long)s.S * s.F * desc->number_units_ignore;
     for (int b : kBuckets) {
         if (b > bucket) break;
         BucketSet& bs = p->sets[p->nsets++];
         bs.bucket = b;
-        auto configure_gather = [&](int n) {
-            bs.has[kTiledGather] = tiled_gather_configure(n, s.S, s.F, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kFwd]) &&
-                                   tiled_gather_configure(n, s.F, s.S, s.G, s.H, s.W, b, blur_k, act, &bs.tiled[kDx]);
-            // the dense members, bucket 4 only; downwards, as the bf16 radius-3 member needs the radius-4 one
-            for (int m = kBf16R4; m >= kSplit2; --m) {
-                const int r = kRadius[m];
-                bool want = b == 4 && bs.has[kTiledGather];
-                if (m == kBf16R4) want = want && want_dense;
-                else if (m == kBf16R3) want = want && bs.has[kBf16R4];
-                else if (is_line(m)) continue;               // (below)
-                else want = want && split_allowed && (split_forced || (split_pays((2.0 * r + 1) * (2.0 * r + 1), s.S, s.F, g_live, s.H, s.W) &&
-                                                                       split_pays((2.0 * r + 1) * (2.0 * r + 1), s.F, s.S, g_live, s.H, s.W)));
-                DenseConfig* cfg = bs.dense[m - kSplit2];
-                bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
-                            kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
-            }
-            // the line members: bucket 4's set like the others; radius 8 where the plan's offsets reach it and radius 4 is held
-            for (int m = kLine4; m <= kLine8; ++m) {
-                const int r = kRadius[m];
-                // (DAU_FLAG_STATIC_BUCKET: no per-call selection, the flag is inert as the outliers flag is)
-                const bool want = b == 4 && bs.has[kTiledGather] && (flags & DAU_FLAG_DENSE_SPLIT_LINE) && split_allowed &&
-                                  !(flags & DAU_FLAG_STATIC_BUCKET) &&
-                                  (m == kLine4 || (bucket >= 8 && bs.has[kLine4])) &&
-                                  (split_forced || (split_pays(2.0 * r + 1, s.S, s.F, g_live, s.H, s.W) &&
-                                                    split_pays(2.0 * r + 1, s.F, s.S, g_live, s.H, s.W)));
-                DenseConfig* cfg = bs.dense[m - kSplit2];
-                bs.has[m] = want && kDense[m - kSplit2].configure(n, s.S, s.F, s.G, s.H, s.W, r, blur_k, act, &cfg[kFwd]) &&
-                            kDense[m - kSplit2].configure(n, s.F, s.S, s.G, s.H, s.W, r, blur_k, act, &cfg[kDx]);
-            }
-            // radius 3 + ring: where the radius-3 member is; its list holds the entries of ring_limit live units and of the ignored ones
-            // (the input-gradient table ignores no unit, and the count leaves them out)
-            for (int dir : {kFwd, kDx}) {
-                bs.tiled[dir].nhwc = nhwc;
-                for (int m = kSplit2; m <= kLine8; ++m) bs.dense[m - kSplit2][dir].nhwc = nhwc;
-            }
-            bs.tiled[kFwd].in_relu = in_relu;
-            for (int m = kSplit2; m <= kLine8; ++m) bs.dense[m - kSplit2][kFwd].in_relu = in_relu;
-            bs.ring = (flags & DAU_FLAG_DENSE_SPLIT_OUTLIERS) && bs.has[kSplit3];
-            if (bs.ring) {
-                bs.ring_limit = (unsigned)(live_units * DAU_TUNE_INT("DAU_RING_LIMIT_PERMILLE", kRingLimitPermille) / 1000);
-                for (int dir : {kFwd, kDx}) ring_configure(bs.dense[kSplit3 - kSplit2][dir], (long)bs.ring_limit + ignored_units, &bs.ringcfg[dir]);
-            }
-            return std::max(gather_bytes(bs, kFwd), gather_bytes(bs, kDx));
-        };
-        auto configure_dot = [&](int n) {
-            Shape sn = s; sn.N = n;
-            bs.has[kTiledDot] = tiled_dot_configure(sn, b, blur_k, act, desc->number_units_ignore, &bs.tiled_dot);
-            bs.tiled_dot.nhwc = nhwc;
-            bs.tiled_dot.in_relu = in_relu;
-            return dot_bytes(bs);
-        };
-        // slab candidates: the whole batch, then its even divisors (image pairs stay together), largest first
-        auto pick_slab = [&](auto&& configure) {
-            int chosen = s.N;
-            for (int n = s.N; n >= 2; --n) {
-                if (s.N % n || (n != s.N && (n & 1))) continue;
-                chosen = n;
-                if ((double)configure(n) <= budget_bytes) break;
-            }
-            configure(chosen);
-            return chosen;
-        };
-        bs.slab_gather = pick_slab(configure_gather);
-        bs.slab_dot = pick_slab(configure_dot);
-        const bool whole_dot = b == 4 && bs.has[kTiledDot] && bs.slab_dot == s.N;
-        {
-            // dense parameter gradients: the bf16-dense layer's bucket-4 set, whole batch in one slab, three or more units (its cost
-            // does not depend on the unit count: 15.3 ms at the north-star size against 16.0 ms for the exact gather-dot of a
-            // four-unit block, 9.7 ms of two units); DAU_FLAG_DENSE_WGRAD_NEVER / _ALWAYS: never / from one unit on.  The radius-3
-            // form where the radius-4 one and the radius-3 gather-sum are there.
-            const int min_units = (flags & DAU_FLAG_DENSE_WGRAD_NEVER) ? 1 << 30 : (flags & DAU_FLAG_DENSE_WGRAD_ALWAYS) ? 1 : 3;
-            for (int m = kWgradR4; m >= kWgradR3; --m) {
-                const WgradFns& fn = kWgrad[m - kWgradR3];
-                WgradConfig& cfg = bs.wgrad[m - kWgradR3];
-                const bool want = m == kWgradR4 ? whole_dot && bs.has[kBf16R4] && s.G >= min_units : bs.has[kWgradR4] && bs.has[kBf16R3];
-                bs.has[m] = want && fn.configure(s, blur_k, bf16, &cfg) && (double)fn.workspace_bytes(cfg) <= budget_bytes;
-            }
-        }
-        {
-            // two-limb f16 gather-dot: bucket 4, interpolation on, 2-D units, the whole batch in one pass; by default where the blocks
-            // of four units per channel pair are at least 3/4 full (G = 3, 4, 7, 8, ...), with DAU_FLAG_DENSE_SPLIT_F16 whatever the
-            // unit count.  fp32, f16 and bf16 layers alike; a bf16 layer's error is staged in one limb (split_dot_configure)
-            const bool interp2d = (flags & DAU_FLAG_USE_INTERPOLATION) && !(flags & DAU_FLAG_SINGLE_DIM_KERNEL);
-            const bool fill = 4 * s.G >= 3 * 4 * ((s.G + 3) / 4);
-            bs.has[kSplitDot] = split_allowed && whole_dot && interp2d && (split_forced || fill) &&
-                                split_dot_configure(s, blur_k, act, &bs.sdot) && (double)split_dot_workspace_bytes(bs.sdot) <= budget_bytes;
-            bs.sdot.nhwc = nhwc;
-            bs.sdot.in_relu = in_relu;
-            // its line members (DAU_FLAG_SPLIT_DOT_LINE, single-dimension layers): held where the 2-D member would be; radius 8 where
-            // the plan's offsets reach it and radius 4 is held (DAU_FLAG_STATIC_BUCKET: no per-call selection, the flag is inert)
-            for (int m = kDotLine4; m <= kDotLine8; ++m) {
-                SplitDotConfig& cfg = bs.sdline[m - kDotLine4];
-                const DotLineFns& fn = kDotLine[m - kDotLine4];
-                const bool want = (flags & DAU_FLAG_SPLIT_DOT_LINE) && split_allowed && whole_dot && !(flags & DAU_FLAG_STATIC_BUCKET) &&
-                                  (split_forced || fill) && (m == kDotLine4 || (bucket >= 8 && bs.has[kDotLine4]));
-                bs.has[m] = want && fn.configure(s, blur_k, act, &cfg) && (double)fn.workspace_bytes(cfg) <= budget_bytes;
-                cfg.nhwc = nhwc;
-                cfg.in_relu = in_relu;
-            }
-        }
+        configure_set(*p, budget_bytes, bs);
     }
-    const bool fwd_ok = p->top().has[kTiledGather], dot_ok = p->top().has[kTiledDot];
-    if ((bf16 || f16) && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
-        return fail(DAU_INVALID_ARGUMENT, "%s needs the tiled kernels, which do not support this shape / algo",
-                    f16 ? "DAU_FLAG_IO_F16" : "DAU_FLAG_IO_BF16");
-    if (nhwc && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_IO_NHWC needs the tiled kernels, which do not support this shape / algo");
-    if (in_relu && (desc->algo == DAU_ALGO_DIRECT || !(fwd_ok && dot_ok)))
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_INPUT_RELU needs the tiled kernels, which do not support this shape / algo");
-    if (desc->algo == DAU_ALGO_TILED && !(fwd_ok && dot_ok)) return fail(DAU_INVALID_ARGUMENT, "DAU_ALGO_TILED does not support this shape");
-    p->algo_fwd = (desc->algo != DAU_ALGO_DIRECT && fwd_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
-    p->algo_bwd = (desc->algo != DAU_ALGO_DIRECT && dot_ok) ? DAU_ALGO_TILED : DAU_ALGO_DIRECT;
-    // dynamic selection: tiled kernels, more than one bucket or a member that goes ahead of the sets, not switched off
-    // (DAU_FLAG_STATIC_BUCKET).  The pinned status mirror needs a device; without one (header-only checks on a CPU box) the plan
-    // simply has no hint.
-    bool ahead = false;
-    for (int m = 0; m < kNumMembers; ++m) ahead = ahead || (goes_ahead(m) && p->sets[0].has[m]);
-    p->dynamic = (p->nsets > 1 || ahead) && !(flags & DAU_FLAG_STATIC_BUCKET) &&
-                 (p->algo_fwd == DAU_ALGO_TILED || p->algo_bwd == DAU_ALGO_TILED);
-    if (!p->dynamic || p->algo_fwd != DAU_ALGO_TILED) p->sets[0].ring = false;   // no per-call selection: the flag is inert
+    if (int rc = finish_plan(p.get())) return rc;
+    // The pinned status mirror needs a device; without one (header-only checks on a CPU box) the plan simply has no hint.
     void* hs = nullptr;
     // portable + mapped: a plan may be used on any device, and every device's prepare_units_kernel writes the mirror
     if (hipHostMalloc(&hs, sizeof(HostStatus), hipHostMallocPortable | hipHostMallocMapped) == hipSuccess && hs) {
@@ -831,16 +855,12 @@ int dau_conv_plan_get_info(const dau_conv_plan* plan, dau_conv_plan_info* info) 
     info->gather_fblock = tiled_fwd ? top.tiled[kFwd].fblock : 0;
     info->gather_variant = tiled_fwd ? top.tiled[kFwd].variant : -1;
     info->dense_bf16_radius3 = dense_reachable && plan->dynamic && s0[kBf16R3] ? (s0[kWgradR3] ? 2 : 1) : 0;
-    info->gather_dense_split = 0;
-    if (plan->dynamic && tiled_fwd)
-        for (int m = kSplit2; m <= kSplit4; ++m)
-            if (s0[m]) info->gather_dense_split |= 1 << kRadius[m];
-    if (plan->sets[0].ring) info->gather_dense_split |= 1 << 5;
-    if (plan->dynamic && tiled_fwd && s0[kLine4]) info->gather_dense_split |= 1 << 6;
-    if (plan->dynamic && tiled_fwd && s0[kLine8]) info->gather_dense_split |= 1 << 7;
-    const bool tiled_bwd = plan->algo_bwd == DAU_ALGO_TILED;
-    if (plan->dynamic && tiled_bwd && s0[kDotLine4]) info->gather_dense_split |= 1 << 8;
-    if (plan->dynamic && tiled_bwd && s0[kDotLine8]) info->gather_dense_split |= 1 << 9;
+    // the members a call can reach that report themselves: held, per-call selection on, their pass on the tiled kernels
+    info->gather_dense_split = plan->sets[0].ring ? 1 << kRingInfoBit : 0;
+    const bool tiled_pass[2] = {tiled_fwd, plan->algo_bwd == DAU_ALGO_TILED};   // [PassKind]
+    for (int m = 0; m < kNumMembers; ++m)
+        if (kMember[m].info_bit >= 0 && s0[m] && plan->dynamic && tiled_pass[kMember[m].kind])
+            info->gather_dense_split |= 1 << kMember[m].info_bit;
     return DAU_OK;
 }
 
@@ -850,8 +870,9 @@ int dau_conv_split_dot_geometry(const dau_conv_plan* plan, int32_t* region_width
     for (int i = 0; i < plan->nsets && !rw; ++i) {
         const BucketSet& bs = plan->sets[i];
         if (!bs.has[kSplitDot]) continue;
-        rw = bs.sdot.RW;
-        split_dot_strip(bs.sdot, &items, &steps);
+        const SplitDotConfig& cfg = bs.sdot[kMember[kSplitDot].slot];
+        rw = cfg.RW;
+        split_dot_strip(cfg, &items, &steps);
     }
     if (region_width) *region_width = rw;
     if (strip_items) *strip_items = items;
@@ -892,45 +913,41 @@ int dau_conv_forward(const dau_conv_plan* p, void* stream, const float* x, const
     return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, Epilogue{});
 }
 
-int dau_conv_epilogue_supported(const dau_conv_plan* p, int epilogue) {
+namespace {
+// whether the plan's forward pass takes a fused `what` (an epilogue, a residual); bf16_has: what the bf16-product forms have of it
+int fused_store_supported(const dau_conv_plan* p, int epilogue, const char* what, const char* bf16_has) {
     if (!p) return fail(DAU_INVALID_ARGUMENT, "null argument");
     if (epilogue & ~(DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU))
         return fail(DAU_INVALID_ARGUMENT, "unknown epilogue bits 0x%x (DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU)", epilogue);
     if (p->algo_fwd != DAU_ALGO_TILED)
-        return fail(DAU_INVALID_ARGUMENT, "the direct kernels take no fused epilogue (this plan's forward pass runs on them)");
+        return fail(DAU_INVALID_ARGUMENT, "the direct kernels take no fused %s (this plan's forward pass runs on them)", what);
     if (p->d.flags & DAU_FLAG_DENSE_BF16)
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 plans take no fused epilogue (the bf16-product forms have none)");
+        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 plans take no fused %s (the bf16-product forms have %s)", what, bf16_has);
     return DAU_OK;
+}
+}  // namespace
+
+int dau_conv_epilogue_supported(const dau_conv_plan* p, int epilogue) { return fused_store_supported(p, epilogue, "epilogue", "none"); }
+
+int dau_conv_forward_residual(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
+                              const float* mu2, const float* sigma, const float* bias, const float* residual, int epilogue,
+                              float* y, void* workspace, size_t workspace_bytes) {
+    Epilogue epi;
+    if (residual || epilogue) {
+        // the residual is no epilogue bit: it is taken where a bias is (dau_conv_epilogue_supported(p, DAU_EPILOGUE_BIAS)), also with epilogue == 0
+        if (int rc = residual ? fused_store_supported(p, epilogue, "residual", "no epilogue") : dau_conv_epilogue_supported(p, epilogue)) return rc;
+        if ((epilogue & DAU_EPILOGUE_BIAS) && !bias) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_BIAS without a bias");
+        epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
+        epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
+        epi.residual = residual;
+    }
+    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
 }
 
 int dau_conv_forward_epilogue(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
                               const float* mu2, const float* sigma, const float* bias, int epilogue, float* y,
                               void* workspace, size_t workspace_bytes) {
-    if (epilogue == 0) return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, Epilogue{});
-    if (int rc = dau_conv_epilogue_supported(p, epilogue)) return rc;
-    if ((epilogue & DAU_EPILOGUE_BIAS) && !bias) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_BIAS without a bias");
-    Epilogue epi;
-    epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
-    epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
-    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
-}
-
-int dau_conv_forward_residual(const dau_conv_plan* p, void* stream, const float* x, const float* w, const float* mu1,
-                              const float* mu2, const float* sigma, const float* bias, const float* residual, int epilogue,
-                              float* y, void* workspace, size_t workspace_bytes) {
-    if (!residual) return dau_conv_forward_epilogue(p, stream, x, w, mu1, mu2, sigma, bias, epilogue, y, workspace, workspace_bytes);
-    // the residual is no epilogue bit: it is taken where a bias is (dau_conv_epilogue_supported(p, DAU_EPILOGUE_BIAS)), also with epilogue == 0
-    if (!p || (epilogue & ~(DAU_EPILOGUE_BIAS | DAU_EPILOGUE_RELU))) return dau_conv_epilogue_supported(p, epilogue);
-    if (p->algo_fwd != DAU_ALGO_TILED)
-        return fail(DAU_INVALID_ARGUMENT, "the direct kernels take no fused residual (this plan's forward pass runs on them)");
-    if (p->d.flags & DAU_FLAG_DENSE_BF16)
-        return fail(DAU_INVALID_ARGUMENT, "DAU_FLAG_DENSE_BF16 plans take no fused residual (the bf16-product forms have no epilogue)");
-    if ((epilogue & DAU_EPILOGUE_BIAS) && !bias) return fail(DAU_INVALID_ARGUMENT, "DAU_EPILOGUE_BIAS without a bias");
-    Epilogue epi;
-    epi.bias = (epilogue & DAU_EPILOGUE_BIAS) ? bias : nullptr;
-    epi.relu = (epilogue & DAU_EPILOGUE_RELU) != 0;
-    epi.residual = residual;
-    return forward_pass(p, stream, x, w, mu1, mu2, sigma, y, workspace, workspace_bytes, epi);
+    return dau_conv_forward_residual(p, stream, x, w, mu1, mu2, sigma, bias, nullptr, epilogue, y, workspace, workspace_bytes);
 }
 
 int dau_conv_epilogue_backward(const dau_conv_plan* p, void* stream, const float* dy, const float* y, int epilogue, float* dz,
@@ -962,9 +979,9 @@ namespace {
 int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const float* dy, const float* mu1,
                    const float* mu2, const BwdWs& ws, float* r4, int kinds, const float* w = nullptr) {
     const Shape& s = p->sh;
-    // (the gather-dot's line members: their condition is counted on THIS table, into Status::pad2[0] for the report and into
-    // line[0], which the guards read; line[0] goes back to zero behind the pass, for the count of the input-gradient table;
-    // a NaN / Inf weight counts where the caller has the weights)
+    // (the gather-dot's line members: their condition is counted on THIS table, into Status::dot_off_line_units for the report and
+    // into off_line_units, which the guards read; off_line_units goes back to zero behind the pass, for the count of the
+    // input-gradient table; a NaN / Inf weight counts where the caller has the weights)
     const bool dot_line = p->algo_bwd == DAU_ALGO_TILED && p->dynamic && p->sets[0].has[kDotLine4];
     launch_prepare_units(st, dot_line ? w : nullptr, mu1, mu2, s, p->d.number_units_ignore, p->d.flags, p->bucket, false, ws.table_bare,
                          ws.status, p->host_status, -1, dot_line ? ws.status : nullptr, true);
@@ -976,19 +993,15 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
             const BucketSet& bs = *cand[ci].set;
             const Guard& g = cand[ci].guard;
             const int m = cand[ci].member;
-            if (m == kDotLine4 || m == kDotLine8) {                            // the whole batch in one pass
-                const DotLineFns& fn = kDotLine[m - kDotLine4];
-                fn.prepare(st, bs.sdline[m - kDotLine4], x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
+            const int slot = kMember[m].slot;
+            if (kMember[m].family == kFamSplitDot) {                           // the whole batch in one pass
+                const SplitDotFns& fn = kSplitDotFns[slot];
+                fn.prepare(st, bs.sdot[slot], x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
                 ProfScope prof(p, 2, st);
-                fn.run(st, bs.sdline[m - kDotLine4], ws.table_bare, r4, ws.tiled_dot, g);
-            } else if (m == kSplitDot) {                                       // likewise
-                split_dot_prepare(st, bs.sdot, x, dy, ws.filters, p->drop_col, p->drop_row, ws.tiled_dot, g);
+                fn.run(st, bs.sdot[slot], ws.table_bare, r4, ws.tiled_dot, g);
+            } else if (kMember[m].family == kFamWgrad) {                       // likewise
                 ProfScope prof(p, 2, st);
-                split_dot_run(st, bs.sdot, ws.table_bare, r4, ws.tiled_dot, g);
-            } else if (m == kWgradR3 || m == kWgradR4) {                       // likewise
-                ProfScope prof(p, 2, st);
-                kWgrad[m - kWgradR3].run(st, bs.wgrad[m - kWgradR3], x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4,
-                                         ws.tiled_dot, g, kinds);
+                kWgrad[slot].run(st, bs.wgrad[slot], x, dy, ws.filters, ws.table_bare, p->drop_col, p->drop_row, r4, ws.tiled_dot, g, kinds);
             } else {
                 for (int n0 = 0; n0 < s.N; n0 += bs.slab_dot) {            // the sums of the slabs add up in r4
                     tiled_dot_prepare(st, bs.tiled_dot, slab_ptr(x, (size_t)n0 * s.S * s.H * s.W, p->esize()),
@@ -999,7 +1012,7 @@ int run_param_sums(const dau_conv_plan* p, hipStream_t st, const float* x, const
                 }
             }
         }
-        if (dot_line) launch_zero_words(st, &ws.status->line[0], sizeof(unsigned));
+        if (dot_line) launch_zero_words(st, &ws.status->off_line_units, sizeof(unsigned));
     } else {
         launch_blur_direct(st, x, (long)s.N * s.S, s.H, s.W, ws.filters + 1 * kFilterPlane, kNumK, p->blur_k, ws.xk4);
         ProfScope prof(p, 2, st);
@@ -1085,11 +1098,19 @@ int dau_conv_finalize_param_grads(const dau_conv_plan* p, void* stream, const fl
     return DAU_OK;
 }
 
-int dau_conv_check_status(const dau_conv_plan* p, void* stream, const void* workspace, float* max_abs_mu_out) {
+namespace {
+// the status block of the last call on `workspace`, once the stream has run it
+int read_status(const dau_conv_plan* p, void* stream, const void* workspace, Status* h) {
     if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
-    Status h;
     DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
+    DAU_HIP(hipMemcpy(h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
+    return DAU_OK;
+}
+}  // namespace
+
+int dau_conv_check_status(const dau_conv_plan* p, void* stream, const void* workspace, float* max_abs_mu_out) {
+    Status h;
+    if (int rc = read_status(p, stream, workspace, &h)) return rc;
     float mx;
     std::memcpy(&mx, &h.max_abs_mu_bits, sizeof(float));
     if (max_abs_mu_out) *max_abs_mu_out = mx;
@@ -1099,34 +1120,28 @@ int dau_conv_check_status(const dau_conv_plan* p, void* stream, const void* work
 
 int dau_conv_gather_outlier_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* outlier_units,
                                    int32_t* ring_taken) {
-    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
     Status h;
-    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
-    if (outlier_units) *outlier_units = (int32_t)(h.pad[1] & ~kRingTakenBit);
-    if (ring_taken) *ring_taken = (h.pad[1] & kRingTakenBit) ? 1 : 0;
+    if (int rc = read_status(p, stream, workspace, &h)) return rc;
+    if (outlier_units) *outlier_units = (int32_t)(h.outlier_units & ~kRingTakenBit);
+    if (ring_taken) *ring_taken = (h.outlier_units & kRingTakenBit) ? 1 : 0;
     return DAU_OK;
 }
 
 int dau_conv_gather_line_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* off_line_units,
                                 int32_t* line_radius_taken) {
-    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
     Status h;
-    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
-    if (off_line_units) *off_line_units = (int32_t)h.line[0];
-    if (line_radius_taken) *line_radius_taken = (int32_t)h.line[1];
+    if (int rc = read_status(p, stream, workspace, &h)) return rc;
+    if (off_line_units) *off_line_units = (int32_t)h.off_line_units;
+    if (line_radius_taken) *line_radius_taken = (int32_t)h.line_radius;
     return DAU_OK;
 }
 
 int dau_conv_dot_line_status(const dau_conv_plan* p, void* stream, const void* workspace, int32_t* off_line_units,
                              int32_t* line_radius_taken) {
-    if (!p || !workspace) return fail(DAU_INVALID_ARGUMENT, "null argument");
     Status h;
-    DAU_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    DAU_HIP(hipMemcpy(&h, workspace, sizeof(Status), hipMemcpyDeviceToHost));
-    if (off_line_units) *off_line_units = (int32_t)h.pad2[0];
-    if (line_radius_taken) *line_radius_taken = (int32_t)h.pad2[1];
+    if (int rc = read_status(p, stream, workspace, &h)) return rc;
+    if (off_line_units) *off_line_units = (int32_t)h.dot_off_line_units;
+    if (line_radius_taken) *line_radius_taken = (int32_t)h.dot_line_radius;
     return DAU_OK;
 }
 

@@ -194,7 +194,7 @@ void split_dot_run(hipStream_t st, const SplitDotConfig& cfg, const UnitRef* tab
 // The line forms (-DDAU_SD_1D: namespaces d4 and d8; DAU_FLAG_SPLIT_DOT_LINE): the same source compiled with a horizontal radius
 // of 4 / 8 and a vertical radius of 0, for calls whose units all lie on the row of their pixel -- the parameter gradients of
 // single-dimension layers.  The kind mu2 is computed and discarded.  The dy maxima kernel of a form whose guard has passed writes
-// the form's radius to Status::pad2[1].
+// the form's radius to Status::dot_line_radius.
 #define DAU_DECLARE_SPLIT_DOT_LINE(NS)                                                                                         \
     namespace NS {                                                                                                            \
     bool split_dot_configure(const Shape& sh, int blur_k, int act, SplitDotConfig* cfg);                                      \

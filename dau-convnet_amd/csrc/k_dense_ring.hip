@@ -154,7 +154,7 @@ __global__ void __launch_bounds__(kPassThreads) ring_pass_kernel(const RingPassA
     extern __shared__ __attribute__((aligned(16))) float tile[];   // [16 channels][kTR][kTP]
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     if (!guard_pass(a.guard)) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.status->pad[1], kRingTakenBit);
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&a.status->outlier_units, kRingTakenBit);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int t = blockIdx.x;

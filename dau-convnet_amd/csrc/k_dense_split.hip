@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(256) split_scales_kernel(const unsigned* __res
             out->max_w_bits = m; out->sw = s; out->inv_sw = 1.0f / s;
             // a line form's guard has passed: this member does the pass's work (dau_conv_gather_line_status reports it).  The one
             // write a kernel makes through its guard (dau_common.hpp, Guard): one thread, the same value in every slab of a pass
-            if constexpr (kLine) { if (guard.status) const_cast<Status*>(guard.status)->line[1] = (unsigned)kDR; }
+            if constexpr (kLine) { if (guard.status) const_cast<Status*>(guard.status)->line_radius = (unsigned)kDR; }
         }
     }
 }

@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(256) sd_absmax_x_kernel(const float* __restric
 // of this file makes through its guard (dau_common.hpp, Guard): one thread of the pass's dy maxima kernel.
 __device__ __forceinline__ void sd_mark_taken(const Guard& guard) {
     if constexpr (kSdLine) {
-        if (guard.status && blockIdx.x == 0 && threadIdx.x == 0) const_cast<Status*>(guard.status)->pad2[1] = (unsigned)kSdRX;
+        if (guard.status && blockIdx.x == 0 && threadIdx.x == 0) const_cast<Status*>(guard.status)->dot_line_radius = (unsigned)kSdRX;
     }
 }
 

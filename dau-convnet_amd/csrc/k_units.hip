@@ -28,8 +28,8 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
                                      UnitRef* __restrict__ table, Status* __restrict__ status,
                                      HostStatus* __restrict__ host_status, int count_ignore, Status* line_status, int line_dot) {
     const long units = (long)S * G * F;
-    unsigned int local_max = 0, local_nan = 0, local_out = 0;   // local_out: live units beyond +-3 (Status.pad[1])
-    unsigned int local_off = 0;                                 // units of this table off the line (Status.line[0])
+    unsigned int local_max = 0, local_nan = 0, local_out = 0;   // local_out: live units beyond +-3 (Status::outlier_units)
+    unsigned int local_off = 0;                                 // units of this table off the line (Status::off_line_units)
     // the loop index is the DESTINATION slot, so that the 24-byte table entries are written in order; in the transposed
     // case the three parameter reads are the strided side instead (12 B per unit, served from L2)
     for (long dst = blockIdx.x * (long)blockDim.x + threadIdx.x; dst < units; dst += (long)gridDim.x * blockDim.x) {
@@ -65,8 +65,8 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
     if (line_status) {
         for (int m = 32; m >= 1; m >>= 1) local_off += (unsigned int)__shfl_xor((int)local_off, m);
         if ((threadIdx.x & 63) == 0 && local_off) {
-            atomicAdd(&line_status->line[0], local_off);
-            if (line_dot) atomicAdd(&line_status->pad2[0], local_off);     // the parameter-gradient pass: the count it reports
+            atomicAdd(&line_status->off_line_units, local_off);
+            if (line_dot) atomicAdd(&line_status->dot_off_line_units, local_off);     // the parameter-gradient pass: the count it reports
         }
     }
     if (status) {
@@ -84,12 +84,12 @@ __global__ void prepare_units_kernel(const float* __restrict__ w, const float* _
             for (int i = 1; i < nw; ++i) { local_max = max(local_max, smax[i]); local_nan |= snan[i]; local_out += sout[i]; }
             atomicMax(&status->max_abs_mu_bits, local_max);
             if (local_nan) atomicOr(&status->nan_seen, 1u);
-            if (local_out) atomicAdd(&status->pad[1], local_out);
+            if (local_out) atomicAdd(&status->outlier_units, local_out);
             if (host_status) {
                 // the workgroup that finishes last mirrors the result into pinned host memory (read without a sync by
-                // dau_conv_last_status and as the next call's offset-bucket hint); pad[0] counts finished workgroups
+                // dau_conv_last_status and as the next call's offset-bucket hint); the ticket counts finished workgroups
                 __threadfence();
-                if (atomicAdd(&status->pad[0], 1u) == gridDim.x - 1) {
+                if (atomicAdd(&status->ticket, 1u) == gridDim.x - 1) {
                     const unsigned mx = atomicMax(&status->max_abs_mu_bits, 0u), nn = atomicOr(&status->nan_seen, 0u);
                     volatile unsigned* h = reinterpret_cast<volatile unsigned*>(host_status);
                     h[0] = mx; h[1] = nn; h[2] = 1u;   // [2]: a completed call has reported

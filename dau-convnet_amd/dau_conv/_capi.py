@@ -334,6 +334,15 @@ class Plan(object):
             raise FailedPreconditionError("DAUConv: %s() before any forward / backward call of this plan that kept its workspace" % what)
         return call.ws
 
+    def _status_pair(self, what, query):
+        """Sync; the pair of int32 that the library's `query` reads from the status block of the last call, for the method `what`."""
+        a, b = ctypes.c_int32(), ctypes.c_int32()
+        ws = self._status_ws(what)
+        dev = ws.device
+        with torch.cuda.device(dev):
+            _check(getattr(lib, query)(self._h, _stream(dev), _ptr(ws), ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def epilogue_supported(self, epilogue=EPILOGUE_BIAS | EPILOGUE_RELU):
         """True if forward() takes this epilogue (EPILOGUE_* bits); raises InvalidArgumentError naming the reason otherwise: a plan
         whose forward pass runs on the direct kernels, a FLAG_DENSE_BF16 plan, unknown bits."""
@@ -487,12 +496,8 @@ class Plan(object):
     def outlier_status(self):
         """Sync; -> (outlier_units, ring_taken) of the last call: the live units with max(|mu1|,|mu2|) > 3, and whether one of its
         gather-sum passes ran as the radius-3 GEMM plus the ring pass (FLAG_DENSE_SPLIT_OUTLIERS) rather than another member."""
-        units, taken = ctypes.c_int32(), ctypes.c_int32()
-        ws = self._status_ws("outlier_status")
-        dev = ws.device
-        with torch.cuda.device(dev):
-            _check(lib.dau_conv_gather_outlier_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
-        return units.value, bool(taken.value)
+        units, taken = self._status_pair("outlier_status", "dau_conv_gather_outlier_status")
+        return units, bool(taken)
 
     def split_dot_geometry(self):
         """-> (region_width, strip_items, strip_k_steps) of the two-limb f16 parameter-gradient kernel: the K steps of a full item,
@@ -506,23 +511,13 @@ class Plan(object):
         """Sync; -> (off_line_units, line_radius_taken) of the last call: the units of its gather-sum table that do not lie on the row
         of their pixel (counted by plans that hold a line member, FLAG_DENSE_SPLIT_LINE), and 4 or 8 if its gather-sum pass ran as the
         line member of that radius, 0 if another member did the work."""
-        units, taken = ctypes.c_int32(), ctypes.c_int32()
-        ws = self._status_ws("line_status")
-        dev = ws.device
-        with torch.cuda.device(dev):
-            _check(lib.dau_conv_gather_line_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
-        return units.value, taken.value
+        return self._status_pair("line_status", "dau_conv_gather_line_status")
 
     def dot_line_status(self):
         """Sync; -> (off_line_units, line_radius_taken) of the last backward call: the units of its bare parameter-gradient table that
         do not lie on the row of their pixel (counted by plans that hold a line member of the gather-dot, FLAG_SPLIT_DOT_LINE), and
         4 or 8 if its parameter gradients ran as the line member of that radius, 0 if another member did the work."""
-        units, taken = ctypes.c_int32(), ctypes.c_int32()
-        ws = self._status_ws("dot_line_status")
-        dev = ws.device
-        with torch.cuda.device(dev):
-            _check(lib.dau_conv_dot_line_status(self._h, _stream(dev), _ptr(ws), ctypes.byref(units), ctypes.byref(taken)))
-        return units.value, taken.value
+        return self._status_pair("dot_line_status", "dau_conv_dot_line_status")
 
     def last_status(self):
         """No sync: max(|mu|) seen by the most recent COMPLETED call of this plan (None before any has completed);
