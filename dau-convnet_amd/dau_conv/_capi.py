@@ -288,14 +288,19 @@ class Plan(object):
         _check(lib.dau_conv_workspace_bytes(self._h, which, ctypes.byref(n)))
         return n.value
 
+    def _ws_bytes(self, which):
+        """workspace_bytes(which), asked of the library once per plan and pass."""
+        need = self._ws.get(which)
+        if need is None:
+            need = self._ws[which] = self.workspace_bytes(which)
+        return need
+
     def _workspace(self, which, device):
         """The scratch memory of one pass (called with `device` current).  Under stream capture: a tensor of exactly the pass's size
         from the capturing allocator, which the caller drops when the call returns -- the graph's private pool hands memory out again
         in capture order, which is the order of the replay, so the pool holds the largest workspace of a model, not the sum; the
         shared workspace is neither read, grown nor replaced, and no pass reads what another left in its workspace."""
-        need = self._ws.get(which)
-        if need is None:
-            need = self._ws[which] = self.workspace_bytes(which)
+        need = self._ws_bytes(which)
         captured = torch.cuda.is_current_stream_capturing()
         key = (device.index, torch.cuda.current_stream(device).cuda_stream)
         self._tls.pending = (key, captured, False)       # (the calling thread's: the GIL is released during the library call)
@@ -360,21 +365,32 @@ class Plan(object):
         except InvalidArgumentError as e:
             raise InvalidArgumentError("no fused residual: %s" % e)
 
+    def _req_call(self, x, dy=None, **params):
+        """The checks every pass makes of its tensors, in this order: the input, the output gradient if the pass takes one, then the
+        parameters as named -- each [1,S,G,F] float32."""
+        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
+        if dy is not None:
+            _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype, self._io_format)
+        for name, t in params.items():
+            _req(t, name, (1, self.S, self.G, self.F))
+
+    def _new_grads(self, need_mask, dev):
+        """(dw, dmu1, dmu2, dsigma): a fresh [1,S,G,F] float32 tensor for each one need_mask asks for, None for the others."""
+        return tuple(torch.empty((1, self.S, self.G, self.F), dtype=torch.float32, device=dev) if need_mask & bit else None
+                     for bit in (NEED_DW, NEED_DMU1, NEED_DMU2, NEED_DSIGMA))
+
     def forward(self, x, w, mu1, mu2, sigma, bias=None, relu=False, residual=None):
         """y, or with bias ([F] float32) / residual / relu the fused epilogue y = act((sum + bias[f]) + residual[n,f,h,w]): fp32 adds
         in that order and a clamp on the value the plain call stores, before the store's one rounding; y keeps the plan's dtype and
         layout.  residual: a tensor like y (shape, dtype, layout) that is only read; it must not share memory with anything the call
         writes.  A residual without bias or relu is a plain fused add."""
-        pshape = (1, self.S, self.G, self.F)
         if residual is not None:             # (first: a plan that takes none is refused whatever the tensors are)
             self._residual_supported()
             yshape = (self.N, self.F, self.H, self.W)
             if tuple(residual.shape) != yshape:      # (the shape before the device: a refusal that names the shape wherever the tensor lives)
                 raise InvalidArgumentError("residual has shape %s, expected %s" % (tuple(residual.shape), yshape))
             _req(residual, "residual", yshape, self.io_dtype, self._io_format)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
-        for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
-            _req(t, n, pshape)
+        self._req_call(x, weights=w, mu1=mu1, mu2=mu2, sigma=sigma)
         if bias is not None:
             _req(bias, "bias", (self.F,))
         dev = _same_device(x, w, mu1, mu2, sigma, bias, residual)
@@ -420,28 +436,18 @@ class Plan(object):
                 dz = torch.empty(shape, dtype=self.io_dtype, device=dev, memory_format=self._io_format)
             dbias = torch.empty((self.F,), dtype=torch.float32, device=dev) if need_dbias else None
             # a small workspace of its own: the shared one still holds the status block of the last forward / backward call
-            need = self._ws.get(PASS_EPILOGUE_BACKWARD)
-            if need is None:
-                need = self._ws[PASS_EPILOGUE_BACKWARD] = self.workspace_bytes(PASS_EPILOGUE_BACKWARD)
+            need = self._ws_bytes(PASS_EPILOGUE_BACKWARD)
             ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev) if need_dbias else None
             _check(lib.dau_conv_epilogue_backward(self._h, _stream(dev), _ptr(dy), _ptr(y) if relu else None, epilogue,
                                                   _ptr(dz) if relu else None, _ptr(dbias), _ptr(ws), need if need_dbias else 0))
         return (dz if relu else None), dbias
 
     def backward(self, x, dy, w, mu1, mu2, sigma, need_mask=NEED_ALL):
-        pshape = (1, self.S, self.G, self.F)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
-        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype, self._io_format)
-        for t, n in ((w, "weights"), (mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
-            _req(t, n, pshape)
+        self._req_call(x, dy, weights=w, mu1=mu1, mu2=mu2, sigma=sigma)
         dev = _same_device(x, dy, w, mu1, mu2, sigma)
-        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             dx = torch.empty(x.shape, dtype=self.io_dtype, device=dev, memory_format=self._io_format) if need_mask & NEED_DX else None
-            dw = new(pshape) if need_mask & NEED_DW else None
-            dmu1 = new(pshape) if need_mask & NEED_DMU1 else None
-            dmu2 = new(pshape) if need_mask & NEED_DMU2 else None
-            dsigma = new(pshape) if need_mask & NEED_DSIGMA else None
+            dw, dmu1, dmu2, dsigma = self._new_grads(need_mask, dev)
             ws = self._workspace(PASS_BACKWARD, dev)
             _check(lib.dau_conv_backward(self._h, _stream(dev), _ptr(x), _ptr(dy), _ptr(w), _ptr(mu1), _ptr(mu2), _ptr(sigma),
                                          _ptr(dx), _ptr(dw), _ptr(dmu1), _ptr(dmu2), _ptr(dsigma), _ptr(ws), ws.numel(),
@@ -452,11 +458,7 @@ class Plan(object):
     def backward_param_sums(self, x, dy, mu1, mu2, sigma, out=None):
         """Raw parameter-gradient sums [4, S, G, F] (kinds w, mu1, mu2, sigma) of this batch: linear in the batch, so a
         data-parallel caller all-reduces THIS buffer and only then calls finalize_param_grads()."""
-        pshape = (1, self.S, self.G, self.F)
-        _req(x, "input", (self.N, self.S, self.H, self.W), self.io_dtype, self._io_format)
-        _req(dy, "grad", (self.N, self.F, self.H, self.W), self.io_dtype, self._io_format)
-        for t, n in ((mu1, "mu1"), (mu2, "mu2"), (sigma, "sigma")):
-            _req(t, n, pshape)
+        self._req_call(x, dy, mu1=mu1, mu2=mu2, sigma=sigma)
         dev = _same_device(x, dy, mu1, mu2, sigma, out)
         with torch.cuda.device(dev):
             if out is None:
@@ -470,16 +472,11 @@ class Plan(object):
 
     def finalize_param_grads(self, sums, w, need_mask=NEED_DW | NEED_DMU1 | NEED_DMU2 | NEED_DSIGMA):
         """(dw, dmu1, dmu2, dsigma) from (all-reduced) sums: dmu *= w * lr, dsigma *= w, ignored units -> 0, NaN dmu -> 0."""
-        pshape = (1, self.S, self.G, self.F)
         _req(sums, "sums", (4, self.S, self.G, self.F))
-        _req(w, "weights", pshape)
+        _req(w, "weights", (1, self.S, self.G, self.F))
         dev = _same_device(sums, w)
-        new = lambda: torch.empty(pshape, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            dw = new() if need_mask & NEED_DW else None
-            dmu1 = new() if need_mask & NEED_DMU1 else None
-            dmu2 = new() if need_mask & NEED_DMU2 else None
-            dsigma = new() if need_mask & NEED_DSIGMA else None
+            dw, dmu1, dmu2, dsigma = self._new_grads(need_mask, dev)
             _check(lib.dau_conv_finalize_param_grads(self._h, _stream(dev), _ptr(sums), _ptr(w), _ptr(dw), _ptr(dmu1),
                                                      _ptr(dmu2), _ptr(dsigma), int(need_mask)))
         return dw, dmu1, dmu2, dsigma

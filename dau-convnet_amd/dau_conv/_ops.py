@@ -33,10 +33,8 @@ Two of today's eager rules depend on the plan, and the implementations bring the
     the output and the input gradient are converted to channels_last."""
 import collections
 import weakref
-from typing import Optional
 
 import torch
-from torch import Tensor
 
 from . import _capi
 from . import dau_conv as _impl
@@ -51,19 +49,52 @@ _CHECK = {"async": "async", True: "on", False: "off"}
 _UNCHECK = {"async": "async", "on": True, "off": False}
 
 
+def _untri(channels_last):
+    if channels_last not in _UNTRI:
+        raise _capi.InvalidArgumentError("channels_last must be -1 (by dtype), 0 or 1")
+    return _UNTRI[channels_last]
+
+
+# One trailing argument of the ops.  type: its schema type; encode: the argument from a _settings() dict; decode: the _settings()
+# keywords from the argument
+_Setting = collections.namedtuple("_Setting", "name type encode decode")
+
+
+def _as_is(name, type):
+    return _Setting(name, type, lambda st: st[name], lambda v: {name: v})
+
+
+# The ops' settings, in schema order: all that encode_settings, _run_settings, the schemas' tails and _N_ARGS know of them
+_SETTINGS = (
+    _as_is("number_units_ignore", "SymInt"), _as_is("kernel_size", "SymInt"), _as_is("unit_testing", "bool"),
+    _as_is("mu_learning_rate_factor", "float"), _as_is("single_dim_kernel", "bool"), _as_is("forbid_positive_dim1", "bool"),
+    _as_is("use_interpolation", "bool"),
+    # (the two packed pairs: the schema has no argument of its own for dense_line_grads, nor for dense_line below)
+    _Setting("algo", "SymInt", lambda st: st["algo"] + (_LINE_GRADS if st["dense_line_grads"] else 0),
+             lambda v: dict(algo=v & ~_LINE_GRADS, dense_line_grads=bool(v & _LINE_GRADS))),
+    _as_is("dense_bf16", "bool"),
+    _Setting("dense_split", "SymInt", lambda st: _SPLIT[(st["dense_split"], st["dense_line"])],
+             lambda v: dict(zip(("dense_split", "dense_line"), _UNSPLIT[v]))),
+    _as_is("dense_outliers", "bool"),
+    _Setting("channels_last", "SymInt", lambda st: _TRI[st["channels_last"]], lambda v: dict(channels_last=_untri(v))),
+    _Setting("check_offsets", "str", lambda st: _CHECK[st["check_offsets"]], lambda v: dict(check_offsets=_UNCHECK[v])))
+_NAMES = tuple(s.name for s in _SETTINGS)
+_SCHEMA_TAIL = ", ".join("%s %s" % (s.type, s.name) for s in _SETTINGS)
+
+
 def encode_settings(st):
     """The op's trailing arguments from a _settings() dict, in schema order."""
-    return (st["number_units_ignore"], st["kernel_size"], st["unit_testing"], st["mu_learning_rate_factor"], st["single_dim_kernel"],
-            st["forbid_positive_dim1"], st["use_interpolation"], st["algo"] + (_LINE_GRADS if st.get("dense_line_grads") else 0), st["dense_bf16"],
-            _SPLIT[(st["dense_split"], bool(st.get("dense_line")))],
-            st["dense_outliers"], _TRI[st["channels_last"]], _CHECK[st["check_offsets"]])
+    return tuple(s.encode(st) for s in _SETTINGS)
 
 
 def _layout_settings(dense_bf16, channels_last):
     """All of the settings that _wants_nhwc reads."""
-    if channels_last not in _UNTRI:
-        raise _capi.InvalidArgumentError("channels_last must be -1 (by dtype), 0 or 1")
-    return dict(dense_bf16=bool(dense_bf16), channels_last=_UNTRI[channels_last])
+    return dict(dense_bf16=bool(dense_bf16), channels_last=_untri(channels_last))
+
+
+def _tail_layout(tail):
+    """_layout_settings of an op's trailing arguments: all a shape function reads of them."""
+    return _layout_settings(tail[_NAMES.index("dense_bf16")], tail[_NAMES.index("channels_last")])
 
 
 # ----------------------------------------------------------------------------------------------
@@ -122,20 +153,17 @@ def _NO_TENSOR():
     return None
 
 
-def _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
-                  forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last, check_offsets):
-    """The _settings() dict of a real call."""
-    if dense_split not in _UNSPLIT or check_offsets not in _UNCHECK:
+def _run_settings(w, sigma, input_relu, *tail):
+    """The _settings() dict of a real call, from the op's trailing arguments."""
+    arg = dict(zip(_NAMES, tail, strict=True))
+    if arg["dense_split"] not in _UNSPLIT or arg["check_offsets"] not in _UNCHECK:
         raise _capi.InvalidArgumentError("dense_split must be -1, 0, 1, 2 or 3 and check_offsets \"async\", \"on\" or \"off\"")
-    st = _impl._settings(sigma, number_units_ignore=number_units_ignore, num_output=w.shape[-1], kernel_size=kernel_size,
-                         unit_testing=unit_testing, mu_learning_rate_factor=mu_learning_rate_factor, single_dim_kernel=single_dim_kernel,
-                         forbid_positive_dim1=forbid_positive_dim1, use_interpolation=use_interpolation,
-                         sigma_hint=_sigma_hint(sigma, like=("like", sigma.device.index, tuple(w.shape), kernel_size, number_units_ignore,
-                                                             single_dim_kernel, forbid_positive_dim1, use_interpolation)),
-                         check_offsets=_UNCHECK[check_offsets], algo=algo & ~_LINE_GRADS, dense_line_grads=bool(algo & _LINE_GRADS), dense_split=_UNSPLIT[dense_split][0],
-                         dense_line=_UNSPLIT[dense_split][1], dense_outliers=dense_outliers, **_layout_settings(dense_bf16, channels_last))
-    if input_relu:
-        st["input_relu"] = True
+    attrs = dict(num_output=w.shape[-1], sigma_hint=_sigma_hint(sigma, like=("like", sigma.device.index, tuple(w.shape)) + tuple(
+        arg[n] for n in ("kernel_size", "number_units_ignore", "single_dim_kernel", "forbid_positive_dim1", "use_interpolation"))))
+    for s in _SETTINGS:
+        attrs.update(s.decode(arg[s.name]))
+    st = _impl._settings(sigma, **attrs)
+    st["input_relu"] = bool(input_relu)
     return st
 
 
@@ -172,15 +200,11 @@ def _check_shapes(x, w, residual=None):
 # ----------------------------------------------------------------------------------------------
 # dau_conv::conv
 # ----------------------------------------------------------------------------------------------
-@torch.library.custom_op("dau_conv::conv", mutates_args=())
-def conv(x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, bias: Optional[Tensor], residual: Optional[Tensor],
-         relu: bool, input_relu: bool, number_units_ignore: int, kernel_size: int, unit_testing: bool,
-         mu_learning_rate_factor: float, single_dim_kernel: bool, forbid_positive_dim1: bool, use_interpolation: bool, algo: int,
-         dense_bf16: bool, dense_split: int, dense_outliers: bool, channels_last: int, check_offsets: str) -> Tensor:
+@torch.library.custom_op("dau_conv::conv", mutates_args=(), schema="(Tensor x, Tensor w, Tensor mu1, Tensor mu2, Tensor sigma, "
+                         "Tensor? bias, Tensor? residual, bool relu, bool input_relu, " + _SCHEMA_TAIL + ") -> Tensor")
+def conv(x, w, mu1, mu2, sigma, bias, residual, relu, input_relu, *tail):
     _check_shapes(x, w, residual)
-    st = _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
-                       forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last,
-                       check_offsets)
+    st = _run_settings(w, sigma, input_relu, *tail)
     nhwc = _impl._wants_nhwc(x, st)
     w, mu1, mu2 = (_impl._c(_impl._f32(t)) for t in (w, mu1, mu2))
     sigma = _tiled(sigma, w)
@@ -205,29 +229,23 @@ def conv(x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, bias: Op
 
 
 @conv.register_fake
-def _conv_fake(x, w, mu1, mu2, sigma, bias, residual, relu, input_relu, number_units_ignore, kernel_size, unit_testing,
-               mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split,
-               dense_outliers, channels_last, check_offsets):
+def _conv_fake(x, w, mu1, mu2, sigma, bias, residual, relu, input_relu, *tail):
     _check_shapes(x, w, residual)
-    nhwc = _impl._wants_nhwc(x, _layout_settings(dense_bf16, channels_last))
+    nhwc = _impl._wants_nhwc(x, _tail_layout(tail))
     return _empty_act(x, (x.shape[0], w.shape[-1], x.shape[2], x.shape[3]), nhwc)
 
 
 # ----------------------------------------------------------------------------------------------
 # dau_conv::conv_backward
 # ----------------------------------------------------------------------------------------------
-@torch.library.custom_op("dau_conv::conv_backward", mutates_args=())
-def conv_backward(grad: Tensor, x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, sigma: Tensor, y: Optional[Tensor], relu: bool,
-                  input_relu: bool, need_mask: int, need_dbias: bool, number_units_ignore: int, kernel_size: int, unit_testing: bool,
-                  mu_learning_rate_factor: float, single_dim_kernel: bool, forbid_positive_dim1: bool, use_interpolation: bool,
-                  algo: int, dense_bf16: bool, dense_split: int, dense_outliers: bool, channels_last: int,
-                  check_offsets: str) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+@torch.library.custom_op("dau_conv::conv_backward", mutates_args=(), schema="(Tensor grad, Tensor x, Tensor w, Tensor mu1, Tensor mu2, "
+                         "Tensor sigma, Tensor? y, bool relu, bool input_relu, SymInt need_mask, bool need_dbias, " + _SCHEMA_TAIL +
+                         ") -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+def conv_backward(grad, x, w, mu1, mu2, sigma, y, relu, input_relu, need_mask, need_dbias, *tail):
     _check_shapes(x, w)
     if relu and y is None:
         raise _capi.InvalidArgumentError("dau_conv::conv_backward: relu needs the forward's output")
-    st = _run_settings(w, sigma, input_relu, number_units_ignore, kernel_size, unit_testing, mu_learning_rate_factor, single_dim_kernel,
-                       forbid_positive_dim1, use_interpolation, algo, dense_bf16, dense_split, dense_outliers, channels_last,
-                       check_offsets)
+    st = _run_settings(w, sigma, input_relu, *tail)
     nhwc = _impl._wants_nhwc(x, st)
     w, mu1, mu2 = (_impl._c(_impl._f32(t)) for t in (w, mu1, mu2))
     sigma = _tiled(sigma, w)
@@ -258,11 +276,9 @@ def conv_backward(grad: Tensor, x: Tensor, w: Tensor, mu1: Tensor, mu2: Tensor, 
 
 
 @conv_backward.register_fake
-def _conv_backward_fake(grad, x, w, mu1, mu2, sigma, y, relu, input_relu, need_mask, need_dbias, number_units_ignore, kernel_size,
-                        unit_testing, mu_learning_rate_factor, single_dim_kernel, forbid_positive_dim1, use_interpolation, algo,
-                        dense_bf16, dense_split, dense_outliers, channels_last, check_offsets):
+def _conv_backward_fake(grad, x, w, mu1, mu2, sigma, y, relu, input_relu, need_mask, need_dbias, *tail):
     _check_shapes(x, w)
-    nhwc = _impl._wants_nhwc(x, _layout_settings(dense_bf16, channels_last))
+    nhwc = _impl._wants_nhwc(x, _tail_layout(tail))
     f32 = lambda shape: torch.empty(shape, dtype=torch.float32, device=x.device)
     need = int(need_mask) & _capi.NEED_ALL
     pshape = (1, w.shape[1], w.shape[2], w.shape[3])
@@ -275,7 +291,7 @@ def _conv_backward_fake(grad, x, w, mu1, mu2, sigma, y, relu, input_relu, need_m
 # ----------------------------------------------------------------------------------------------
 # autograd of dau_conv::conv
 # ----------------------------------------------------------------------------------------------
-_N_ARGS = 22            # x, w, mu1, mu2, sigma, bias, residual, relu, input_relu and the thirteen settings
+_N_ARGS = 9 + len(_SETTINGS)         # x, w, mu1, mu2, sigma, bias, residual, relu, input_relu and the settings
 
 
 def _setup_context(ctx, inputs, output):

@@ -88,8 +88,6 @@ def is_channels_last(t):
 # dx -> channels_last -- at the north-star layer: 23.66 against 25.66 ms (float32), 23.03 against 24.46 (float16), 21.18 against
 # 22.53 (bfloat16), the rounds of one box within 0.1 ms of each other.  channels_last=True runs the NHWC plan whatever this table says.
 _NHWC_BY_DEFAULT = {torch.float32: True, torch.float16: True, torch.bfloat16: True}
-# plan keys whose NHWC form the library refused (shapes that fall back to the direct kernels): asked once, then today's path
-_NHWC_REFUSED = set()
 
 
 def _wants_nhwc(x, settings):
@@ -100,27 +98,6 @@ def _wants_nhwc(x, settings):
     if x.dtype == torch.bfloat16 and settings["dense_bf16"]:
         return False                     # DAU_FLAG_IO_NHWC excludes DAU_FLAG_DENSE_BF16: that layer converts, as before
     return True if cl is True else _NHWC_BY_DEFAULT.get(x.dtype, False)
-
-
-# (shape, dtype, attrs) whose FLAG_INPUT_RELU plan the library refused (shapes that fall back to the direct kernels): asked once
-_INPUT_RELU_REFUSED = set()
-
-
-def _get_plan(x, w, settings, nhwc=False):
-    """The cached plan of this call.  nhwc: the FLAG_IO_NHWC plan if the library builds one for the shape, else the NCHW plan
-    (Plan.io_layout tells which came back).  settings["input_relu"]: the FLAG_INPUT_RELU plan where the library builds one, else
-    the plan without the flag (Plan.input_relu tells which came back; the caller then applies the ReLU itself)."""
-    if settings.get("input_relu") and not (x.dtype == torch.bfloat16 and settings["dense_bf16"]):   # (the flag excludes DAU_FLAG_DENSE_BF16)
-        asked = (tuple(x.shape), tuple(w.shape), x.dtype, x.device.index, settings["kernel_size"], settings["number_units_ignore"],
-                 settings["algo"], _capi.filter_support(settings["sigma_hint"]))
-        if asked not in _INPUT_RELU_REFUSED:
-            try:
-                return _get_plan_with(x, w, settings, nhwc, _capi.FLAG_INPUT_RELU)
-            except _capi.InvalidArgumentError as e:
-                if "DAU_FLAG_INPUT_RELU" not in str(e):
-                    raise
-                _INPUT_RELU_REFUSED.add(asked)   # no tiled kernels for this shape / algo
-    return _get_plan_with(x, w, settings, nhwc, 0)
 
 
 def _check_activations(activation, input_activation):
@@ -149,11 +126,9 @@ def _residual_fusable(residual, x, w):
     return residual.dtype == x.dtype and tuple(residual.shape) == (x.shape[0], w.shape[-1]) + tuple(x.shape[2:])
 
 
-def _get_plan_with(x, w, settings, nhwc, extra_flags):
-    N, S, H, W = x.shape
-    _, _, G, F = w.shape
-    _check_weights(x, w, settings)
-    flags = extra_flags
+def _plan_flags(dtype, settings):
+    """The DAU_FLAG_* bits of a call's plan, from its activation dtype and its settings; the optional flags are _get_plan's."""
+    flags = 0
     if settings["use_interpolation"]:
         flags |= _capi.FLAG_USE_INTERPOLATION
     if settings["unit_testing"]:
@@ -162,13 +137,13 @@ def _get_plan_with(x, w, settings, nhwc, extra_flags):
         flags |= _capi.FLAG_SINGLE_DIM_KERNEL
     if settings["forbid_positive_dim1"]:
         flags |= _capi.FLAG_FORBID_POSITIVE_DIM1
-    if x.dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         flags |= _capi.FLAG_IO_BF16      # bfloat16 activations (input, output and their gradients); fp32 parameters
         if settings["dense_bf16"]:
             # calls whose offsets lie within +-4: the gather-sum passes (and, from three units on, the parameter gradients)
             # as densified bf16 MFMA GEMMs
             flags |= _capi.FLAG_DENSE_BF16
-    elif x.dtype == torch.float16:
+    elif dtype == torch.float16:
         # float16 activations (autocast, .half()): the members and the arithmetic of the fp32 plan, 16-bit loads and stores;
         # fp32 parameters.  dense_bf16 does not apply, as for fp32 input
         flags |= _capi.FLAG_IO_F16
@@ -182,49 +157,75 @@ def _get_plan_with(x, w, settings, nhwc, extra_flags):
         flags |= _capi.FLAG_DENSE_SPLIT_OUTLIERS
     # opt-in, single-dimension layers: calls whose units lie on a line run the 1 x 9 / 1 x 17 two-limb GEMM (_settings has checked the
     # pairs: single-dimension, not dense_split=False, not dense_bf16)
-    if settings.get("dense_line"):
+    if settings["dense_line"]:
         flags |= _capi.FLAG_DENSE_SPLIT_LINE
     # likewise their parameter gradients: the line members of the two-limb gather-dot (the same pairs checked)
-    if settings.get("dense_line_grads"):
+    if settings["dense_line_grads"]:
         flags |= _capi.FLAG_SPLIT_DOT_LINE
-    make_key = lambda fl: (N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], fl, settings["algo"],
-                           _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"]), x.device.index)
-    make_plan = lambda fl: _capi.Plan(N, S, F, G, H, W, max_kernel_size=settings["kernel_size"],
-                                      number_units_ignore=settings["number_units_ignore"], flags=fl, algo=settings["algo"],
-                                      sigma_hint=settings["sigma_hint"], mu_learning_rate_factor=settings["mu_learning_rate_factor"],
-                                      device=x.device)
-    plan = None
-    if nhwc and make_key(flags | _capi.FLAG_IO_NHWC) not in _NHWC_REFUSED:
-        key = make_key(flags | _capi.FLAG_IO_NHWC)
-        plan = _PLANS.get(key)
-        if plan is not None:
-            _PLANS.move_to_end(key)
-            return plan
-        try:
-            plan = make_plan(flags | _capi.FLAG_IO_NHWC)
-        except _capi.InvalidArgumentError as e:
-            if "DAU_FLAG_IO_NHWC" not in str(e):
-                raise
-            _NHWC_REFUSED.add(key)       # no tiled kernels for this shape / algo: the NCHW plan below, as without the feature
-    if plan is None:
-        key = make_key(flags)
-        plan = _PLANS.get(key)
-        if plan is not None:
-            _PLANS.move_to_end(key)
-            return plan
-        plan = make_plan(flags)
-    if settings["algo"] == _capi.ALGO_AUTO and _capi.ALGO_DIRECT in (plan.info["algo_forward"], plan.info["algo_backward"]):
+    return flags
+
+
+_PlanKey = collections.namedtuple("_PlanKey", "N S F G H W kernel_size number_units_ignore flags algo support mu_learning_rate_factor device")
+
+
+def _cached(key, make):
+    """The plan cached under this _PlanKey, now the most recently used; else make(), stored under it."""
+    plan = _PLANS.get(key)
+    if plan is not None:
+        _PLANS.move_to_end(key)
+        return plan
+    plan = make()
+    if key.algo == _capi.ALGO_AUTO and _capi.ALGO_DIRECT in (plan.info["algo_forward"], plan.info["algo_backward"]):
         # the LDS-tiled kernels refused this shape (e.g. more than 16 units per channel pair under a kernel larger than 17, a
         # prefilter window or error row larger than the LDS): correct, but orders of magnitude slower -- say so once per plan
         which = [n for n, a in (("forward / input gradient", plan.info["algo_forward"]), ("parameter gradients", plan.info["algo_backward"]))
                  if a == _capi.ALGO_DIRECT]
         warnings.warn("DAUConv: N=%d C=%d->%d %dx%d, %d units, max_kernel_size=%d: the %s run on the plain one-thread-per-output "
                       "kernels (the tiled MFMA kernels do not support this shape); expect them to be orders of magnitude slower"
-                      % (N, S, F, H, W, G, settings["kernel_size"], " and the ".join(which)), RuntimeWarning, stacklevel=3)
+                      % (key.N, key.S, key.F, key.H, key.W, key.G, key.kernel_size, " and the ".join(which)), RuntimeWarning,
+                      stacklevel=3)         # (the caller of _get_plan, which is the one caller of this)
     _PLANS[key] = plan
     plan._cache_key = key
     _evict()
     return plan
+
+
+# Flags a call would like and the library may refuse for its shape (shapes that fall back to the direct kernels), outermost first, and
+# the name by which its refusal tells which one it refuses.  _REFUSED: the plan keys that were refused so -- the flags outside the
+# refused one decided, those inside it not yet set: each is asked once, then the call runs without the flag
+_OPTIONAL_FLAGS = ((_capi.FLAG_INPUT_RELU, "DAU_FLAG_INPUT_RELU"), (_capi.FLAG_IO_NHWC, "DAU_FLAG_IO_NHWC"))
+_REFUSED = set()
+
+
+def _get_plan(x, w, settings, nhwc=False):
+    """The cached plan of this call.  nhwc: the FLAG_IO_NHWC plan if the library builds one for the shape, else the NCHW plan
+    (Plan.io_layout tells which came back).  settings["input_relu"]: the FLAG_INPUT_RELU plan where the library builds one, else
+    the plan without the flag (Plan.input_relu tells which came back; the caller then applies the ReLU itself)."""
+    N, S, H, W = x.shape
+    _, _, G, F = w.shape
+    _check_weights(x, w, settings)
+    base = _plan_flags(x.dtype, settings)
+    support, lr = _capi.filter_support(settings["sigma_hint"]), float(settings["mu_learning_rate_factor"])
+    make_key = lambda fl: _PlanKey(N, S, F, G, H, W, settings["kernel_size"], settings["number_units_ignore"], fl, settings["algo"],
+                                   support, lr, x.device.index)
+    # (FLAG_INPUT_RELU excludes DAU_FLAG_DENSE_BF16: that layer applies the ReLU itself, unasked)
+    wanted = (settings["input_relu"] and not base & _capi.FLAG_DENSE_BF16, nhwc)
+    while True:
+        flags, asked = base, []
+        for (flag, name), want in zip(_OPTIONAL_FLAGS, wanted):
+            if want and make_key(flags | flag) not in _REFUSED:
+                flags |= flag
+                asked.append((name, make_key(flags)))        # (what to remember if the library names this flag)
+        try:
+            return _cached(make_key(flags), lambda: _capi.Plan(
+                N, S, F, G, H, W, max_kernel_size=settings["kernel_size"], number_units_ignore=settings["number_units_ignore"],
+                flags=flags, algo=settings["algo"], sigma_hint=settings["sigma_hint"],
+                mu_learning_rate_factor=settings["mu_learning_rate_factor"], device=x.device))
+        except _capi.InvalidArgumentError as e:
+            refused = [key for name, key in asked if name in str(e)]
+            if not refused:
+                raise
+            _REFUSED.add(refused[-1])        # (the innermost flag named.)  No tiled kernels for this shape / algo: without it, as before
 
 
 def _check_before(plan, mode):
@@ -261,6 +262,18 @@ def check_pending_offsets(device=None):
                 "captured with: capture again" % (worst, worst, planned, planned, plan.N, plan.S, plan.F, plan.H, plan.W))
 
 
+def _check_line_options(single_dim, dense_split, dense_bf16, dense_line, dense_line_grads):
+    """The rules of the two opt-in line options, for the layer's constructor and for _settings() alike."""
+    for option, on, flag in (("dense_line_grads", dense_line_grads, "DAU_FLAG_SPLIT_DOT_LINE"),
+                             ("dense_line", dense_line, "DAU_FLAG_DENSE_SPLIT_LINE")):
+        if on and not single_dim:
+            raise ValueError("%s=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)" % option)
+        if on and dense_split is not None and not dense_split:
+            raise ValueError("%s=True excludes dense_split=False" % option)
+        if on and dense_bf16:
+            raise ValueError("%s=True excludes dense_bf16=True (%s excludes DAU_FLAG_DENSE_BF16)" % (option, flag))
+
+
 def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, num_output=64, kernel_size=9, pad=4,
               stride=1, unit_normalization=True, square_unit_normalization=False, mean_iteration_step=1,
               sigma_iteration_step=1, component_border_bound=1.0, sigma_lower_bound=0.3, merge_iteration_step=0,
@@ -268,18 +281,9 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
               forbid_positive_dim1=False, use_interpolation=True, sigma_hint=None, check_offsets="async",
               algo=_capi.ALGO_AUTO, dense_bf16=False, dense_split=None, process_group=None, grad_reduce="mean", name=None,
               dense_outliers=False, channels_last=None, dense_line=False, dense_line_grads=False):
-    if dense_line_grads and not single_dim_kernel:
-        raise ValueError("dense_line_grads=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
-    if dense_line_grads and dense_split is not None and not dense_split:
-        raise ValueError("dense_line_grads=True excludes dense_split=False")
-    if dense_line_grads and dense_bf16:
-        raise ValueError("dense_line_grads=True excludes dense_bf16=True (DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16)")
-    if dense_line and not single_dim_kernel:
-        raise ValueError("dense_line=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
-    if dense_line and dense_split is not None and not dense_split:
-        raise ValueError("dense_line=True excludes dense_split=False")
-    if dense_line and dense_bf16:
-        raise ValueError("dense_line=True excludes dense_bf16=True (DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16)")
+    """The attrs of a call, checked and normalised: every key is always there (input_relu=False: the caller sets it for a call with
+    the ReLU in front)."""
+    _check_line_options(single_dim_kernel, dense_split, dense_bf16, dense_line, dense_line_grads)
     if not unit_normalization or square_unit_normalization:
         raise _capi.InvalidArgumentError("only unit_normalization=True, square_unit_normalization=False is implemented")
     if sigma_hint is None:
@@ -298,7 +302,7 @@ def _settings(sigma, number_units_x=2, number_units_y=2, number_units_ignore=0, 
                 dense_split=(None if dense_split is None else bool(dense_split)), dense_outliers=bool(dense_outliers),
                 process_group=process_group, grad_reduce=grad_reduce,
                 channels_last=(None if channels_last is None else bool(channels_last)), dense_line=bool(dense_line),
-                dense_line_grads=bool(dense_line_grads))
+                dense_line_grads=bool(dense_line_grads), input_relu=False)
 
 
 def _c(t):
@@ -496,8 +500,7 @@ def dau_conv(input, weights, mu1, mu2, sigma, bias=None, activation=None, residu
         return residual_in_torch()
     weights, mu1, mu2, sigma = _f32(weights), _f32(mu1), _f32(mu2), _f32(sigma)
     st = _settings(sigma, **attrs)
-    if input_activation == "relu":
-        st["input_relu"] = True          # part of the plan key (_get_plan): the plan takes the raw input
+    st["input_relu"] = input_activation == "relu"        # part of the plan key (_get_plan): the plan takes the raw input
     if bias is None and activation is None and residual is None:
         return _DAUConvFunction.apply(input, weights, mu1, mu2, sigma, st)
     _check_bias(bias, weights)
@@ -624,6 +627,18 @@ def _run_init(init, shape):
 # ----------------------------------------------------------------------------------------------
 # layer
 # ----------------------------------------------------------------------------------------------
+# The engine options: what this binding adds to the reference's layer arguments.  Each goes by one name as a DAUConv2d argument and
+# attribute, a _DAUConvolution2d argument and attribute, and an attr of dau_conv()
+_ENGINE_OPTIONS = ("check_offsets", "algo", "dense_bf16", "dense_split", "dense_outliers", "dense_line", "dense_line_grads",
+                   "channels_last", "process_group", "grad_reduce")
+# (attr of dau_conv(), the _DAUConvolution2d attribute it comes from)
+_OP_ATTRS = (("num_output", "num_output"), ("number_units_ignore", "num_dau_units_ignore"), ("kernel_size", "max_kernel_size"),
+             ("pad", "_pad"), ("component_border_bound", "dau_unit_border_bound"), ("sigma_lower_bound", "dau_unit_sigma_bound"),
+             ("mu_learning_rate_factor", "mu_learning_rate_factor"), ("single_dim_kernel", "dau_unit_single_dim"),
+             ("forbid_positive_dim1", "dau_aggregation_forbid_positive_dim1"), ("use_interpolation", "dau_mu_interpolation"),
+             ("unit_testing", "unit_testing"), ("name", "name")) + tuple((option, option) for option in _ENGINE_OPTIONS)
+
+
 class _DAUConvolution2d(object):
     """Helper that clips the offsets and calls the op (dau_conv.py:113-219)."""
 
@@ -676,18 +691,9 @@ class _DAUConvolution2d(object):
         m = self.mean_max_allowed_offset
         mu1 = torch.clamp(mu1, min=-m, max=m)
         mu2 = torch.clamp(mu2, min=-m, max=m)
+        attrs = {attr: getattr(self, name) for attr, name in _OP_ATTRS}      # (read now: an attribute may be assigned after build())
         return dau_conv(inp, w, mu1, mu2, sigma, bias=bias, activation=activation, residual=residual, input_activation=input_activation,
-                        num_output=self.num_output, number_units_x=self.dau_units[0], number_units_y=self.dau_units[1],
-                        number_units_ignore=self.num_dau_units_ignore, kernel_size=self.max_kernel_size,
-                        pad=self._pad, component_border_bound=self.dau_unit_border_bound,
-                        sigma_lower_bound=self.dau_unit_sigma_bound, mu_learning_rate_factor=self.mu_learning_rate_factor,
-                        single_dim_kernel=self.dau_unit_single_dim,
-                        forbid_positive_dim1=self.dau_aggregation_forbid_positive_dim1,
-                        use_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing,
-                        sigma_hint=sigma_hint, check_offsets=self.check_offsets, algo=self.algo,
-                        dense_bf16=self.dense_bf16, dense_split=self.dense_split, dense_outliers=self.dense_outliers,
-                        process_group=self.process_group, grad_reduce=self.grad_reduce, name=self.name,
-                        channels_last=self.channels_last, dense_line=self.dense_line, dense_line_grads=self.dense_line_grads)
+                        number_units_x=self.dau_units[0], number_units_y=self.dau_units[1], sigma_hint=sigma_hint, **attrs)
 
 
 class DAUConv2d(nn.Module):
@@ -698,33 +704,47 @@ class DAUConv2d(nn.Module):
     previous call's on-device result from pinned host memory before each call, no stall, errors surface one call late
     (`dau_conv.check_pending_offsets()` flushes); True: wait for every call and raise at once, as the reference does
     (a call under stream capture cannot wait: there True behaves as "async");
-    False: never read the result back.  Graph capture (`torch.cuda.graph`, `make_graphed_callables`, the cudagraph trees of
+    False: never read the result back.
+
+    Graph capture (`torch.cuda.graph`, `make_graphed_callables`, the cudagraph trees of
     torch.compile): run the layer once before capturing; a captured call reads no sigma on the host, takes its workspace from the
     graph's pool and pins its plan (`dau_conv.release_captured_plans()`); the plan and its prefilter support are frozen in the graph,
     and `dau_conv.check_pending_offsets()` also raises when a replay's sigma needed more taps than the plan holds; a `process_group=`
-    layer cannot be captured.  `dense_split` (None: the library's choice, True: always, False: never): calls whose
+    layer cannot be captured.
+
+    `dense_split` (None: the library's choice, True: always, False: never): calls whose
     offsets lie within +-2 / +-3 / +-4 run their two gather-sum passes as a densified GEMM on the f16 matrix cores with both
     operands split into two binary16 limbs -- fp32 accuracy (the exact kernels' parity bar), about 1.7x faster at four units per
     channel pair; by default a plan holds the radii that pay for its unit count.  Every image is scaled on its own, so an output
-    image (and its input gradient) depends only on that image and the parameters, never on its batch-mates.  `dense_outliers=True` (opt-in): a call whose
+    image (and its input gradient) depends only on that image and the parameters, never on its batch-mates.
+
+    `dense_outliers=True` (opt-in): a call whose
     offsets reach beyond +-3 (up to +-4) in few units -- a trained layer's offsets drift to the +-3.99 clip of kernel 9 -- keeps the
     radius-3 GEMM and gathers those units' outer taps in a sparse pass of its own, instead of moving the whole pass to the 9 x 9
-    member; same accuracy, no effect on calls within +-3 or with many such units.  `dense_line=True` (opt-in, single-dimension layers:
+    member; same accuracy, no effect on calls within +-3 or with many such units.
+
+    `dense_line=True` (opt-in, single-dimension layers:
     DAUConv1d, or `dau_unit_single_dim=True`; ValueError elsewhere and together with `dense_split=False` or `dense_bf16=True`): a call whose units all
     lie on the row of their pixel (mu2 == 0) runs its two gather-sum passes as the two-limb GEMM over ONE row of taps -- 1 x 9 for
     offsets within +-4, 1 x 17 within +-8 -- instead of the 9 x 9 kernel or the exact gather; same accuracy; a call with a unit off
-    the line runs what it runs without the argument, bit for bit (DAU_FLAG_DENSE_SPLIT_LINE).  `dense_line_grads=True` (opt-in, the same layers and
+    the line runs what it runs without the argument, bit for bit (DAU_FLAG_DENSE_SPLIT_LINE).
+
+    `dense_line_grads=True` (opt-in, the same layers and
     the same ValueErrors): such a call runs its parameter gradients as the line member of the two-limb gather-dot, horizontal radius 4 or 8, in
-    place of the exact fp32 gather-dot; fp32 accuracy, independent of `dense_line` (DAU_FLAG_SPLIT_DOT_LINE).  `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
+    place of the exact fp32 gather-dot; fp32 accuracy, independent of `dense_line` (DAU_FLAG_SPLIT_DOT_LINE).
+
+    `dense_bf16=True` (bfloat16 inputs only): calls whose offsets lie within +-4 run
     their forward and input-gradient passes as a densified bf16 matrix-core GEMM (DAU_FLAG_DENSE_BF16: taps and blurred
     activations rounded to bf16, fp32 sums) and, from three units per channel on, their
     parameter gradients as dense cross-correlations on the same cores -- the whole step about 2x faster than the exact
     path at six units, at the bf16 tolerance.
+
     Activations may be float32, bfloat16 or float16; the output has the input's dtype.  float16 input (torch.autocast("cuda"),
     GradScaler training, `model.half()`) runs the kernels and the fp32 arithmetic of a float32 layer with 16-bit loads and stores
     (DAU_FLAG_IO_F16); the layer casts nothing under autocast.  Parameters of any floating dtype are used as float32 and get
     their gradients in their own dtype.  The bias is added after the op with ordinary type promotion: a float16 (or bfloat16)
     output plus a float32 bias gives a float32 result; after `.half()` the bias is float16 and so is the result.
+
     `fused_epilogue=True` (default False: the line above): the bias add (when `use_bias`) and the activation, when it is
     `torch.relu`, `torch.nn.functional.relu` or an `nn.ReLU`, run inside the kernels' store -- y = act(sum + bias[f]) in fp32
     before the one rounding -- so the output has the INPUT's dtype (float16 in, float16 out: the next layer keeps its 16-bit loads
@@ -732,6 +752,7 @@ class DAUConv2d(nn.Module):
     pass (the bias gradient stays local, as below).  For float32 the output is bit for bit the unfused one.  Any other activation
     callable is applied after the op; strides > 1 slice the fused result (bias and ReLU commute with the slice); layers whose
     plan has no fused epilogue (shapes on the direct kernels, `dense_bf16=True`) run unfused.
+
     `channels_last` (None, True, False): what a channels_last input (`x.to(memory_format=torch.channels_last)`; a tensor whose
     strides also fit NCHW -- one channel, or H = W = 1 -- counts as contiguous) runs on.  True: the NHWC plan (DAU_FLAG_IO_NHWC) --
     the same kernels reading and writing [N][H][W][C], no copy of x, which is saved as it is, a channels_last output, and in backward
@@ -739,6 +760,7 @@ class DAUConv2d(nn.Module):
     of the contiguous call.  False: today's path: the input is made contiguous, the output is contiguous.  None (default): the
     NHWC plan for the dtypes where it measured faster than converting (`dau_conv._NHWC_BY_DEFAULT`).  Layers with
     `dense_bf16=True` and shapes that run on the direct kernels have no NHWC plan and convert, whatever the argument.
+
     `input_activation` (None): an activation applied to the INPUT, in front of the layer.  "relu", `torch.relu`,
     `torch.nn.functional.relu` or an `nn.ReLU` is fused into the layer (DAU_FLAG_INPUT_RELU): in a `Conv2d -> BatchNorm2d -> ReLU ->
     DAUConv2d` stack, drop the ReLU module and give the layer the BatchNorm output -- the kernels clamp x where they load it and mask
@@ -746,12 +768,14 @@ class DAUConv2d(nn.Module):
     for bit those of `layer(torch.relu(x))`.  Any other callable is applied in torch before the layer.  Works with channels_last,
     autocast, `.half()` / `.bfloat16()`, `fused_epilogue`, `residual=`, `strides > 1` and `process_group=`; layers whose plan cannot
     take the flag (`dense_bf16=True`, shapes on the direct kernels) run `torch.relu` in front.
+
     `process_group` (a torch.distributed group, or True for the default one): batch-sharded data parallelism INSIDE the
     layer's backward -- the raw parameter-gradient sums of the local shard are all-reduced (one flat [4,S,G,F] buffer, RCCL
     over xGMI with backend "nccl") while the input gradient is computed, and the elementwise tail runs on the reduced sums;
     weights / mu1 / mu2 / sigma gradients come out identical on every rank, averaged over the ranks (`grad_reduce="mean"`,
     the DistributedDataParallel convention) or summed (`"sum"`).  The bias gradient is ordinary autograd and is not exchanged
     here.  Wrapping such a layer in DistributedDataParallel as well is harmless but redundant (it averages identical values).
+
     torch.compile: a built layer (`in_channels=` given, or called once) traces into one opaque op, `torch.ops.dau_conv.conv`, with
     the offset clamp, the stride slice and an unfused bias / activation as ordinary traced ops around it; every combination above
     goes through that op, and a trainable sigma does not recompile.  A `process_group=` layer runs outside the graph (one graph
@@ -773,18 +797,7 @@ class DAUConv2d(nn.Module):
                  dense_outliers=False, channels_last=None, fused_epilogue=False, input_activation=None, dense_line=False,
                  dense_line_grads=False, **kwargs):
         super(DAUConv2d, self).__init__()
-        if dense_line_grads and not dau_unit_single_dim:
-            raise ValueError("dense_line_grads=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
-        if dense_line_grads and dense_split is not None and not dense_split:
-            raise ValueError("dense_line_grads=True excludes dense_split=False")
-        if dense_line_grads and dense_bf16:
-            raise ValueError("dense_line_grads=True excludes dense_bf16=True (DAU_FLAG_SPLIT_DOT_LINE excludes DAU_FLAG_DENSE_BF16)")
-        if dense_line and not dau_unit_single_dim:
-            raise ValueError("dense_line=True needs a single-dimension layer (DAUConv1d, or dau_unit_single_dim=True)")
-        if dense_line and dense_split is not None and not dense_split:
-            raise ValueError("dense_line=True excludes dense_split=False")
-        if dense_line and dense_bf16:
-            raise ValueError("dense_line=True excludes dense_bf16=True (DAU_FLAG_DENSE_SPLIT_LINE excludes DAU_FLAG_DENSE_BF16)")
+        _check_line_options(dau_unit_single_dim, dense_split, dense_bf16, dense_line, dense_line_grads)
         self.rank = 2
         self.filters = int(filters)
         du = (dau_units, dau_units) if isinstance(dau_units, int) else tuple(dau_units)
@@ -931,10 +944,7 @@ class DAUConv2d(nn.Module):
             dau_unit_border_bound=self.dau_unit_border_bound, dau_unit_single_dim=self.dau_unit_single_dim,
             dau_aggregation_forbid_positive_dim1=self.dau_aggregation_forbid_positive_dim1,
             dau_mu_interpolation=self.dau_mu_interpolation, unit_testing=self.unit_testing, data_format="NCHW",
-            name=self.name, check_offsets=self.check_offsets, algo=self.algo, dense_bf16=self.dense_bf16,
-            process_group=self.process_group, grad_reduce=self.grad_reduce, dense_split=self.dense_split,
-            dense_outliers=self.dense_outliers, channels_last=self.channels_last, dense_line=self.dense_line,
-            dense_line_grads=self.dense_line_grads)
+            name=self.name, **{option: getattr(self, option) for option in _ENGINE_OPTIONS})
         self.built = True
 
     def _var(self, key):
@@ -985,27 +995,26 @@ class DAUConv2d(nn.Module):
         if self.input_activation is not None and not self._input_relu:
             inputs = self.input_activation(inputs)
         in_act = "relu" if self._input_relu else None
+
+        def op(**epilogue):
+            return self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
+                                            input_activation=in_act, **epilogue)
         if self.fused_epilogue:
             # bias and ReLU inside the op's store; both commute with the slicing that emulates strides > 1
             relu = self.activation in (torch.relu, nn.functional.relu) or isinstance(self.activation, nn.ReLU)
             bias = self._parameters["bias"] if self.use_bias else None
             if residual is not None and self.strides > 1:
                 # the residual has the SAMPLED shape: the bias stays in the store, the add and the activation follow the slice
-                outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint, bias=bias,
-                                                   input_activation=in_act)
-                outputs = outputs[:, :, ::self.strides, ::self.strides] + residual
+                outputs = op(bias=bias)[:, :, ::self.strides, ::self.strides] + residual
                 return self.activation(outputs) if self.activation is not None else outputs
             # (a residual joins them in the store: act((sum + bias) + residual); one the op cannot fuse it adds in torch)
-            outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
-                                               bias=bias, activation="relu" if relu else None, residual=residual,
-                                               input_activation=in_act)
+            outputs = op(bias=bias, activation="relu" if relu else None, residual=residual)
             if self.strides > 1:
                 outputs = outputs[:, :, ::self.strides, ::self.strides]
             if self.activation is not None and not relu:
                 return self.activation(outputs)
             return outputs
-        outputs = self._dau_convolution_op(inputs, self.dau_weights, self.dau_mu1, self.dau_mu2, sigma_t, sigma_hint=hint,
-                                           input_activation=in_act)
+        outputs = op()
         # strides > 1 are emulated by sampling the stride-1 output (dau_conv.py:497-498)
         if self.strides > 1:
             outputs = outputs[:, :, ::self.strides, ::self.strides]
@@ -1083,6 +1092,32 @@ def get_scope_layer(scope):
     return _SCOPES[scope]
 
 
+def _slim(layer_class, inputs, filters, dau_units, max_kernel_size, data_format, activation_fn, normalizer_fn, normalizer_params,
+          fused_epilogue, reuse, outputs_collections, scope, **layer_kwargs):
+    """dau_conv2d / dau_conv1d: the layer of this scope -- a layer_class made with layer_kwargs (bias_initializer among them) the
+    first time -- applied to inputs, then the normalizer and the activation."""
+    if data_format not in [None, 'NCHW']:
+        raise ValueError('Invalid data_format: %r' % (data_format,))
+    if inputs.dim() != 4:
+        raise ValueError('DAU convolution not supported for input with rank', inputs.dim())
+    df = 'channels_first' if data_format and data_format.startswith('NC') else 'channels_last'
+    # fused_epilogue: the layer itself adds the bias and applies activation_fn (fused where it is a ReLU) -- unless a normalizer
+    # stands between them
+    fuse_act = bool(fused_epilogue) and normalizer_fn is None and activation_fn is not None
+    layer = _scoped_layer(scope, reuse, 'DAUConv', lambda name: layer_class(
+        filters, dau_units, max_kernel_size, data_format=df, activation=activation_fn if fuse_act else None,
+        fused_epilogue=fused_epilogue, use_bias=bool(not normalizer_fn and layer_kwargs["bias_initializer"]), unit_testing=False,
+        name=name, **layer_kwargs))
+    outputs = layer(inputs)
+    if normalizer_fn is not None:
+        outputs = normalizer_fn(outputs, **(normalizer_params or {}))
+    if activation_fn is not None and not fuse_act:
+        outputs = activation_fn(outputs)
+    if outputs_collections is not None:
+        outputs_collections.append(outputs)
+    return outputs
+
+
 def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learning_rate_factor=500, data_format=None,
                activation_fn=torch.relu, normalizer_fn=None, normalizer_params=None, weights_initializer=None,
                weights_regularizer=None, weights_constraint=None, mu1_initializer=None, mu1_regularizer=None,
@@ -1093,34 +1128,17 @@ def dau_conv2d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                trainable=True, scope=None, dense_outliers=False, fused_epilogue=False, input_activation_fn=None):
     """slim-style functional form of DAUConv2d.  Its variables live in a Python-side scope registry (_SCOPES), which Dynamo does not
     trace: dau_conv2d / dau_conv1d stay eager -- under torch.compile, build the model from the DAUConv2d / DAUConv1d modules."""
-    if data_format not in [None, 'NCHW']:
-        raise ValueError('Invalid data_format: %r' % (data_format,))
-    if inputs.dim() != 4:
-        raise ValueError('DAU convolution not supported for input with rank', inputs.dim())
-    df = 'channels_first' if data_format and data_format.startswith('NC') else 'channels_last'
-    # fused_epilogue: the layer itself adds the bias and applies activation_fn (fused where it is a ReLU) -- unless a normalizer
-    # stands between them
-    fuse_act = bool(fused_epilogue) and normalizer_fn is None and activation_fn is not None
-    layer = _scoped_layer(scope, reuse, 'DAUConv', lambda name: DAUConv2d(
-        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=activation_fn if fuse_act else None,
-        fused_epilogue=fused_epilogue,
-        use_bias=bool(not normalizer_fn and biases_initializer), mu_learning_rate_factor=mu_learning_rate_factor,
+    return _slim(
+        DAUConv2d, inputs, filters, dau_units, max_kernel_size, data_format, activation_fn, normalizer_fn, normalizer_params,
+        fused_epilogue, reuse, outputs_collections, scope, strides=stride, mu_learning_rate_factor=mu_learning_rate_factor,
         weight_initializer=weights_initializer, mu1_initializer=mu1_initializer, mu2_initializer=mu2_initializer,
         sigma_initializer=sigma_initializer, bias_initializer=biases_initializer, weight_regularizer=weights_regularizer,
         mu1_regularizer=mu1_regularizer, mu2_regularizer=mu2_regularizer, sigma_regularizer=sigma_regularizer,
         bias_regularizer=biases_regularizer, weight_constraint=weights_constraint, mu1_constraint=mu1_constraint,
         mu2_constraint=mu2_constraint, sigma_constraint=sigma_constraint, bias_constraint=biases_constraint,
         dau_unit_border_bound=dau_unit_border_bound, dau_sigma_trainable=dau_sigma_trainable,
-        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
-        dense_outliers=dense_outliers, input_activation=input_activation_fn))
-    outputs = layer(inputs)
-    if normalizer_fn is not None:
-        outputs = normalizer_fn(outputs, **(normalizer_params or {}))
-    if activation_fn is not None and not fuse_act:
-        outputs = activation_fn(outputs)
-    if outputs_collections is not None:
-        outputs_collections.append(outputs)
-    return outputs
+        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, dense_outliers=dense_outliers,
+        input_activation=input_activation_fn)
 
 
 def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learning_rate_factor=500, data_format=None,
@@ -1133,33 +1151,16 @@ def dau_conv1d(inputs, filters, dau_units, max_kernel_size, stride=1, mu_learnin
                dense_outliers=False, fused_epilogue=False, input_activation_fn=None, dense_line=False, dense_line_grads=False):
     """slim-style functional form of DAUConv1d; like dau_conv2d it keeps its variables in the Python-side scope registry and stays
     eager under torch.compile."""
-    if data_format not in [None, 'NCHW']:
-        raise ValueError('Invalid data_format: %r' % (data_format,))
-    if inputs.dim() != 4:
-        raise ValueError('DAU convolution not supported for input with rank', inputs.dim())
-    df = 'channels_first' if data_format and data_format.startswith('NC') else 'channels_last'
-    fuse_act = bool(fused_epilogue) and normalizer_fn is None and activation_fn is not None      # (as dau_conv2d)
-    layer = _scoped_layer(scope, reuse, 'DAUConv', lambda name: DAUConv1d(
-        filters, dau_units, max_kernel_size, strides=stride, data_format=df, activation=activation_fn if fuse_act else None,
-        fused_epilogue=fused_epilogue,
-        use_bias=bool(not normalizer_fn and biases_initializer), mu_learning_rate_factor=mu_learning_rate_factor,
+    return _slim(
+        DAUConv1d, inputs, filters, dau_units, max_kernel_size, data_format, activation_fn, normalizer_fn, normalizer_params,
+        fused_epilogue, reuse, outputs_collections, scope, strides=stride, mu_learning_rate_factor=mu_learning_rate_factor,
         weight_initializer=weights_initializer, mu1_initializer=mu1_initializer, sigma_initializer=sigma_initializer,
         bias_initializer=biases_initializer, weight_regularizer=weights_regularizer, mu1_regularizer=mu1_regularizer,
         sigma_regularizer=sigma_regularizer, bias_regularizer=biases_regularizer, weight_constraint=weights_constraint,
         mu1_constraint=mu1_constraint, sigma_constraint=sigma_constraint, dau_unit_border_bound=dau_unit_border_bound,
-        dau_sigma_trainable=dau_sigma_trainable,
-        dau_aggregation_forbid_positive_dim1=dau_aggregation_forbid_positive_dim1,
-        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, unit_testing=False, name=name,
-        dense_outliers=dense_outliers, input_activation=input_activation_fn, dense_line=dense_line,
-        dense_line_grads=dense_line_grads))
-    outputs = layer(inputs)
-    if normalizer_fn is not None:
-        outputs = normalizer_fn(outputs, **(normalizer_params or {}))
-    if activation_fn is not None and not fuse_act:
-        outputs = activation_fn(outputs)
-    if outputs_collections is not None:
-        outputs_collections.append(outputs)
-    return outputs
+        dau_sigma_trainable=dau_sigma_trainable, dau_aggregation_forbid_positive_dim1=dau_aggregation_forbid_positive_dim1,
+        dau_mu_interpolation=dau_mu_interpolation, trainable=trainable, dense_outliers=dense_outliers,
+        input_activation=input_activation_fn, dense_line=dense_line, dense_line_grads=dense_line_grads)
 
 
 # the opaque ops of the torch.compile path; imported last: _ops.py uses this module's helpers

@@ -56,6 +56,50 @@ def test_import_registers_both_ops_and_leaves_the_gpu_alone():
     assert torch.cuda.is_initialized() == was
 
 
+# _settings() keywords per trailing argument of the ops: every value the argument takes, the packed pairs in full (dense_line rides
+# in dense_split, dense_line_grads in algo; both need a single-dimension layer)
+_ROUND_TRIP = {
+    "number_units_ignore": [dict(number_units_ignore=v) for v in (0, 1, 3)],
+    "kernel_size": [dict(kernel_size=v) for v in (9, 17, 33)],
+    "unit_testing": [dict(unit_testing=v) for v in (False, True)],
+    "mu_learning_rate_factor": [dict(mu_learning_rate_factor=v) for v in (1.0, 500.0, 0.25)],
+    "single_dim_kernel": [dict(single_dim_kernel=v) for v in (False, True)],
+    "forbid_positive_dim1": [dict(forbid_positive_dim1=v) for v in (False, True)],
+    "use_interpolation": [dict(use_interpolation=v) for v in (True, False)],
+    "algo": [dict(algo=a, dense_line_grads=g, single_dim_kernel=g) for a in (0, 1, 2) for g in (False, True)],
+    "dense_bf16": [dict(dense_bf16=v) for v in (False, True)],
+    "dense_split": [dict(dense_split=s, dense_line=line, single_dim_kernel=line)
+                    for s, line in ((None, False), (False, False), (True, False), (None, True), (True, True))],
+    "dense_outliers": [dict(dense_outliers=v) for v in (False, True)],
+    "channels_last": [dict(channels_last=v) for v in (None, False, True)],
+    "check_offsets": [dict(check_offsets=v) for v in ("async", True, False)],
+}
+
+
+@pytest.mark.parametrize("name", _ORDER)
+def test_settings_round_trip_through_the_ops_arguments(name):
+    """_run_settings(w, sigma, False, *encode_settings(st)) gives st back, key for key and type for type, for every value of every
+    trailing argument; the values of an argument all encode differently, and only in that argument's slot."""
+    import importlib
+    from dau_conv import _ops
+    impl = importlib.import_module("dau_conv.dau_conv")
+    assert tuple(s.name for s in _ops._SETTINGS) == _ORDER == tuple(_ROUND_TRIP) and _ops._N_ARGS == 9 + len(_ORDER)
+    sigma, w = torch.full((1,), 0.5), torch.zeros(1, S, G, F)
+    plain = _ops.encode_settings(impl._settings(sigma, num_output=F))
+    slot, seen = _ORDER.index(name), set()
+    for kw in _ROUND_TRIP[name]:
+        st = impl._settings(sigma, num_output=F, **kw)
+        enc = _ops.encode_settings(st)
+        assert len(enc) == len(_ORDER)
+        # (single_dim_kernel, which the line options need, has a slot of its own)
+        assert all(enc[i] == plain[i] for i in range(len(enc)) if i != slot and _ORDER[i] != "single_dim_kernel"), (kw, enc)
+        seen.add(enc[slot])
+        back = _ops._run_settings(w, sigma, False, *enc)
+        assert back == st and all(type(back[k]) is type(st[k]) for k in st), (kw, back, st)
+        assert _ops._run_settings(w, sigma, True, *enc) == dict(st, input_relu=True)
+    assert len(seen) == len(_ROUND_TRIP[name])
+
+
 def test_import_does_not_pull_in_dynamo():
     import subprocess
     code = ("import sys; sys.path[:0] = %r; import dau_conv, torch; "

@@ -146,11 +146,11 @@ def test_the_flag_is_part_of_the_plan_key_and_refusals_fall_back():
     assert not got.input_relu and got.info["gather_dense_bf16"]
     # the direct kernels: refused once, remembered
     std = impl._settings(sigma, num_output=16, kernel_size=9, sigma_hint=0.5, algo=_capi.ALGO_DIRECT)
-    n = len(impl._INPUT_RELU_REFUSED)
+    n = len(impl._REFUSED)
     got = impl._get_plan(x, w, dict(std, input_relu=True))
     assert not got.input_relu and got.info["algo_forward"] == _capi.ALGO_DIRECT
-    assert len(impl._INPUT_RELU_REFUSED) == n + 1
-    assert impl._get_plan(x, w, dict(std, input_relu=True)) is got and len(impl._INPUT_RELU_REFUSED) == n + 1
+    assert len(impl._REFUSED) == n + 1
+    assert impl._get_plan(x, w, dict(std, input_relu=True)) is got and len(impl._REFUSED) == n + 1
 
 
 def test_dau_conv_refuses_other_input_activations():
